@@ -11,7 +11,14 @@ Adam, on 22 synthetic clips (3x16x112x112, fp32) per GPU with random-init weight
 averaged across ranks by the bucketed RCCL all-reduce of ``ddp.GradientSync``, overlapped
 with backward.  Inputs are resident in HBM before the timed region (``--input u8`` instead
 streams uint8 frames over PCIe every step and runs the clip transform on the device: the
-PCIe-inclusive rate, never the headline).  Rank 0 prints ONE JSON line.  Extra objects on it:
+PCIe-inclusive rate, never the headline).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (``value``, ``ms_per_step``, per-step
+device times, the host's lead, the allocator's requests inside the timed region).  ``--dump-outputs DIR``
+then also writes what the last timed step computed as ``DIR/<name>.npy``: the embeddings and loss it
+returned and a fixed, seeded sample of the model state it left (``dump_outputs``).  ``--full`` adds the secondary
+measurements, each after the timed region (``--no-cpu-baseline`` / ``--no-phases`` / ``--no-extras`` drop
+single ones):
 
 * ``roofline``  : the dominant kernel (the fp32-MFMA convolution on the 64->144 1x3x3 shape,
   41 % of forward FLOPs; kw taps in Winograd F(4,3) form).  ``achieved`` / ``frac`` are the
@@ -21,7 +28,9 @@ PCIe-inclusive rate, never the headline).  Rank 0 prints ONE JSON line.  Extra o
   direct-convolution (algorithmic) rate SURVEY 8d counts is ``algorithmic_tflops``;
 * ``cpu_baseline``: the CPU oracle (oracle/restatement.py, pinned to the reference) timed on
   this host's cores on a bounded sample (N = 2 clips), rank 0 at N = 1 only;
-* ``host_enqueue_ms``: host time to queue one step's launches (no device sync inside);
+* ``host_enqueue_ms.idle_queue``: host time to queue one step's launches (no device sync inside);
+* ``phases``: forward-only and forward+backward times, N = 1 only;
+* ``resident_input_same_process``: with ``--input u8``, the resident-input rate of the same process;
 * ``extra``: after everything else, N = 1 only: BASELINE.json configs[3] (C3D training step),
   configs[4]'s per-GPU work (32-frame bf16 ``evaluate()`` protocol) and the mixed-precision (bf16)
   training step of SURVEY row a12 (``extra.train_bf16``: never the headline).
@@ -31,6 +40,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import random
 import statistics
 import sys
 import threading
@@ -203,11 +213,21 @@ def parse(argv=None):
     ap.add_argument("--input-hw", default="128x171", help="frame size of the uint8 source clips for --input u8")
     ap.add_argument("--timeout", type=float, default=DEFAULT_TIMEOUT_S,
                     help="seconds after which ranks that are still running are stopped and the run fails")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C3D / 32-frame bf16 eval legs after the timed region")
-    ap.add_argument("--no-phases", action="store_true", help="skip the forward-only / forward+backward legs (counter passes over whole steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements after the timed region: roofline of the dominant kernel, idle-queue "
+                         "host enqueue time, forward / forward+backward phases, CPU baseline, the u8 run's resident reference "
+                         "and the extra.* legs (C3D, 32-frame bf16 eval, bf16 training steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy: embeddings, loss and a seeded sample of "
+                         "the model state after the step (float32), and the sample's positions (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the C3D / 32-frame bf16 eval legs after the timed region")
+    ap.add_argument("--no-phases", action="store_true", help="with --full: skip the forward-only / forward+backward legs (counter passes over whole steps)")
     ap.add_argument("--cpu-steps", type=int, default=12)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def log(msg: str) -> None:
@@ -340,6 +360,41 @@ def allocator_delta(a, b):
     return {"device_allocs": b["device_allocs"] - a["device_allocs"], "device_frees": b["device_frees"] - a["device_frees"],
             "alloc_retries": b["alloc_retries"] - a["alloc_retries"], "reserved_mb_before": a["reserved_mb"],
             "reserved_mb_after": b["reserved_mb"]}
+
+
+STATE_SAMPLE = 1 << 20             # model-state values written by --dump-outputs (4 MB of float32)
+
+
+def dump_outputs(out_dir: str, y, loss, model, seed: int = 0):
+    """``--dump-outputs``: what the last timed step computed, as ``.npy`` files in ``out_dir``: the ``(N, 300)`` embeddings
+    and the loss ``train_step`` returned (float32), and ``state_sample``, up to ``STATE_SAMPLE`` values (float32) of the model
+    state it left (every floating ``state_dict`` entry in key order, flattened and concatenated: updated weights and BatchNorm
+    running statistics) at the sorted positions ``state_sample_index`` (float64) drawn from a generator seeded with ``seed``, so
+    two runs with the same arguments sample the same positions.  Returns ``{name: shape}``."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    state = [t.detach().reshape(-1) for t in model.state_dict().values() if t.is_floating_point()]
+    total = sum(t.numel() for t in state)
+    idx = torch.unique(torch.randint(0, total, (STATE_SAMPLE,), generator=torch.Generator().manual_seed(seed)))   # sorted
+    flat = torch.cat([t.float() for t in state])
+    arrays = {"embeddings": y.detach().float().cpu().numpy(),
+              "loss": loss.detach().float().reshape(1).cpu().numpy(),
+              "state_sample": flat[idx.to(flat.device)].cpu().numpy(),
+              "state_sample_index": idx.numpy().astype(np.float64)}
+    del flat
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def resident_reference_entry(resident_ms, clips_per_step: int, u8_ms: float):
+    """``resident_input_same_process`` of an ``--input u8`` line: the resident-input step time measured in the same process
+    (``resident_ms``), its rate, and the u8 step's time relative to it.  None when it was not measured (a run without ``--full``).
+    Pure function (tested on CPU)."""
+    if resident_ms is None:
+        return None
+    return {"ms_per_step": round(resident_ms, 3), "value": round(clips_per_step / (resident_ms * 1e-3), 3), "unit": "clips/s",
+            "u8_over_resident": round(resident_ms / u8_ms, 4)}
 
 
 def run_queued(step_fn, steps):
@@ -650,6 +705,7 @@ def main():
             dist.init_process_group(backend)
 
     torch.manual_seed(0)
+    random.seed(0)                                       # --input u8: the training transform draws its crops and flips from `random`
     model = network.get_network(SimpleNamespace(network=args.network, fixconvs=False, nopretrained=False))
     model.load_state_dict(synthetic.keyed_state_dict(model.state_dict(), seed=0))
     model.to(dev).train()
@@ -693,7 +749,7 @@ def main():
             torch.cuda.synchronize()
         log(f"warm-up step {i} " + ("done" if i == 0 else "queued"))
     dom = DOMINANT.get(args.network)
-    timer = ops.KernelTimer("conv_fwd", dict(dom["geometry"], N=args.batch)) if dom else None
+    timer = ops.KernelTimer("conv_fwd", dict(dom["geometry"], N=args.batch)) if dom and args.full else None
     ops.KERNEL_TIMER = timer
     barrier()
     alloc_before = allocator_snapshot(dev)
@@ -701,9 +757,9 @@ def main():
     host_marks = []
     t0 = time.perf_counter()
     step_marks[0].record()
-    loss = None
+    y_last = loss = None
     for i in range(args.steps):
-        _, loss = step()
+        y_last, loss = step()
         step_marks[i + 1].record()
         host_marks.append(time.perf_counter() - t0)
     t_queued = host_marks[-1] if host_marks else 0.0     # every launch of the K steps is queued; nothing was awaited (but the pacer)
@@ -716,6 +772,12 @@ def main():
     host_step_ms = [1e3 * (b - a) for a, b in zip([0.0] + host_marks[:-1], host_marks)]
     log(f"timed {args.steps} steps in {elapsed:.3f}s (host had queued them after {t_queued:.3f}s, {host_lead_steps} step(s) ahead of the device; "
         f"allocator in the timed region: {alloc_timed})")
+    # (before any other step changes the model: the u8 run's resident reference and --full's legs run more)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, y_last, loss, model)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
+
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -723,7 +785,7 @@ def main():
 
     # --input u8: the resident-input rate of the SAME process and device right after (devices of the pool differ by a few percent)
     resident_ref = None
-    if feeder is not None:
+    if feeder is not None and args.full:
         xr = synthetic.synthetic_clips(args.batch, FRAMES, SIZE, rank=rank).to(dev)
         for _ in range(2):
             train.train_step(model, optimizer, criterion, xr, z, sync, pacer=pacer)
@@ -736,19 +798,21 @@ def main():
         del xr
 
     # host time to queue ONE step on an idle queue (no back-pressure from a full HIP queue): after the timed region
-    enqueue = []
-    for _ in range(3):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        step()
-        enqueue.append(time.perf_counter() - t)
-    barrier()
-    host_enqueue_ms = 1e3 * statistics.median(enqueue)
+    host_enqueue_ms = None
+    if args.full:
+        enqueue = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            step()
+            enqueue.append(time.perf_counter() - t)
+        barrier()
+        host_enqueue_ms = 1e3 * statistics.median(enqueue)
 
     # SURVEY 8d also asks for the forward-only and forward+backward times: measured AFTER the timed
     # region (N = 1 only), never part of `value`
     phases = None
-    if world == 1 and feeder is None and not args.no_phases:
+    if world == 1 and feeder is None and args.full and not args.no_phases:
         def timed(fn, iters=5):
             fn()
             torch.cuda.synchronize()
@@ -798,9 +862,7 @@ def main():
                        "final_loss": float(loss.item()) if loss is not None else None},
             # host side of a step: time until its last launch is queued.  `in_timed_region` includes any back-pressure of a
             # full HIP queue (the host runs ahead of the GPU); `idle_queue` is one step queued right after a device sync.
-            "host_enqueue_ms": {"idle_queue": round(host_enqueue_ms, 3),
-                                "in_timed_region": round(1e3 * t_queued / args.steps, 3),
-                                "frac_of_step": round(host_enqueue_ms / ms_per_step, 3),
+            "host_enqueue_ms": {"in_timed_region": round(1e3 * t_queued / args.steps, 3),
                                 "cores_of_this_rank": len(cores) if cores else usable_cores(),
                                 # the first steps of the timed region show the host's own cost (the queue is empty: nothing holds it
                                 # back); once it is `pacer_depth` steps ahead it waits for the device at the head of every step
@@ -812,12 +874,17 @@ def main():
                                   "max": round(max(step_dev_ms), 3)},
             "allocator_in_timed_region": alloc_timed,
             "degraded": False,                           # True: a secondary leg (extra.*) failed; its error is in the leg and on stderr
+            "full": bool(args.full),
         }
+        if host_enqueue_ms is not None:
+            out["host_enqueue_ms"].update(idle_queue=round(host_enqueue_ms, 3), frac_of_step=round(host_enqueue_ms / ms_per_step, 3))
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
         if feeder is not None:
             out["config"]["pcie_bytes_per_step"] = int(feeder.bytes_per_step)
-            out["resident_input_same_process"] = {"ms_per_step": round(resident_ref, 3),
-                                                  "value": round(world * args.batch / (resident_ref * 1e-3), 3), "unit": "clips/s",
-                                                  "u8_over_resident": round(resident_ref / ms_per_step, 4)}
+            resident = resident_reference_entry(resident_ref, world * args.batch, ms_per_step)
+            if resident is not None:
+                out["resident_input_same_process"] = resident
             out["config"]["input_pipeline"] = ("pinned uint8 (N,T,H,W,3) -> hipMemcpyAsync on a copy stream, two slots -> "
                                                "zsv_clip_transform (auxiliary/transforms.py:41-56) -> model")
         if sync is not None:
@@ -832,9 +899,9 @@ def main():
             out["roofline"] = roofline_entry(dom, args.batch, timer.durations_ms())
         if phases is not None:
             out["phases"] = phases
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.network, args.cpu_steps)
-        if world == 1 and not args.no_extras and args.network == "r2plus1d_18" and feeder is None:
+        if world == 1 and args.full and not args.no_extras and args.network == "r2plus1d_18" and feeder is None:
             del model, optimizer, x
             torch.cuda.empty_cache()
             extra = {}

@@ -504,6 +504,56 @@ def run_autocast_bf16_c3d():
     return out
 
 
+PIN_NETWORKS = ("r2plus1d_18", "r3d_18", "c3d")
+
+
+def pin_case(name: str):
+    """Inputs of ``tests/test_oracle.py::test_restatement_is_pinned_to_the_imported_reference`` for one network: keyed weights
+    (seed 5, BatchNorm jitter), clips (seed 8), train mode except C3D (eval)."""
+    size, frames, n = (112, 16, 1) if name == "c3d" else (32, 4, 2)
+    return dict(weights_seed=5, clip_seed=8, n=n, frames=frames, size=size, train=name != "c3d")
+
+
+def run_restatement_pin():
+    """``restatement_pin.npz``: what the REFERENCE's networks compute on the pinning test's inputs -- the ``state_dict`` keys,
+    the embeddings, which parameters get no gradient, and per live parameter the fp64 norm of its gradient and its values at
+    ``sample_idx`` -- after checking that the restatement reproduces the reference bit for bit on the same inputs."""
+    ref_network, _ = import_reference()
+    out = {}
+    for name in PIN_NETWORKS:
+        c = pin_case(name)
+        opt = R.make_opt(name)
+        ref, mine = ref_network.get_network(opt), R.oracle_network(opt)
+        assert list(ref.state_dict().keys()) == list(mine.state_dict().keys()), name
+        weights = S.keyed_state_dict(ref.state_dict(), seed=c["weights_seed"], bn_jitter=True)
+        ref.load_state_dict(weights)
+        mine.load_state_dict(weights)
+        x = S.synthetic_clips(c["n"], c["frames"], c["size"], seed=c["clip_seed"])
+        for m in (ref, mine):
+            m.train(c["train"])
+        ya, yb = R.embed(ref, x), R.embed(mine, x)
+        assert torch.equal(ya, yb), name
+        ya.sum().backward()
+        yb.sum().backward()
+        names, norms, samples = [], [], []
+        for (k, p), (_, q) in zip(ref.named_parameters(), mine.named_parameters()):
+            assert (p.grad is None) == (q.grad is None), k
+            if p.grad is not None:
+                assert torch.equal(p.grad, q.grad), k
+                g = p.grad.detach().reshape(-1)
+                names.append(k)
+                norms.append(g.double().norm().item())
+                samples.append(g[torch.from_numpy(sample_idx(g.numel()))].numpy())
+        out[f"{name}_state_keys"] = np.array(list(ref.state_dict().keys()))
+        out[f"{name}_emb_f32"] = ya.detach().numpy()
+        out[f"{name}_dead_params"] = np.array([k for k, p in ref.named_parameters() if p.grad is None], dtype=str)
+        out[f"{name}_grad_names"] = np.array(names)
+        out[f"{name}_grad_norm_f64"] = np.array(norms, dtype=np.float64)
+        out[f"{name}_grad_sample_f32"] = np.concatenate(samples).astype(np.float32)
+        out.update({f"{name}_meta_{k}": np.array(v) for k, v in c.items()})
+    return out
+
+
 def main():
     torch.set_num_threads(os.cpu_count() or 8)
     ref_network, _ = import_reference()
@@ -511,7 +561,8 @@ def main():
     only = set(sys.argv[1:])
     for name, fn in (("transforms", run_transforms), ("transforms_t4", run_transforms_t4), ("accuracy", run_accuracy),
                      ("surface_extras", run_surface_extras), ("r2plus1d_t32_batch", run_t32_batch),
-                     ("r2plus1d_small_autocast_bf16", run_autocast_bf16), ("c3d_autocast_bf16", run_autocast_bf16_c3d)):
+                     ("r2plus1d_small_autocast_bf16", run_autocast_bf16), ("c3d_autocast_bf16", run_autocast_bf16_c3d),
+                     ("restatement_pin", run_restatement_pin)):
         if only and name not in only:
             continue
         t0 = time.time()

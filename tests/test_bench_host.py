@@ -87,3 +87,47 @@ def test_parse_defaults_finish_within_minutes():
     a = bench.parse([])
     assert (a.gpus, a.steps, a.warmup, a.input, a.network) == (1, 20, 5, "resident", "r2plus1d_18")
     assert 60 <= a.timeout <= 900
+
+
+def test_plain_run_is_lean_and_full_is_opt_in():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    b = bench.parse(["--full", "--dump-outputs", "out", "--no-extras"])
+    assert b.full and b.dump_outputs == "out" and b.no_extras
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        try:
+            bench.parse(bad)
+        except SystemExit as e:
+            assert e.code != 0
+        else:
+            raise AssertionError(bad)
+
+
+def test_dump_outputs_writes_the_step_outputs_and_a_seeded_state_sample(tmp_path, monkeypatch):
+    """--dump-outputs: embeddings and loss as returned, plus a sample of the model state at positions that do not change
+    between runs; float32 / float64 only, bounded in size."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "STATE_SAMPLE", 500)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(40, 30), torch.nn.BatchNorm1d(30))
+    y, loss = torch.randn(4, 300), torch.tensor(0.25)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), y, loss, model)
+    bench.dump_outputs(str(tmp_path / "b"), y, loss, model)
+    assert set(shapes) == {"embeddings", "loss", "state_sample", "state_sample_index"}
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in shapes}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["embeddings"], y.numpy()) and got["loss"].tolist() == [0.25]
+    flat = torch.cat([t.reshape(-1).float() for t in model.state_dict().values() if t.is_floating_point()]).numpy()
+    idx = got["state_sample_index"].astype(np.int64)
+    assert 0 < len(idx) <= 500 and np.all(np.diff(idx) > 0) and idx[-1] < flat.size
+    assert np.array_equal(got["state_sample"], flat[idx])
+    assert np.array_equal(np.load(tmp_path / "b" / "state_sample_index.npy"), got["state_sample_index"])
+
+
+def test_u8_line_without_the_resident_reference():
+    """A plain `--input u8` run does not measure the resident-input reference (it is a --full leg): its entry is absent,
+    not a crash; with the reference measured, the entry is the same-process comparison."""
+    assert bench.resident_reference_entry(None, 22, 40.0) is None
+    r = bench.resident_reference_entry(38.5, 22, 40.0)
+    assert r == {"ms_per_step": 38.5, "value": round(22 / 0.0385, 3), "unit": "clips/s", "u8_over_resident": round(38.5 / 40.0, 4)}

@@ -9,7 +9,6 @@ import torch
 
 from helpers import load_golden
 from oracle import transforms_oracle as TO
-from oracle.reference_import import reference_available
 from zeroshotvideoclassification_amd import preprocess
 
 
@@ -37,16 +36,6 @@ def test_restatement_and_draw_order_reproduce_the_reference_fixtures():
         assert preprocess.ClipTransform(True).draw_params(1, hres, wres) == [(ci, cj, 0)]
         n += 1
     assert n == 4
-
-
-@pytest.mark.skipif(not reference_available(), reason="/root/reference exists only in the build container")
-def test_fixtures_are_outputs_of_the_imported_reference():
-    from oracle.reference_import import import_reference_transforms
-    RT = import_reference_transforms()
-    for h, w, clip, val, trn, (seed, i, j, f) in _golden_cases():
-        assert torch.equal(RT.get_transform(True)(clip), val)
-        random.seed(seed)
-        assert torch.equal(RT.get_transform(False)(clip), trn)
 
 
 @pytest.mark.gpu
@@ -87,15 +76,6 @@ def test_restatement_reproduces_the_multi_frame_fixtures():
         assert torch.equal(TO.clip_transform(clip, i, j, bool(f)), want)
         n += 1
     assert n == 2
-
-
-@pytest.mark.skipif(not reference_available(), reason="/root/reference exists only in the build container")
-def test_multi_frame_fixtures_are_outputs_of_the_imported_reference():
-    from oracle.reference_import import import_reference_transforms
-    RT = import_reference_transforms()
-    for kind, h, w, t, clip, want, (seed, i, j, f) in _golden_t4_cases():
-        random.seed(seed)
-        assert torch.equal(RT.get_transform(kind == "val")(clip), want)
 
 
 @pytest.mark.gpu
