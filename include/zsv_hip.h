@@ -179,6 +179,21 @@ int zsv_bn_bwd(const float* dy, const float* x, const float* y, int32_t N, int32
                const float* gamma, const float* beta, const float* save_mean, const float* save_invstd,
                int fuse_relu, float* dx, float* d_residual, float* dgamma, float* dbeta,
                void* workspace, size_t workspace_bytes, void* stream);
+/* Backward of the eval-mode (frozen statistics) fused op, y = relu?(a*x + b (+ residual)) with a = gamma / sqrt(running_var + eps),
+ * b = beta - running_mean * a: g = dy * mask, dx = a * g, d_residual = g (when != NULL), dgamma = sum g * xhat with
+ * xhat = (x - running_mean) / sqrt(running_var + eps), dbeta = sum g.  ONE pass over the tensors (no mean-subtraction terms),
+ * then a C-wave finalize of the fixed-order partials (bitwise reproducible).  fuse_relu as zsv_bn_bwd (2: mask recomputed from
+ * x with zsv_bn_fwd_eval's / zsv_bn_eval_coeffs' exact fma).  dgamma and dbeta both NULL: no reduction at all, and neither the
+ * workspace nor x (with fuse_relu != 2) is read.  Workspace: zsv_bn_workspace_bytes(N, C, S). */
+int zsv_bn_bwd_eval(const float* dy, const float* x, const float* y, int32_t N, int32_t C, int32_t S,
+                    const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                    int fuse_relu, float* dx, float* d_residual, float* dgamma, float* dbeta,
+                    void* workspace, size_t workspace_bytes, void* stream);
+/* Frozen (eval-mode) BatchNorm feeding a convolution that applies it: coef = [2][coef_pitch] (scale row a, shift row b as in
+ * zsv_bn_bwd_eval; entries C .. coef_pitch-1 are 0) for zsv_conv3d_fwd_pre / zsv_conv3d_wgrad_pre, from the running statistics.
+ * Nothing else is written.  The backward is zsv_bn_bwd_eval with fuse_relu = 2. */
+int zsv_bn_eval_coeffs(int32_t C, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                       float eps, float* coef, int32_t coef_pitch, void* stream);
 
 /* ---- elementwise -------------------------------------------------------------- */
 /* nn.ReLU / F.relu (resnet.py:49; network.py:147-166,614). */
@@ -310,6 +325,20 @@ int zsv_bn_cl_fwd_train_stats(const void* z, const void* residual, int64_t R, in
 int zsv_bn_cl_bwd(const void* dy, const void* y, const void* z, int64_t R, int32_t C, const float* gamma, const float* save_mean,
                   const float* save_invstd, const float* fwd_coef, int relu_mask, void* dz, void* g_out, float* dgamma, float* dbeta,
                   void* workspace, size_t workspace_bytes, void* stream);
+/* Eval-mode (frozen statistics) BatchNorm3d on channels-last bf16, statistics and affine fp32 (frozen-BatchNorm fine-tuning under
+ * autocast):
+ * zsv_bn_cl_fwd_eval: coef = [4][Cp] floats (a = gamma/sqrt(running_var + eps), b = beta - running_mean*a, invstd, running_mean;
+ *   pad channels 0) and y = relu?(fma(z, a, b) (+ residual)) rounded once to bf16.  No statistics pass; the running statistics
+ *   are only read.  Keep coef for the backward.
+ * zsv_bn_cl_bwd_eval: ONE pass: g = dy * mask (relu_mask: y > 0 with y != NULL, else fma(z, a, b) > 0 -- the forward's exact
+ *   mask), dz = a*g (bf16), g_out = g (may be NULL); with dgamma and/or dbeta (C floats, may be NULL) fixed-order partials of
+ *   sum g, sum g*z in the workspace (zsv_bn_cl_workspace_bytes(R, C)) and a finalize: dbeta = sum g,
+ *   dgamma = invstd * (sum g*z - running_mean * sum g).  Neither: no reduction, no workspace, z read only for the mask. */
+int zsv_bn_cl_fwd_eval(const void* z, const void* residual, int64_t R, int32_t C, const float* gamma, const float* beta,
+                       const float* running_mean, const float* running_var, float eps, int fuse_relu, void* y, float* coef,
+                       void* stream);
+int zsv_bn_cl_bwd_eval(const void* dy, const void* y, const void* z, int64_t R, int32_t C, const float* coef, int relu_mask, void* dz,
+                       void* g_out, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
 /* Weight gradient of a convolution from channels-last bf16 operands (x [N][Ti][Hi][Wi][CinP], dz [N][To][Ho][Wo][CoutP]) with
  * fp32 accumulation: dw (Cout, Cin, kT, kH, kW) fp32 -- aten::convolution_backward's weight gradient under autocast
  * (resnet.py:40-52 1x3x3 / 3x1x1 incl. the strided ones, resnet.py:23-30 3x3x3, resnet.py:270 1x1x1).  The workspace holds

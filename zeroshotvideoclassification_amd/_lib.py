@@ -63,6 +63,9 @@ SIGNATURES = {
                                 c_size_t, _P]),
     "zsv_bn_bwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P,
                            c_size_t, _P]),
+    "zsv_bn_bwd_eval": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_float, c_int, _P, _P, _P, _P, _P,
+                                c_size_t, _P]),
+    "zsv_bn_eval_coeffs": (c_int, [c_int32, _P, _P, _P, _P, c_float, _P, c_int32, _P]),
     "zsv_relu_fwd": (c_int, [_P, _P, c_int64, _P]),
     "zsv_relu_bwd": (c_int, [_P, _P, _P, c_int64, _P]),
     "zsv_relu_bwd_bias": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, c_size_t, _P]),
@@ -92,6 +95,8 @@ SIGNATURES = {
     "zsv_conv3d_bf16_stat_rows": (c_int32, [POINTER(ConvDesc)]),
     "zsv_conv3d_bf16_fwd_stats": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, c_int32, _P, _P]),
     "zsv_bn_cl_bwd": (c_int, [_P, _P, _P, c_int64, c_int32, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "zsv_bn_cl_fwd_eval": (c_int, [_P, _P, c_int64, c_int32, _P, _P, _P, _P, c_float, c_int, _P, _P, _P]),
+    "zsv_bn_cl_bwd_eval": (c_int, [_P, _P, _P, c_int64, c_int32, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "zsv_conv3d_bf16_wgrad_workspace_bytes": (c_size_t, [POINTER(ConvDesc)]),
     "zsv_conv3d_bf16_wgrad": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, c_size_t, _P]),
     "zsv_maxpool3d_bf16_bwd": (c_int, [_P, _P] + [c_int32] * 14 + [_P, _P]),

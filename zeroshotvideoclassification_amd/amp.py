@@ -168,6 +168,40 @@ def bn_cl_bwd(dy: torch.Tensor, y: Optional[torch.Tensor], z: torch.Tensor, bn: 
     return dz, g, dgamma, dbeta
 
 
+def bn_cl_fwd_eval(z: torch.Tensor, bn: nn.BatchNorm3d, residual: Optional[torch.Tensor], relu: bool):
+    """Eval-mode (frozen) ``BatchNorm3d`` (+ residual) (+ ReLU) on a channels-last bf16 tensor with the running statistics:
+    (y, coef), coef = the (4, Cp) rows (scale, shift, invstd, running mean) ``bn_cl_bwd_eval`` takes.  Nothing is written to the
+    module's buffers."""
+    if bn.running_mean is None or bn.running_var is None:
+        raise RuntimeError("amp: an eval-mode BatchNorm3d needs running statistics")
+    lib = _lib.load()
+    y = torch.empty_like(z)
+    coef = torch.empty((4, z.shape[-1]), dtype=torch.float32, device=z.device)
+    _lib.check(lib.zsv_bn_cl_fwd_eval(z.data_ptr(), ops._ptr(residual), _rows(z), bn.num_features, ops._ptr(bn.weight),
+                                      ops._ptr(bn.bias), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps),
+                                      1 if relu else 0, y.data_ptr(), coef.data_ptr(), ops._stream()), "zsv_bn_cl_fwd_eval")
+    return y, coef
+
+
+def bn_cl_bwd_eval(dy: torch.Tensor, y: Optional[torch.Tensor], z: torch.Tensor, bn: nn.BatchNorm3d, coef: torch.Tensor, relu: bool,
+                   want_g: bool, want_dgamma: bool = True, want_dbeta: bool = True):
+    """Backward of ``bn_cl_fwd_eval`` in one pass: (dz, g or None, dgamma or None, dbeta or None).  ``y`` None with ``relu``: the
+    mask is recomputed from z with the forward's coefficients."""
+    lib = _lib.load()
+    c = bn.num_features
+    r = _rows(z)
+    dgamma = torch.empty(c, dtype=torch.float32, device=z.device) if want_dgamma else None
+    dbeta = torch.empty(c, dtype=torch.float32, device=z.device) if want_dbeta else None
+    nbytes = lib.zsv_bn_cl_workspace_bytes(r, c) if (want_dgamma or want_dbeta) else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device) if nbytes else None
+    dz = torch.empty_like(z)
+    g = torch.empty_like(z) if want_g else None
+    _lib.check(lib.zsv_bn_cl_bwd_eval(dy.data_ptr(), ops._ptr(y) if relu else None, z.data_ptr(), r, c, coef.data_ptr(),
+                                      1 if relu else 0, dz.data_ptr(), ops._ptr(g), ops._ptr(dgamma), ops._ptr(dbeta), ops._ptr(ws),
+                                      nbytes, ops._stream()), "zsv_bn_cl_bwd_eval")
+    return dz, g, dgamma, dbeta
+
+
 def cl_to_ncdhw_f32(x: torch.Tensor, channels: int) -> torch.Tensor:
     """[N][T][H][W][Cp] bf16 -> (N, channels, T, H, W) fp32."""
     n, t, h, w, _ = x.shape
@@ -251,7 +285,7 @@ class _Unit:
 
 
 class _Record:
-    __slots__ = ("unit", "x", "z", "y", "mean", "invstd", "desc", "has_res", "clips", "coef")
+    __slots__ = ("unit", "x", "z", "y", "mean", "invstd", "desc", "has_res", "clips", "coef", "frozen")
 
 
 def _units(mods) -> List[_Unit]:
@@ -299,9 +333,11 @@ class Bf16TrainPath:
         blob = pack_conv(d, u.conv.weight.detach(), None, None)
         timer = None if torch.cuda.is_current_stream_capturing() else ops.KERNEL_TIMER      # (timing events cannot be captured)
         mark = timer.start() if timer is not None and timer.wants("conv_bf16_fwd", d) else None
-        # the BatchNorm's batch statistics come out of the convolution's epilogue (ZSV_AMP_NO_CONV_STATS=1: a pass over z instead)
+        # the BatchNorm's batch statistics come out of the convolution's epilogue (ZSV_AMP_NO_CONV_STATS=1: a pass over z instead);
+        # a frozen (eval-mode) BatchNorm normalises with its running statistics and needs none
+        frozen = not u.bn.training
         stats = None
-        if os.environ.get("ZSV_AMP_NO_CONV_STATS"):
+        if frozen or os.environ.get("ZSV_AMP_NO_CONV_STATS"):
             z = conv_bf16(d, x, blob, None, False)
         else:
             z, partials, rows = conv_bf16_stats(d, x, blob)
@@ -310,12 +346,17 @@ class Bf16TrainPath:
             timer.stop(mark)
         # (a unit with ReLU and no residual keeps its scale / shift rows: the backward recomputes the mask from z, y is not read there)
         keep_coef = tape is not None and u.relu and residual is None
-        out = bn_cl_fwd_train(z, u.bn, residual, u.relu, want_coef=keep_coef, conv_stats=stats)
-        y, mean, invstd = out[0], out[1], out[2]
+        if frozen:
+            y, coef = bn_cl_fwd_eval(z, u.bn, residual, u.relu)
+            mean = invstd = None
+        else:
+            out = bn_cl_fwd_train(z, u.bn, residual, u.relu, want_coef=keep_coef, conv_stats=stats)
+            y, mean, invstd = out[0], out[1], out[2]
+            coef = out[3] if keep_coef else None
         if tape is not None:
             r = _Record()
             r.unit, r.x, r.z, r.y, r.mean, r.invstd, r.desc, r.has_res, r.clips = u, x, z, y, mean, invstd, d, residual is not None, clips
-            r.coef = out[3] if keep_coef else None
+            r.coef, r.frozen = coef, frozen
             tape.append(r)
         return y
 
@@ -455,10 +496,15 @@ class Bf16TrainPath:
             r = tape[idx]
             idx -= 1
             u = r.unit
-            dz, g, dgamma, dbeta = bn_cl_bwd(dy, r.y, r.z, u.bn, r.mean, r.invstd, u.relu, want_g, fwd_coef=r.coef)
-            if u.bn.weight is not None:
+            if r.frozen:          # running statistics: one pass; the mask from y only when the forward had a residual
+                dz, g, dgamma, dbeta = bn_cl_bwd_eval(dy, r.y if r.has_res else None, r.z, u.bn, r.coef, u.relu, want_g,
+                                                      u.bn.weight is not None and u.bn.weight.requires_grad,
+                                                      u.bn.bias is not None and u.bn.bias.requires_grad)
+            else:
+                dz, g, dgamma, dbeta = bn_cl_bwd(dy, r.y, r.z, u.bn, r.mean, r.invstd, u.relu, want_g, fwd_coef=r.coef)
+            if u.bn.weight is not None and dgamma is not None:
                 grads[id(u.bn.weight)] = dgamma
-            if u.bn.bias is not None:
+            if u.bn.bias is not None and dbeta is not None:
                 grads[id(u.bn.bias)] = dbeta
             if need_weight_grads and u.conv.weight.requires_grad:
                 grads[id(u.conv.weight)] = self._wgrad(r, dz)
@@ -706,7 +752,8 @@ class _TrunkBf16(Function):
         ctx.graphed = None
         if record and is_graph_enabled() and all(p.requires_grad for p in params):
             graphs = path.__dict__.setdefault("_graphs", {})
-            key = (tuple(clips.shape), clips.device.index)
+            # the BatchNorm modes are part of the key: a module switched to eval (or back) after capture re-captures
+            key = (tuple(clips.shape), clips.device.index, tuple(u.bn.training for u in path.units))
             with torch.cuda.device(clips.device):
                 g = graphs.get(key)
                 if g is None:
@@ -757,7 +804,8 @@ class _TrunkBf16(Function):
 
 
 def trunk_features(trunk: nn.Module, clips: torch.Tensor) -> torch.Tensor:
-    """``VideoResNet.forward``'s pooled output (resnet.py:251-254) for (N, 3, T, H, W) fp32 clips, trunk in bf16, train mode."""
+    """``VideoResNet.forward``'s pooled output (resnet.py:251-254) for (N, 3, T, H, W) fp32 clips, trunk in bf16, train mode.
+    Each BatchNorm keeps its own mode: eval-mode (frozen) ones normalise with their running statistics and leave them alone."""
     if not clips.is_cuda:
         raise RuntimeError("amp: MI355X HIP tensors only (there is no CPU fallback)")
     path = train_path_for(trunk)

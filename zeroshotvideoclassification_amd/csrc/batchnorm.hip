@@ -10,6 +10,7 @@
 //   finalize: C threads                -> mean, invstd, scale/shift, running stats
 //   apply   : read x (+res), write y   -> float4 along S when S % 4 == 0
 //   bwd     : reduce (read dy, x, y) + apply (read dy, x, y; write dx (+dres))
+//   bwd_eval: one pass (read dy, x or y; write dx (+dres)) + a C-wave finalize of dgamma / dbeta
 // Per-thread partial sums are fp32 over <= ~128 elements, combined in fp64 with
 // wave-level shuffles (64-wide) and a 4-entry LDS exchange; the slices of a channel are
 // summed in fixed order, so results are bitwise reproducible run to run.
@@ -206,16 +207,38 @@ __global__ __launch_bounds__(256) void bn_finalize_partials_kernel(const float* 
     shift[c] = __fmaf_rn(-(float)mean, sc, bt);
 }
 
+// Running-statistics affine of channel c: y = x * sc + sh, sc = gamma / sqrt(rv + eps), sh = beta - rm * sc (one fma).  Every
+// eval-mode pass (forward, folded-convolution coefficients, backward masks) takes its coefficients from here: the same bits.
+__device__ __forceinline__ void eval_coeff(int c, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                           const float* __restrict__ rm, const float* __restrict__ rv, float eps, float& invstd,
+                                           float& sc, float& sh) {
+    invstd = 1.f / sqrtf(rv[c] + eps);
+    const float g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+    sc = g * invstd;
+    sh = __fmaf_rn(-rm[c], sc, bt);
+}
+
 __global__ void bn_eval_coeff_kernel(int C, const float* __restrict__ gamma, const float* __restrict__ beta,
                                      const float* __restrict__ rm, const float* __restrict__ rv, float eps,
                                      float* __restrict__ scale, float* __restrict__ shift) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float invstd = 1.f / sqrtf(rv[c] + eps);
-    const float g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
-    const float sc = g * invstd;
+    float invstd, sc, sh;
+    eval_coeff(c, gamma, beta, rm, rv, eps, invstd, sc, sh);
     scale[c] = sc;
-    shift[c] = bt - rm[c] * sc;
+    shift[c] = sh;
+}
+
+// coef = [2][pitch] (scale row, shift row) of a frozen BatchNorm for zsv_conv3d_fwd_pre / zsv_conv3d_wgrad_pre; tail entries 0
+__global__ void bn_eval_coef_rows_kernel(int C, int pitch, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                         const float* __restrict__ rm, const float* __restrict__ rv, float eps,
+                                         float* __restrict__ coef) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= pitch) return;
+    float invstd = 0.f, sc = 0.f, sh = 0.f;
+    if (c < C) eval_coeff(c, gamma, beta, rm, rv, eps, invstd, sc, sh);
+    coef[c] = sc;
+    coef[pitch + c] = sh;
 }
 
 // ---- y = relu?(x*scale[c] + shift[c] + res?) ------------------------------------------
@@ -442,6 +465,92 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
 }
 
+// ---- eval-mode (frozen statistics) backward: ONE pass --------------------------------------------------------------------
+// g = dy * mask (RELU as bn_bwd_reduce_kernel, the mode-2 mask with eval_coeff's scale / shift), dx = scale * g, d_residual = g;
+// SUMS: the block's partial sum g and sum g * xhat (xhat = (x - running_mean) * invstd) to part[2][C][slices] -- no
+// mean-subtraction terms depend on them, so the input gradient needs no second pass.  Same (channel, slice) grid and fixed
+// summation order as bn_bwd_reduce_kernel: bitwise reproducible.
+template <int RELU, bool DRES, bool SUMS>
+__global__ __launch_bounds__(256) void bn_bwd_eval_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                          const float* __restrict__ y, float* __restrict__ dx,
+                                                          float* __restrict__ dres, int N, int C, int S, int slices,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          const float* __restrict__ rm, const float* __restrict__ rv, float eps,
+                                                          double* __restrict__ part, bool nt) {
+    __shared__ double red[4];
+    const int c = blockIdx.x, sl = blockIdx.y;
+    const bool vec = (S % 4) == 0;
+    int b, e;
+    slice_range(N * S, slices, sl, vec, b, e);
+    float is, sc, sh;
+    eval_coeff(c, gamma, beta, rm, rv, eps, is, sc, sh);
+    const float mu = rm[c];
+    float s1 = 0.f, s2 = 0.f;
+    if (vec) {
+        for (int i = b + 4 * (int)threadIdx.x; i < e; i += 4 * 256) {
+            const int n = i / S, s = i - n * S;
+            const size_t off = ((size_t)n * C + c) * S + s;
+            float4 g = ld4(dy + off, nt);
+            float4 xv;
+            if (SUMS || RELU == 2) xv = ld4(x + off, nt);
+            if (RELU == 1) {
+                const float4 yv = ld4(y + off, nt);
+                g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
+                g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
+            } else if (RELU == 2) {
+                g.x = __fmaf_rn(xv.x, sc, sh) > 0.f ? g.x : 0.f; g.y = __fmaf_rn(xv.y, sc, sh) > 0.f ? g.y : 0.f;
+                g.z = __fmaf_rn(xv.z, sc, sh) > 0.f ? g.z : 0.f; g.w = __fmaf_rn(xv.w, sc, sh) > 0.f ? g.w : 0.f;
+            }
+            if (DRES) st4(dres + off, g, nt);
+            st4(dx + off, make_float4(sc * g.x, sc * g.y, sc * g.z, sc * g.w), nt);
+            if (SUMS) {
+                s1 += (g.x + g.y) + (g.z + g.w);
+                s2 += (g.x * ((xv.x - mu) * is) + g.y * ((xv.y - mu) * is)) +
+                      (g.z * ((xv.z - mu) * is) + g.w * ((xv.w - mu) * is));
+            }
+        }
+    } else {
+        for (int i = b + (int)threadIdx.x; i < e; i += 256) {
+            const int n = i / S, s = i - n * S;
+            const size_t off = ((size_t)n * C + c) * S + s;
+            float g = dy[off];
+            const float xs = (SUMS || RELU == 2) ? x[off] : 0.f;
+            if (RELU == 1) g = y[off] > 0.f ? g : 0.f;
+            else if (RELU == 2) g = __fmaf_rn(xs, sc, sh) > 0.f ? g : 0.f;
+            if (DRES) dres[off] = g;
+            dx[off] = sc * g;
+            if (SUMS) {
+                s1 += g;
+                s2 += g * ((xs - mu) * is);
+            }
+        }
+    }
+    if (SUMS) {
+        const double t1 = block_sum_256<double>((double)s1, red);
+        const double t2 = block_sum_256<double>((double)s2, red);
+        if (threadIdx.x == 0) {
+            part[(size_t)c * slices + sl] = t1;
+            part[(size_t)(C + c) * slices + sl] = t2;
+        }
+    }
+}
+
+// dgamma = sum g*xhat, dbeta = sum g from the partials (one 64-lane wave per channel, fixed order as bn_bwd_finalize_kernel)
+__global__ void bn_bwd_eval_finalize_kernel(const double* __restrict__ part, int C, int slices, float* __restrict__ dgamma,
+                                            float* __restrict__ dbeta) {
+    const int c = blockIdx.x;
+    double sg = 0.0, sgx = 0.0;
+    for (int k = threadIdx.x; k < slices; k += 64) {
+        sg += part[(size_t)c * slices + k];
+        sgx += part[(size_t)(C + c) * slices + k];
+    }
+    sg = wave_sum(sg);
+    sgx = wave_sum(sgx);
+    if (threadIdx.x != 0) return;
+    if (dgamma) dgamma[c] = (float)sgx;
+    if (dbeta) dbeta[c] = (float)sg;
+}
+
 static int check_ncs(int N, int C, int S) {
     if (N <= 0 || C <= 0 || S <= 0) return ZSV_E_BAD_SHAPE;
     if ((double)N * C * S >= 2147483647.0) return ZSV_E_TOO_LARGE;
@@ -593,5 +702,46 @@ extern "C" int zsv_bn_bwd(const float* dy, const float* x, const float* y, int32
     else if (fuse_relu == 1) { if (d_residual) ZSV_BWD_APPLY(1, true); else ZSV_BWD_APPLY(1, false); }
     else { if (d_residual) ZSV_BWD_APPLY(0, true); else ZSV_BWD_APPLY(0, false); }
 #undef ZSV_BWD_APPLY
+    return launch_status();
+}
+
+extern "C" int zsv_bn_eval_coeffs(int32_t C, const float* gamma, const float* beta, const float* running_mean,
+                                  const float* running_var, float eps, float* coef, int32_t coef_pitch, void* stream_) {
+    if (C <= 0 || coef_pitch < C) return ZSV_E_BAD_SHAPE;
+    if (!running_mean || !running_var || !coef) return ZSV_E_NULL;
+    hipLaunchKernelGGL(bn_eval_coef_rows_kernel, dim3((coef_pitch + 127) / 128), dim3(128), 0, (hipStream_t)stream_, C, coef_pitch,
+                       gamma, beta, running_mean, running_var, eps, coef);
+    return launch_status();
+}
+
+extern "C" int zsv_bn_bwd_eval(const float* dy, const float* x, const float* y, int32_t N, int32_t C, int32_t S,
+                               const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                               float eps, int fuse_relu, float* dx, float* d_residual, float* dgamma, float* dbeta,
+                               void* workspace, size_t workspace_bytes, void* stream_) {
+    int st = check_ncs(N, C, S);
+    if (st) return st;
+    if (fuse_relu < 0 || fuse_relu > 2) return ZSV_E_BAD_SHAPE;
+    const bool sums = dgamma != nullptr || dbeta != nullptr;
+    if (!dy || !dx || !running_mean || !running_var) return ZSV_E_NULL;
+    if ((sums || fuse_relu == 2) && !x) return ZSV_E_NULL;
+    if (fuse_relu == 1 && !y) return ZSV_E_NULL;
+    if (sums && (!workspace || workspace_bytes < bn_ws_bytes(N, C, S))) return ZSV_E_WORKSPACE;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int slices = bn_slices(N, C, S);
+    double* part = sums ? (double*)workspace : nullptr;
+    const dim3 grid(C, slices);
+    const bool nt = bn_stream(N, C, S);
+#define ZSV_BWD_EVAL(R, D, SU) hipLaunchKernelGGL((bn_bwd_eval_kernel<R, D, SU>), grid, dim3(256), 0, stream, dy, x, y, dx, d_residual, \
+                                                  N, C, S, slices, gamma, beta, running_mean, running_var, eps, part, nt)
+#define ZSV_BWD_EVAL_R(R) do { \
+        if (d_residual) { if (sums) ZSV_BWD_EVAL(R, true, true); else ZSV_BWD_EVAL(R, true, false); } \
+        else { if (sums) ZSV_BWD_EVAL(R, false, true); else ZSV_BWD_EVAL(R, false, false); } } while (0)
+    if (fuse_relu == 2) ZSV_BWD_EVAL_R(2);
+    else if (fuse_relu == 1) ZSV_BWD_EVAL_R(1);
+    else ZSV_BWD_EVAL_R(0);
+#undef ZSV_BWD_EVAL_R
+#undef ZSV_BWD_EVAL
+    if ((st = launch_status()) || !sums) return st;
+    hipLaunchKernelGGL(bn_bwd_eval_finalize_kernel, dim3(C), dim3(64), 0, stream, (const double*)part, C, slices, dgamma, dbeta);
     return launch_status();
 }

@@ -4,7 +4,8 @@
 // Host C++ only (built with g++ against the torch headers; no device code, nothing generated): every operator builds the POD
 // descriptor from the tensor sizes, takes the stream torch is currently recording on, allocates the workspace from torch's caching
 // allocator and calls the same `zsv_*` entry point the ctypes glue (`_lib.py` / `ops.py`) calls.  The differentiable forms
-// (`zsv::conv3d`, `zsv::batch_norm_relu`, `zsv::relu`, `zsv::linear`) register an Autograd kernel, so C++ / TorchScript callers get the reference's
+// (`zsv::conv3d`, `zsv::batch_norm_relu`, `zsv::batch_norm_relu_eval`, `zsv::relu`, `zsv::linear`) register an Autograd kernel,
+// so C++ / TorchScript callers get the reference's
 // `nn.Conv3d` (resnet.py:23-30,40-52; network.py:102-117) and `nn.BatchNorm3d (+ ReLU)` (resnet.py:46-49,94-98) semantics
 // without Python.  The training harness of this repo keeps the ctypes path (panel cache, side-stream weight gradients, fused
 // block tails live in ops.py); tests/test_torch_binding_gpu.py checks both bindings against each other bit for bit.
@@ -143,6 +144,61 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_train_bwd(const at::Tensor& dy
     return {dx, dgamma, dbeta};
 }
 
+// eval-mode (frozen statistics) BatchNorm3d (+ ReLU): y = relu?(x * a + b) from the running statistics, which are only read
+at::Tensor bn_eval_fwd(const at::Tensor& x, const at::Tensor& gamma, const at::Tensor& beta, const at::Tensor& running_mean,
+                       const at::Tensor& running_var, double eps, bool relu) {
+    want(x, "x", 5);
+    want(gamma, "weight", 1);
+    want(beta, "bias", 1);
+    want(running_mean, "running_mean", 1);
+    want(running_var, "running_var", 1);
+    const int32_t N = (int32_t)x.size(0), C = (int32_t)x.size(1), S = (int32_t)(x.size(2) * x.size(3) * x.size(4));
+    TORCH_CHECK(gamma.numel() == C && beta.numel() == C && running_mean.numel() == C && running_var.numel() == C,
+                "batch_norm: per-channel tensors must have ", C, " entries");
+    at::Tensor y = at::empty_like(x);
+    const size_t bytes = zsv_bn_workspace_bytes(N, C, S);
+    at::Tensor ws = scratch(bytes, x);
+    ok(zsv_bn_fwd_eval(x.data_ptr<float>(), N, C, S, gamma.data_ptr<float>(), beta.data_ptr<float>(), running_mean.data_ptr<float>(),
+                       running_var.data_ptr<float>(), nullptr, relu ? 1 : 0, (float)eps, y.data_ptr<float>(), ws.data_ptr(), bytes,
+                       stream_of(x)),
+       "zsv_bn_fwd_eval");
+    return y;
+}
+
+// backward of the op above in one pass: dx, dgamma, dbeta (ReLU mask recomputed from x with the forward's exact fma)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_eval_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& gamma,
+                                                           const at::Tensor& beta, const at::Tensor& running_mean,
+                                                           const at::Tensor& running_var, double eps, bool relu,
+                                                           bool want_dgamma = true, bool want_dbeta = true) {
+    want(dy, "dy", 5);
+    want(x, "x", 5);
+    want(gamma, "weight", 1);
+    want(beta, "bias", 1);
+    want(running_mean, "running_mean", 1);
+    want(running_var, "running_var", 1);
+    TORCH_CHECK(dy.sizes() == x.sizes(), "bn_eval_bwd: dy does not have x's shape");
+    const int32_t N = (int32_t)x.size(0), C = (int32_t)x.size(1), S = (int32_t)(x.size(2) * x.size(3) * x.size(4));
+    TORCH_CHECK(gamma.numel() == C && beta.numel() == C && running_mean.numel() == C && running_var.numel() == C,
+                "batch_norm: per-channel tensors must have ", C, " entries");
+    at::Tensor dx = at::empty_like(x);
+    at::Tensor dgamma = want_dgamma ? at::empty({C}, x.options()) : at::Tensor();
+    at::Tensor dbeta = want_dbeta ? at::empty({C}, x.options()) : at::Tensor();
+    const size_t bytes = zsv_bn_workspace_bytes(N, C, S);
+    at::Tensor ws = scratch(bytes, x);
+    ok(zsv_bn_bwd_eval(dy.data_ptr<float>(), x.data_ptr<float>(), nullptr, N, C, S, gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                       running_mean.data_ptr<float>(), running_var.data_ptr<float>(), (float)eps, relu ? 2 : 0, dx.data_ptr<float>(),
+                       nullptr, want_dgamma ? dgamma.data_ptr<float>() : nullptr, want_dbeta ? dbeta.data_ptr<float>() : nullptr,
+                       ws.data_ptr(), bytes, stream_of(x)),
+       "zsv_bn_bwd_eval");
+    return {dx, dgamma, dbeta};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_eval_bwd_op(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& gamma,
+                                                              const at::Tensor& beta, const at::Tensor& running_mean,
+                                                              const at::Tensor& running_var, double eps, bool relu) {
+    return bn_eval_bwd(dy, x, gamma, beta, running_mean, running_var, eps, relu);
+}
+
 // nn.ReLU (resnet.py:49; network.py:147-166,614) and its backward (mask from the saved output, like ReLU(inplace=True))
 at::Tensor relu_fwd(const at::Tensor& x) {
     TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), "relu: contiguous float32 GPU tensor expected");
@@ -258,6 +314,30 @@ at::Tensor batch_norm_relu_autograd(const at::Tensor& x, const at::Tensor& gamma
     return BatchNormReluFn::apply(x, gamma, beta, running_mean, running_var, momentum, eps, relu);
 }
 
+struct BatchNormReluEvalFn : public torch::autograd::Function<BatchNormReluEvalFn> {
+    static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& x, const at::Tensor& gamma, const at::Tensor& beta,
+                              const at::Tensor& running_mean, const at::Tensor& running_var, double eps, bool relu) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        at::Tensor y = bn_eval_fwd(x, gamma, beta, running_mean, running_var, eps, relu);
+        ctx->save_for_backward({x, gamma, beta, running_mean.clone(), running_var.clone()});       // (statistics as the forward saw them)
+        ctx->saved_data["eps"] = eps;
+        ctx->saved_data["relu"] = relu;
+        return y;
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
+        const auto s = ctx->get_saved_variables();
+        // (a frozen affine -- gamma / beta without gradients -- skips the reduction)
+        auto [dx, dgamma, dbeta] = bn_eval_bwd(grads[0].contiguous(), s[0], s[1], s[2], s[3], s[4], ctx->saved_data["eps"].toDouble(),
+                                               ctx->saved_data["relu"].toBool(), ctx->needs_input_grad(1), ctx->needs_input_grad(2));
+        return {dx, dgamma, dbeta, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+    }
+};
+
+at::Tensor batch_norm_relu_eval_autograd(const at::Tensor& x, const at::Tensor& gamma, const at::Tensor& beta,
+                                         const at::Tensor& running_mean, const at::Tensor& running_var, double eps, bool relu) {
+    return BatchNormReluEvalFn::apply(x, gamma, beta, running_mean, running_var, eps, relu);
+}
+
 struct ReluFn : public torch::autograd::Function<ReluFn> {
     static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& x) {
         at::AutoDispatchBelowADInplaceOrView guard;
@@ -318,6 +398,10 @@ TORCH_LIBRARY(zsv, m) {
           "float eps, bool relu=False) -> (Tensor, Tensor, Tensor)");
     m.def("bn_train_bwd(Tensor dy, Tensor x, Tensor y, Tensor weight, Tensor bias, Tensor save_mean, Tensor save_invstd, "
           "bool relu=False) -> (Tensor, Tensor, Tensor)");
+    m.def("bn_eval_fwd(Tensor x, Tensor weight, Tensor bias, Tensor running_mean, Tensor running_var, float eps, bool relu=False) "
+          "-> Tensor");
+    m.def("bn_eval_bwd(Tensor dy, Tensor x, Tensor weight, Tensor bias, Tensor running_mean, Tensor running_var, float eps, "
+          "bool relu=False) -> (Tensor, Tensor, Tensor)");
     m.def("relu_fwd(Tensor x) -> Tensor");
     m.def("relu_bwd(Tensor dy, Tensor y) -> Tensor");
     m.def("linear_fwd(Tensor x, Tensor w, Tensor? bias, bool relu=False) -> Tensor");
@@ -328,6 +412,8 @@ TORCH_LIBRARY(zsv, m) {
     m.def("conv3d(Tensor x, Tensor w, Tensor? bias, int[3] stride, int[3] padding) -> Tensor");
     m.def("batch_norm_relu(Tensor x, Tensor weight, Tensor bias, Tensor(a!) running_mean, Tensor(b!) running_var, float momentum, "
           "float eps, bool relu=False) -> Tensor");
+    m.def("batch_norm_relu_eval(Tensor x, Tensor weight, Tensor bias, Tensor running_mean, Tensor running_var, float eps, "
+          "bool relu=False) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(zsv, CUDA, m) {      // torch's name of the HIP backend on ROCm builds
@@ -338,6 +424,9 @@ TORCH_LIBRARY_IMPL(zsv, CUDA, m) {      // torch's name of the HIP backend on RO
     m.impl("bn_train_bwd", bn_train_bwd);
     m.impl("conv3d", conv3d_plain);
     m.impl("batch_norm_relu", batch_norm_relu_plain);
+    m.impl("bn_eval_fwd", bn_eval_fwd);
+    m.impl("bn_eval_bwd", bn_eval_bwd_op);
+    m.impl("batch_norm_relu_eval", bn_eval_fwd);
     m.impl("relu_fwd", relu_fwd);
     m.impl("relu_bwd", relu_bwd);
     m.impl("linear_fwd", linear_fwd);
@@ -350,6 +439,7 @@ TORCH_LIBRARY_IMPL(zsv, CUDA, m) {      // torch's name of the HIP backend on RO
 TORCH_LIBRARY_IMPL(zsv, Autograd, m) {
     m.impl("conv3d", conv3d_autograd);
     m.impl("batch_norm_relu", batch_norm_relu_autograd);
+    m.impl("batch_norm_relu_eval", batch_norm_relu_eval_autograd);
     m.impl("relu", relu_autograd);
     m.impl("linear", linear_autograd);
 }

@@ -256,6 +256,98 @@ __global__ __launch_bounds__(256) void bn_cl_bwd_apply_kernel(ClShape sh, const 
     }
 }
 
+// ---- eval-mode (frozen statistics) BatchNorm ----------------------------------------------------------------------------
+// coef [4][Cp] from the running statistics: a = gamma*invstd, b = beta - mean*a (as bn_cl_fwd_finalize_kernel: fp64, rounded once),
+// invstd, mean; pad channels 0.  The forward applies (a, b) with bn_cl_apply_kernel; the backward takes the same rows back, so its
+// recomputed ReLU mask is the forward's and the running statistics are read once, at the forward.
+__global__ void bn_cl_eval_coef_kernel(int C, int Cp, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                       const float* __restrict__ rm, const float* __restrict__ rv, float eps, float* __restrict__ coef) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= Cp) return;
+    float a = 0.f, b = 0.f, is = 0.f, mu = 0.f;
+    if (c < C) {
+        const double invstd = 1.0 / sqrt((double)rv[c] + (double)eps);
+        const double g = gamma ? (double)gamma[c] : 1.0, bt = beta ? (double)beta[c] : 0.0;
+        const double ad = g * invstd;
+        a = (float)ad;
+        b = (float)(bt - (double)rm[c] * ad);
+        is = (float)invstd;
+        mu = rm[c];
+    }
+    coef[c] = a;
+    coef[Cp + c] = b;
+    coef[2 * Cp + c] = is;
+    coef[3 * Cp + c] = mu;
+}
+
+// ONE pass: g = dy (* mask), dz = a*g (bf16), g_out = g; SUMS: the block's (sum g, sum g*z) partials in bn_cl_reduce_kernel's
+// layout and fixed order.  MASK 0: none, 1: y > 0 (saved output), 2: fma(z, a, b) > 0 (the forward's coefficients).
+template <int MASK, bool GOUT, bool SUMS>
+__global__ __launch_bounds__(256) void bn_cl_bwd_eval_kernel(ClShape sh, const u32x4v* __restrict__ dy, const u32x4v* __restrict__ y,
+                                                             const u32x4v* __restrict__ z, const float* __restrict__ coef,
+                                                             u32x4v* __restrict__ dz, u32x4v* __restrict__ gout, float* __restrict__ partial) {
+    extern __shared__ float red[];                 // [RL][2][Cp] (SUMS)
+    const int o = threadIdx.x % sh.G, rl = threadIdx.x / sh.G;
+    float s0[8], s1[8], a[8], b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { s0[j] = s1[j] = 0.f; a[j] = coef[o * 8 + j]; b[j] = coef[sh.Cp + o * 8 + j]; }
+    const long row0 = (long)blockIdx.x * sh.rows_per_block;
+    long row_end = row0 + sh.rows_per_block;
+    if (row_end > sh.R) row_end = sh.R;
+    if (rl < sh.RL) {
+        for (long r = row0 + rl; r < row_end; r += sh.RL) {
+            const long idx = r * sh.G + o;
+            float gv[8], zv[8];
+            unpack8(__builtin_nontemporal_load(dy + idx), gv);
+            if (SUMS || MASK == 2) unpack8(__builtin_nontemporal_load(z + idx), zv);
+            if (MASK == 1) {
+                float yv[8];
+                unpack8(__builtin_nontemporal_load(y + idx), yv);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) gv[j] = yv[j] > 0.f ? gv[j] : 0.f;
+            }
+            if (MASK == 2) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) gv[j] = fmaf(zv[j], a[j], b[j]) > 0.f ? gv[j] : 0.f;
+            }
+            if (GOUT) gout[idx] = pack8(gv);
+            float dv[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) dv[j] = a[j] * gv[j];
+            dz[idx] = pack8(dv);
+            if (SUMS) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { s0[j] += gv[j]; s1[j] = fmaf(gv[j], zv[j], s1[j]); }
+            }
+        }
+        if (SUMS) {
+            float* mine = red + (size_t)rl * 2 * sh.Cp + o * 8;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { mine[j] = s0[j]; mine[sh.Cp + j] = s1[j]; }
+        }
+    }
+    if (!SUMS) return;
+    __syncthreads();
+    float* out = partial + (size_t)blockIdx.x * 2 * sh.Cp;
+    for (int c = threadIdx.x; c < 2 * sh.Cp; c += 256) {
+        float acc = 0.f;
+        for (int l = 0; l < sh.RL; ++l) acc += red[(size_t)l * 2 * sh.Cp + c];
+        out[c] = acc;
+    }
+}
+
+// dbeta = sum g, dgamma = invstd * (sum g*z - mean * sum g) (x_hat with the running statistics); either may be NULL
+__global__ __launch_bounds__(256) void bn_cl_bwd_eval_finalize_kernel(const float* __restrict__ partial, int nb, int C, int Cp,
+                                                                      const float* __restrict__ coef, float* __restrict__ dgamma,
+                                                                      float* __restrict__ dbeta) {
+    const int c = blockIdx.x * 16 + (threadIdx.x & 15);
+    double sg, sgz;
+    partial_sums_16(partial, nb, Cp, c, sg, sgz);
+    if ((threadIdx.x >> 4) != 0 || c >= C) return;
+    if (dgamma) dgamma[c] = (float)((sgz - (double)coef[3 * Cp + c] * sg) * (double)coef[2 * Cp + c]);
+    if (dbeta) dbeta[c] = (float)sg;
+}
+
 // [N][S][Cp] bf16 -> (N, C, S) fp32: 64 voxels x 32 channels per block through LDS
 __global__ __launch_bounds__(256) void cl_bf16_to_ncs_f32_kernel(const unsigned short* __restrict__ x, int S, int C, int Cp,
                                                                  float* __restrict__ out) {
@@ -519,6 +611,62 @@ int zsv_bn_cl_bwd(const void* dy, const void* y, const void* z, int64_t R, int32
     else if (mask == 2) { if (g_out) ZSV_BWD_APPLY(2, true); else ZSV_BWD_APPLY(2, false); }
     else { if (g_out) ZSV_BWD_APPLY(0, true); else ZSV_BWD_APPLY(0, false); }
 #undef ZSV_BWD_APPLY
+    return launch_status();
+}
+
+int zsv_bn_cl_fwd_eval(const void* z, const void* residual, int64_t R, int32_t C, const float* gamma, const float* beta,
+                       const float* running_mean, const float* running_var, float eps, int fuse_relu, void* y, float* coef,
+                       void* stream) {
+    ClShape sh;
+    int nb = 0;
+    const int st = cl_shape(R, C, &sh, &nb);
+    if (st != ZSV_OK) return st;
+    if (!z || !y || !running_mean || !running_var || !coef) return ZSV_E_NULL;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_cl_eval_coef_kernel, dim3((sh.Cp + 127) / 128), dim3(128), 0, s, C, sh.Cp, gamma, beta, running_mean,
+                       running_var, eps, coef);
+    const u32x4v* zz = (const u32x4v*)z;
+    const u32x4v* rr = (const u32x4v*)residual;
+    u32x4v* yy = (u32x4v*)y;
+    if (residual) {
+        if (fuse_relu) hipLaunchKernelGGL((bn_cl_apply_kernel<true, true>), dim3(nb), dim3(256), 0, s, sh, zz, rr, coef, yy);
+        else hipLaunchKernelGGL((bn_cl_apply_kernel<true, false>), dim3(nb), dim3(256), 0, s, sh, zz, rr, coef, yy);
+    } else {
+        if (fuse_relu) hipLaunchKernelGGL((bn_cl_apply_kernel<false, true>), dim3(nb), dim3(256), 0, s, sh, zz, rr, coef, yy);
+        else hipLaunchKernelGGL((bn_cl_apply_kernel<false, false>), dim3(nb), dim3(256), 0, s, sh, zz, rr, coef, yy);
+    }
+    return launch_status();
+}
+
+int zsv_bn_cl_bwd_eval(const void* dy, const void* y, const void* z, int64_t R, int32_t C, const float* coef, int relu_mask, void* dz,
+                       void* g_out, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
+    ClShape sh;
+    int nb = 0;
+    const int st = cl_shape(R, C, &sh, &nb);
+    if (st != ZSV_OK) return st;
+    const bool sums = dgamma != nullptr || dbeta != nullptr;
+    if (!dy || !dz || !coef) return ZSV_E_NULL;
+    const int mask = !relu_mask ? 0 : (y ? 1 : 2);          // 1: the saved output, 2: recomputed from z and the forward's coefficients
+    if ((sums || mask == 2) && !z) return ZSV_E_NULL;
+    if (sums && (!workspace || workspace_bytes < cl_workspace_bytes(sh, nb))) return ZSV_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    float* partial = (float*)workspace;
+    const size_t lds = sums ? (size_t)sh.RL * 2 * sh.Cp * sizeof(float) : 0;
+    const u32x4v *gg = (const u32x4v*)dy, *yy = (const u32x4v*)y, *zz = (const u32x4v*)z;
+    u32x4v *dd = (u32x4v*)dz, *go = (u32x4v*)g_out;
+#define ZSV_BWD_EVAL(M, G, SU) hipLaunchKernelGGL((bn_cl_bwd_eval_kernel<M, G, SU>), dim3(nb), dim3(256), lds, s, sh, gg, yy, zz, coef, dd, go, \
+                                                  partial)
+#define ZSV_BWD_EVAL_M(M) do { \
+        if (g_out) { if (sums) ZSV_BWD_EVAL(M, true, true); else ZSV_BWD_EVAL(M, true, false); } \
+        else { if (sums) ZSV_BWD_EVAL(M, false, true); else ZSV_BWD_EVAL(M, false, false); } } while (0)
+    if (mask == 1) ZSV_BWD_EVAL_M(1);
+    else if (mask == 2) ZSV_BWD_EVAL_M(2);
+    else ZSV_BWD_EVAL_M(0);
+#undef ZSV_BWD_EVAL_M
+#undef ZSV_BWD_EVAL
+    if (sums)
+        hipLaunchKernelGGL(bn_cl_bwd_eval_finalize_kernel, dim3((sh.Cp + 15) / 16), dim3(256), 0, s, partial, nb, C, sh.Cp, coef, dgamma,
+                           dbeta);
     return launch_status();
 }
 

@@ -713,13 +713,17 @@ class _BatchNormAct(Function):
             else:
                 if running_mean is None or running_var is None:
                     raise RuntimeError("eval-mode BatchNorm needs running statistics")
-                save_mean = save_invstd = None
+                # the eval-mode backward's statistics ride in the save_mean / save_invstd slots: a SNAPSHOT of the running
+                # statistics (C floats), since a training-mode forward of the module before this backward would rewrite the
+                # buffers through raw pointers, behind autograd's version counters
+                save_mean, save_invstd = (running_mean.clone(), running_var.clone()) if any(ctx.needs_input_grad) else (None, None)
                 _lib.check(lib.zsv_bn_fwd_eval(x.data_ptr(), n, c, s, _ptr(gamma), _ptr(beta), running_mean.data_ptr(),
                                                running_var.data_ptr(), _ptr(residual), 1 if relu else 0, float(eps),
                                                y.data_ptr(), _ptr(ws), nbytes, _stream()), "zsv_bn_fwd_eval")
         ctx.relu = bool(relu)
         ctx.has_res = residual is not None
         ctx.dims = (n, c, s)
+        ctx.eps = float(eps)
         ctx.skip_link = skip_link if (skip_link is not None and skip_link.armed and residual is not None) else None
         # with a ReLU but no residual the backward recomputes the mask from x: y need not be kept
         ctx.save_for_backward(x, gamma, beta, save_mean, save_invstd, y if (relu and residual is not None) else None)
@@ -728,26 +732,34 @@ class _BatchNormAct(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        if not ctx.training:
-            raise RuntimeError("backward through eval-mode BatchNorm is not part of the hot path "
-                               "(the reference evaluates under torch.no_grad(), main.py:230)")
         x, gamma, beta, save_mean, save_invstd, y = ctx.saved_tensors
         n, c, s = ctx.dims
         lib = _lib.load()
         dy = dy.contiguous()
         dx = torch.empty_like(x)
-        dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
         want_res = ctx.has_res and ctx.needs_input_grad[5]
         # without a fused ReLU the residual gradient is dy itself
         dres = torch.empty_like(x) if (want_res and ctx.relu) else None
         nbytes = lib.zsv_bn_workspace_bytes(n, c, s)
         ws = _workspace(nbytes, x.device)
-        with torch.cuda.device(x.device):
-            mode = 0 if not ctx.relu else (1 if ctx.has_res else 2)
-            _lib.check(lib.zsv_bn_bwd(dy.data_ptr(), x.data_ptr(), _ptr(y), n, c, s, _ptr(gamma), _ptr(beta),
-                                      save_mean.data_ptr(), save_invstd.data_ptr(), mode, dx.data_ptr(), _ptr(dres),
-                                      dgamma.data_ptr(), dbeta.data_ptr(), _ptr(ws), nbytes, _stream()), "zsv_bn_bwd")
+        mode = 0 if not ctx.relu else (1 if ctx.has_res else 2)
+        if ctx.training:
+            dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
+            dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device):
+                _lib.check(lib.zsv_bn_bwd(dy.data_ptr(), x.data_ptr(), _ptr(y), n, c, s, _ptr(gamma), _ptr(beta),
+                                          save_mean.data_ptr(), save_invstd.data_ptr(), mode, dx.data_ptr(), _ptr(dres),
+                                          dgamma.data_ptr(), dbeta.data_ptr(), _ptr(ws), nbytes, _stream()), "zsv_bn_bwd")
+        else:
+            # running statistics (frozen BatchNorm; save_mean / save_invstd hold the forward's snapshot of running_mean /
+            # running_var): one pass, no mean-subtraction terms; a frozen affine skips the sums
+            dgamma = torch.empty(c, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[1] else None
+            dbeta = torch.empty(c, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[2] else None
+            with torch.cuda.device(x.device):
+                _lib.check(lib.zsv_bn_bwd_eval(dy.data_ptr(), x.data_ptr(), _ptr(y), n, c, s, _ptr(gamma), _ptr(beta),
+                                               save_mean.data_ptr(), save_invstd.data_ptr(), ctx.eps, mode, dx.data_ptr(),
+                                               _ptr(dres), _ptr(dgamma), _ptr(dbeta), _ptr(ws), nbytes, _stream()),
+                           "zsv_bn_bwd_eval")
         if want_res and not ctx.relu:
             dres = dy
         if want_res and ctx.skip_link is not None:
@@ -907,11 +919,63 @@ def conv_pre_supported(x_shape, weight_shape, stride, padding) -> bool:
     return bool(_lib.load().zsv_conv3d_pre_supported(byref(d)))
 
 
+class _BatchNormFrozenDeferred(Function):
+    """Eval-mode (frozen statistics) ``BatchNorm3d`` folded into the consuming convolution: returns its input (the handle the
+    consumer differentiates against) and ``coef`` = per-channel (scale, shift) from the running statistics.  Nothing is
+    written but ``coef``; the backward is ``zsv_bn_bwd_eval`` with the ReLU mask recomputed from x."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, eps):
+        ctx.set_materialize_grads(False)
+        _require(x, gamma, beta, running_mean, running_var)
+        if not x.is_contiguous():
+            raise RuntimeError("deferred BatchNorm needs a contiguous input")
+        n, c = int(x.shape[0]), int(x.shape[1])
+        s = x.numel() // (n * c)
+        lib = _lib.load()
+        pitch = (c + 15) // 16 * 16
+        coef = torch.empty((2, pitch), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.zsv_bn_eval_coeffs(c, _ptr(gamma), _ptr(beta), running_mean.data_ptr(), running_var.data_ptr(),
+                                              float(eps), coef.data_ptr(), pitch, _stream()), "zsv_bn_eval_coeffs")
+        ctx.dims = (n, c, s)
+        ctx.eps = float(eps)
+        # a snapshot of the running statistics (see _BatchNormAct.forward): the backward's mask must be the forward's
+        ctx.save_for_backward(x, gamma, beta, running_mean.clone(), running_var.clone())
+        ctx.mark_non_differentiable(coef)
+        return x.view_as(x), coef
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _dcoef=None):
+        x, gamma, beta, running_mean, running_var = ctx.saved_tensors
+        n, c, s = ctx.dims
+        lib = _lib.load()
+        if g is None:                           # output unused downstream
+            return (None,) * 6
+        g = g.contiguous()
+        dx = torch.empty_like(x)
+        dgamma = torch.empty(c, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[1] else None
+        dbeta = torch.empty(c, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[2] else None
+        nbytes = lib.zsv_bn_workspace_bytes(n, c, s)
+        ws = _workspace(nbytes, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.zsv_bn_bwd_eval(g.data_ptr(), x.data_ptr(), None, n, c, s, _ptr(gamma), _ptr(beta),
+                                           running_mean.data_ptr(), running_var.data_ptr(), ctx.eps, 2, dx.data_ptr(), None,
+                                           _ptr(dgamma), _ptr(dbeta), _ptr(ws), nbytes, _stream()), "zsv_bn_bwd_eval")
+        return (dx if ctx.needs_input_grad[0] else None, dgamma, dbeta, None, None, None)
+
+
 def bn_module_deferred(x, bn: torch.nn.Module, stats=None):
-    """``bn`` in training mode without its normalise pass: ``(x_handle, coef)`` for ``conv3d_pre`` (running statistics
-    and ``num_batches_tracked`` are updated exactly as ``bn_module_act`` does)."""
-    if bn.momentum is None or not bn.training:
-        raise RuntimeError("deferred BatchNorm: training mode with a momentum only")
+    """``bn`` without its normalise pass: ``(x_handle, coef)`` for ``conv3d_pre``.  Training mode: running statistics and
+    ``num_batches_tracked`` are updated exactly as ``bn_module_act`` does.  Eval mode (a frozen BatchNorm, running statistics
+    required): ``coef`` comes from the running statistics and no buffer is touched."""
+    if not bn.training:
+        if bn.running_mean is None or bn.running_var is None:
+            raise RuntimeError("deferred BatchNorm: eval mode needs running statistics")
+        return _BatchNormFrozenDeferred.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps))
+    if bn.momentum is None:
+        raise RuntimeError("deferred BatchNorm: training mode needs a momentum (momentum=None is not supported)")
     if bn.track_running_stats and bn.num_batches_tracked is not None:
         if _NBT_PENDING is not None:
             _NBT_PENDING.append(bn.num_batches_tracked)

@@ -44,6 +44,16 @@ def _call(m: nn.Module, x: Tensor, want_stats: bool):
     return m(x), None                  # (a hooked module is called the plain way: its hooks see a tensor, not (y, statistics))
 
 
+def _frozen_in_graph(bn: nn.Module, x: Tensor, conv: Optional[nn.Module]) -> bool:
+    """An eval-mode BatchNorm with running statistics inside a forward that autograd records (frozen-BatchNorm fine-tuning,
+    gradients of an eval-mode model): it takes the fold too.  Without a graph being recorded (inference) the unfolded passes
+    run as before."""
+    if bn.training or bn.running_mean is None or bn.running_var is None or not torch.is_grad_enabled():
+        return False
+    params = [p for p in (bn.weight, bn.bias, getattr(conv, "weight", None)) if p is not None]
+    return x.requires_grad or any(p.requires_grad for p in params)
+
+
 def _run_chain(mods: Sequence[nn.Module], x: Tensor, want_stats: bool = False):
     """Run conv / BN / ReLU children as fused kernel sequences: a convolution followed by a
     training-mode BatchNorm hands over its epilogue statistics (no separate pass over the
@@ -57,10 +67,11 @@ def _run_chain(mods: Sequence[nn.Module], x: Tensor, want_stats: bool = False):
         if isinstance(m, BatchNorm3d):
             relu = isinstance(nxt, nn.ReLU) and not _has_hooks(m, nxt)      # hooked: BatchNorm and ReLU run (and are observed) one by one
             after = mods[i + 2] if (relu and i + 2 < n) else None
-            if relu and m.training and m.momentum is not None and type(after) is Conv3d and x.is_contiguous() \
-                    and not _has_hooks(m, nxt, after) and after.pre_supported(x.shape):
+            if relu and ((m.training and m.momentum is not None) or _frozen_in_graph(m, x, after)) and type(after) is Conv3d \
+                    and x.is_contiguous() and not _has_hooks(m, nxt, after) and after.pre_supported(x.shape):
                 # BN -> ReLU -> conv (Conv2Plus1D's mid tensor, resnet.py:46-52): the convolution applies the affine +
-                # ReLU while it reads the raw tensor; the normalised tensor is never written or read back
+                # ReLU while it reads the raw tensor; the normalised tensor is never written or read back (a frozen
+                # BatchNorm's affine comes from its running statistics)
                 handle, coef = m(x, stats=stats, defer=True)
                 after_next = mods[i + 3] if i + 3 < n else None
                 feeds = isinstance(after_next, BatchNorm3d) and after_next.training

@@ -7,6 +7,7 @@ instead of a foreign-function interface -- C++ / TorchScript, `torch.library` to
 
     torch.ops.zsv.conv3d(x, w, None, [1, 1, 1], [0, 1, 1])          # nn.Conv3d of resnet.py:40-45, differentiable
     torch.ops.zsv.batch_norm_relu(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, 0.1, 1e-5, True)   # resnet.py:46-49
+    torch.ops.zsv.batch_norm_relu_eval(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, 1e-5, True)  # frozen BatchNorm
 
 `load()` registers the operators (idempotent) and fails loudly when the library has not been built; there is no fallback.
 """
@@ -18,7 +19,8 @@ import torch
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libzsv_torch.so")
 OPERATORS = ("version", "conv3d_fwd", "conv3d_dgrad", "conv3d_wgrad", "bn_train_fwd", "bn_train_bwd", "relu_fwd", "relu_bwd",
-             "linear_fwd", "linear_dgrad", "linear_wgrad", "conv3d", "batch_norm_relu", "relu", "linear")
+             "linear_fwd", "linear_dgrad", "linear_wgrad", "conv3d", "batch_norm_relu", "relu", "linear", "bn_eval_fwd",
+             "bn_eval_bwd", "batch_norm_relu_eval")
 _loaded = False
 
 

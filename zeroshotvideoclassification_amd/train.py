@@ -221,7 +221,7 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], 
     if sharded is None:
         sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     rank, world = (dist.get_rank(group), dist.get_world_size(group)) if sharded else (0, 1)
-    was_training = model.training
+    modes = [(m, m.training) for m in model.modules()]     # per module: a frozen BatchNorm in a training model stays frozen
     model.eval()
     if sharded and sync_state:
         src = 0 if group is None else dist.get_global_rank(group, 0)
@@ -250,7 +250,8 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], 
         # queue every batch (and an idle-then-busy GPU showed sporadic 30-80 ms stalls on the test pool)
         trues.append(z.float().reshape(len(l), -1))
         labels.append(l.reshape(-1))
-    model.train(was_training)
+    for m, training in modes:
+        m.training = training
     class_embed = class_embed.to(device)
     width = int(class_embed.shape[1])
     pred = torch.cat(preds) if preds else torch.zeros((0, width), device=device)
