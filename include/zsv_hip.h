@@ -299,6 +299,26 @@ int zsv_maxpool3d_bf16(const void* x, int32_t N, int32_t C, int32_t Ti, int32_t 
 /* [N][S][Cp] bf16 -> (N, C) fp32 mean over the S voxels (resnet.py:251-254 avgpool + flatten). */
 int zsv_meanpool_bf16(const void* x, int32_t N, int32_t S, int32_t C, float* out, void* stream);
 
+/* ---- e4m3 inference path (the eval loop of main.py:224-313 in OCP fp8) ------------ */
+/* The same folded forward as zsv_conv3d_bf16_fwd (Conv3d -> BatchNorm3d.eval() -> ReLU, resnet.py:40-52,94-98, and
+ * `out += residual; relu`, resnet.py:110-111) with e4m3 (float8_e4m3fn: max 448, no inf) operands:
+ *     y = sat_e4m3( relu?( acc * wscale[cout] + shift[cout] (+ residual) ) ),  acc = sum of e4m3 x e4m3 products in fp32
+ * (v_mfma_f32_16x16x32_fp8_fp8).  Weights: w * scale quantised per produced channel, wscale = max|w * scale| / 448.
+ * Activations are not scaled.  Conversions saturate: beyond +-448 gives +-448, never NaN.
+ *
+ * Activations are channels-last e4m3: [N][T][H][W][Cp] with Cp = zsv_fp8_channel_pitch(C) (C rounded up to 64, one K chunk;
+ * pad channels are written as zero).  A clip (Cin <= 4) stays in the bf16 folded form of zsv_clip_to_bf16 (same descriptor
+ * rules as zsv_conv3d_bf16_fwd, bf16 operands) and only its output is e4m3.  `blob` = the packed weights (e4m3, or bf16 for a
+ * clip) followed by Mp fp32 shifts and Mp fp32 wscale factors (zsv_conv3d_fp8_blob_bytes), built once per layer by
+ * zsv_conv3d_fp8_pack (scale / shift may be NULL = 1 / 0).  `residual` (may be NULL) and y have the output's layout, e4m3. */
+int32_t zsv_fp8_channel_pitch(int32_t channels);
+size_t zsv_conv3d_fp8_blob_bytes(const zsv_conv_desc* d);
+int zsv_conv3d_fp8_pack(const zsv_conv_desc* d, const float* w, const float* scale, const float* shift, void* blob, void* stream);
+int zsv_conv3d_fp8_fwd(const zsv_conv_desc* d, const void* x, const void* blob, const void* residual, int fuse_relu, void* y,
+                       void* stream);
+/* [N][S][Cp] e4m3 -> (N, C) fp32 mean over the S voxels (resnet.py:251-254 avgpool + flatten). */
+int zsv_meanpool_fp8(const void* x, int32_t N, int32_t S, int32_t C, float* out, void* stream);
+
 /* ---- bf16 TRAINING step: the reference's mixed-precision step (main.py:172 `with autocast():`, main.py:137,195-203
  * GradScaler) on channels-last bf16 activations [R = N*T*H*W][Cp] (the layout of the bf16 convolution above).  Under
  * autocast aten::batch_norm keeps fp32 statistics / affine parameters on a reduced-precision input and writes the reduced

@@ -1,5 +1,6 @@
 """bf16 evaluation engine: the reference's eval loop body (main.py:224-252, BASELINE config 5)
-with the VideoResNet trunk run in bf16 on ``zsv_conv3d_bf16_fwd``.
+with the VideoResNet trunk run in bf16 on ``zsv_conv3d_bf16_fwd``; ``Fp8Engine`` is the same walk in
+OCP e4m3 (``float8_e4m3fn``) on ``zsv_conv3d_fp8_fwd``.
 
 ``Bf16Engine(model)`` walks a ``network.Model`` whose trunk is a ``resnet.VideoResNet``
 (R(2+1)D-18 / R3D-18 / MC3-18), folds every eval-mode ``BatchNorm3d`` into the convolution in
@@ -102,6 +103,65 @@ def maxpool3d_bf16(x: torch.Tensor, channels: int, kernel, padding) -> torch.Ten
     return y
 
 
+FP8 = torch.float8_e4m3fn
+
+
+def _check_fp8(t: torch.Tensor, what: str) -> None:
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: MI355X HIP tensor expected, got {t.device} (there is no CPU fallback)")
+    if t.dtype != FP8 or not t.is_contiguous():
+        raise RuntimeError(f"{what}: contiguous float8_e4m3fn tensor expected")
+
+
+def fp8_channel_pitch(channels: int) -> int:
+    return int(_lib.load().zsv_fp8_channel_pitch(int(channels)))
+
+
+def pack_conv_fp8(d: ConvDesc, weight: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor]) -> torch.Tensor:
+    """Packed e4m3 weights (w x scale, quantised per produced channel; bf16 for a clip convolution) + fp32 shifts + fp32
+    dequantisation factors for ``conv_fp8``."""
+    ops._require(weight, scale, shift)
+    lib = _lib.load()
+    nbytes = lib.zsv_conv3d_fp8_blob_bytes(byref(d))
+    if nbytes == 0:
+        raise RuntimeError("zsv_conv3d_fp8_blob_bytes: unsupported convolution geometry")
+    blob = torch.empty(int(nbytes), dtype=torch.uint8, device=weight.device)
+    _lib.check(lib.zsv_conv3d_fp8_pack(byref(d), weight.contiguous().data_ptr(), ops._ptr(scale), ops._ptr(shift),
+                                       blob.data_ptr(), ops._stream()), "zsv_conv3d_fp8_pack")
+    return blob
+
+
+def conv_fp8(d: ConvDesc, x: torch.Tensor, blob: torch.Tensor, residual: Optional[torch.Tensor] = None,
+             relu: bool = False) -> torch.Tensor:
+    """y[N][To][Ho][Wo][Cp] = sat_e4m3(relu?(conv(x) * wscale + shift (+ residual))); x is e4m3, or for a clip convolution
+    (Cin <= 4) the bf16 output of ``clip_to_bf16``."""
+    if d.Cin <= 4:
+        _check_bf16(x, "conv_fp8 clip input")
+    else:
+        _check_fp8(x, "conv_fp8 input")
+    expect = (d.N, d.Ti, d.Hi, d.Wi, fp8_channel_pitch(d.Cin))
+    if tuple(x.shape) != expect:
+        raise RuntimeError(f"conv_fp8: input {tuple(x.shape)} does not match the descriptor {expect}")
+    y = torch.empty((d.N, d.To, d.Ho, d.Wo, fp8_channel_pitch(d.Cout)), dtype=FP8, device=x.device)
+    if residual is not None:
+        _check_fp8(residual, "conv_fp8 residual")
+        if residual.shape != y.shape:
+            raise RuntimeError(f"conv_fp8: residual {tuple(residual.shape)} != output {tuple(y.shape)}")
+    _lib.check(_lib.load().zsv_conv3d_fp8_fwd(byref(d), x.data_ptr(), blob.data_ptr(), ops._ptr(residual),
+                                              1 if relu else 0, y.data_ptr(), ops._stream()), "zsv_conv3d_fp8_fwd")
+    return y
+
+
+def meanpool_fp8(x: torch.Tensor, channels: int) -> torch.Tensor:
+    """[N][T][H][W][Cp] e4m3 -> (N, channels) fp32 mean over the voxels."""
+    _check_fp8(x, "meanpool_fp8 input")
+    n = x.shape[0]
+    s = x.shape[1] * x.shape[2] * x.shape[3]
+    out = torch.empty((n, channels), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().zsv_meanpool_fp8(x.data_ptr(), n, s, channels, out.data_ptr(), ops._stream()), "zsv_meanpool_fp8")
+    return out
+
+
 def fold_bn(bn: Optional[nn.BatchNorm3d], conv: nn.Conv3d) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
     """(scale, shift) of ``bn.eval()(conv(x))``: gamma/sqrt(var+eps), beta - mean*scale (+ conv bias)."""
     bias = conv.bias.detach().float() if conv.bias is not None else None
@@ -162,7 +222,20 @@ class _ConvOp:
         return conv_bf16(d, x, self._blob, residual, self.relu)
 
 
-def _conv_bn_relu_chain(mods: List[nn.Module], keep_modules: bool = False) -> List[_ConvOp]:
+class _ConvOpFp8(_ConvOp):
+    """One folded convolution of ``Fp8Engine``: e4m3 weights with per-channel factors, e4m3 output."""
+
+    def __call__(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, wo: Optional[int] = None) -> torch.Tensor:
+        n, t, h, w, _ = x.shape
+        d = self.desc(n, t, h, w)
+        if wo is not None:
+            d.Wo = wo
+        if self._blob is None:
+            self._blob = pack_conv_fp8(d, self.weight, self.scale, self.shift)
+        return conv_fp8(d, x, self._blob, residual, self.relu)
+
+
+def _conv_bn_relu_chain(mods: List[nn.Module], keep_modules: bool = False, op_cls=_ConvOp) -> List[_ConvOp]:
     """[Conv3d, BN?, ReLU?, Conv3d, ...] (nested Sequentials flattened) -> folded ops."""
     flat: List[nn.Module] = []
 
@@ -189,7 +262,7 @@ def _conv_bn_relu_chain(mods: List[nn.Module], keep_modules: bool = False) -> Li
         if i < len(flat) and isinstance(flat[i], nn.ReLU):
             relu = True
             i += 1
-        op = _ConvOp(conv, bn, relu)
+        op = op_cls(conv, bn, relu)
         if keep_modules:
             op._conv, op._bn = conv, bn
         out.append(op)
@@ -199,29 +272,35 @@ def _conv_bn_relu_chain(mods: List[nn.Module], keep_modules: bool = False) -> Li
 class Bf16Engine:
     """Eval-mode ``Model.forward`` (network.py:533-600) in bf16.  See the module docstring."""
 
+    _name, _op = "Bf16Engine", _ConvOp
+
     def __init__(self, model: nn.Module):
         from . import network, resnet
+        name, chain = self._name, (lambda mods: _conv_bn_relu_chain(mods, op_cls=self._op))
         model = getattr(model, "module", model)
         if not isinstance(model, network.Model) or not isinstance(model.model, resnet.VideoResNet):
-            raise RuntimeError("Bf16Engine supports network.Model over a resnet.VideoResNet trunk")
+            raise RuntimeError(f"{name} supports network.Model over a resnet.VideoResNet trunk")
         if next(model.parameters()).device.type != "cuda":
-            raise RuntimeError("Bf16Engine: the model must live on the MI355X HIP device (there is no CPU fallback)")
+            raise RuntimeError(f"{name}: the model must live on the MI355X HIP device (there is no CPU fallback)")
         self.model = model
         trunk = model.model
-        self.stem = _conv_bn_relu_chain(list(trunk.stem))
+        self.stem = chain(list(trunk.stem))
         if not self.stem[0].folded:
-            raise RuntimeError("Bf16Engine: the stem's first convolution must take the clip (<= 4 channels)")
+            raise RuntimeError(f"{name}: the stem's first convolution must take the clip (<= 4 channels)")
         self.blocks = []
         for layer in (trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4):
             for block in layer:
                 if not isinstance(block, resnet.BasicBlock):
-                    raise RuntimeError("Bf16Engine: only BasicBlock trunks (the reference's *_18 models) are supported")
-                conv1 = _conv_bn_relu_chain(list(block.conv1))
-                conv2 = _conv_bn_relu_chain(list(block.conv2))
+                    raise RuntimeError(f"{name}: only BasicBlock trunks (the reference's *_18 models) are supported")
+                conv1 = chain(list(block.conv1))
+                conv2 = chain(list(block.conv2))
                 conv2[-1].relu = True                   # out += residual; relu (resnet.py:110-111)
-                down = _conv_bn_relu_chain(list(block.downsample)) if block.downsample is not None else None
+                down = chain(list(block.downsample)) if block.downsample is not None else None
                 self.blocks.append((conv1, conv2, down))
         self.features = self.blocks[-1][1][-1].cout
+
+    def _pool(self, x: torch.Tensor) -> torch.Tensor:
+        return meanpool_bf16(x, self.features)
 
     @torch.no_grad()
     def trunk(self, clips: torch.Tensor) -> torch.Tensor:
@@ -245,7 +324,7 @@ class Bf16Engine:
             for op in conv2[:-1]:
                 y = op(y)
             x = conv2[-1](y, residual=residual)
-        return meanpool_bf16(x, self.features)
+        return self._pool(x)
 
     @torch.no_grad()
     def __call__(self, x: torch.Tensor):
@@ -254,6 +333,19 @@ class Bf16Engine:
         pooled = self.trunk(clips)
         emb = self.model.output2emb_proj(pooled)                       # network.py:595 (mean already taken)
         return F.normalize(emb, dim=-1), None                          # network.py:596,600
+
+
+class Fp8Engine(Bf16Engine):
+    """Eval-mode ``Model.forward`` (network.py:533-600) in OCP e4m3: ``Bf16Engine``'s walk, structure checks and
+    contract, with every convolution after the clip's on ``zsv_conv3d_fp8_fwd`` (e4m3 x e4m3, fp32 accumulation, weights
+    quantised per produced channel, activations unscaled and saturating at +-448).  The clip convolution keeps bf16 operands
+    (``zsv_clip_to_bf16``, the folded clip form) and writes e4m3; the mean pool reads e4m3 and writes the fp32 (N, 512) feature;
+    the head and the normalisation stay fp32.  A clip's embedding does not depend on the other clips of its batch."""
+
+    _name, _op = "Fp8Engine", _ConvOpFp8
+
+    def _pool(self, x: torch.Tensor) -> torch.Tensor:
+        return meanpool_fp8(x, self.features)
 
 
 class Bf16EngineC3D:
@@ -396,7 +488,8 @@ class Fp32Engine:
 
 
 def engine_for(model: nn.Module, dtype: torch.dtype = torch.bfloat16, rebuild: bool = False):
-    """The model's inference engine for ``dtype`` (bf16: ``Bf16Engine``, fp32: ``Fp32Engine``), rebuilt only when a
+    """The model's inference engine for ``dtype`` (bf16: ``Bf16Engine``, fp32: ``Fp32Engine``, ``torch.float8_e4m3fn``:
+    ``Fp8Engine``, VideoResNet trunks only), rebuilt only when a
     trunk parameter or BatchNorm buffer may have been written since it was built, e.g. once per epoch for the
     three test sets of main.py:352-358.  "Written" = the tensors' identity / version counters (torch-side
     writes) AND ``_lib.raw_write_generation()``: the HIP BatchNorm running-statistics update, ``FusedAdam``,
@@ -417,6 +510,10 @@ def engine_for(model: nn.Module, dtype: torch.dtype = torch.bfloat16, rebuild: b
             raise RuntimeError("no folded fp32 engine for C3D (it has no BatchNorm to fold): use the module's own forward")
         elif dtype == torch.float32:
             engine = Fp32Engine(own)
+        elif dtype == FP8 and is_c3d:
+            raise RuntimeError("C3D has no fp8 (float8_e4m3fn) engine: use bf16 or the module's own forward")
+        elif dtype == FP8:
+            engine = Fp8Engine(own)
         else:
             raise RuntimeError(f"no inference engine for {dtype} (fp32 or bf16)")
         cached = (key, engine)

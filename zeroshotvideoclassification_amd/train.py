@@ -203,7 +203,8 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], 
     label -1 (failed loads, auxiliary_dataset.py:502-505) are dropped like main.py:246-248.
     ``dtype=torch.bfloat16`` runs the forward on the bf16 engine (``inference.Bf16Engine``, the
     reduced-precision eval of BASELINE config 5 / the reference's autocast, main.py:172), ``torch.float32``
-    on the folded fp32 engine (``inference.Fp32Engine``); default (None): the module's own fp32 forward.
+    on the folded fp32 engine (``inference.Fp32Engine``), ``torch.float8_e4m3fn`` on the e4m3 engine
+    (``inference.Fp8Engine``, VideoResNet trunks only); default (None): the module's own fp32 forward.
 
     With ``torch.distributed`` initialised (one process per GPU; ``sharded`` defaults to that) every rank
     iterates the SAME ``batches`` and runs the forward for every ``world``-th one (batch ``i`` belongs to
@@ -231,9 +232,9 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], 
             _lib.note_raw_write()                          # `.data` writes: cached folded-BatchNorm engines must rebuild
     device = device or next(model.parameters()).device
     forward = model
-    if dtype in (torch.bfloat16, torch.float32):
+    if dtype in (torch.bfloat16, torch.float32, torch.float8_e4m3fn):
         from .inference import engine_for
-        forward = engine_for(model, dtype)                 # BatchNorm folded; fp32 or bf16 activations
+        forward = engine_for(model, dtype)                 # BatchNorm folded; fp32, bf16 or e4m3 activations
     elif dtype is not None:
         raise RuntimeError(f"evaluate: dtype {dtype} is not supported (fp32 or bf16)")
     preds, trues, labels = [], [], []
