@@ -33,7 +33,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from helpers import make_opt  # noqa: E402
-from zeroshotvideoclassification_amd import amp, network, ops, synthetic, train  # noqa: E402
+from zeroshotvideoclassification_amd import amp, inference, network, ops, synthetic, train  # noqa: E402
 
 DEV = "cuda"
 N = 22                                  # clips of the benchmarked step
@@ -471,14 +471,14 @@ POOLS = [("pool1", 64, (16, 112, 112), (1, 2, 2), (0, 0, 0)), ("pool2", 128, (16
 
 @pytest.mark.parametrize("case", POOLS, ids=[c[0] for c in POOLS])
 def test_c3d_pool_and_relu_bias_backward_at_size(case):
-    """``maxpool3d_bf16_fwd`` / ``maxpool3d_bf16_bwd`` and ``relu_bias_bwd_cl`` on each pool's full-size input (the output of a
+    """``maxpool3d_bf16`` / ``maxpool3d_bf16_bwd`` and ``relu_bias_bwd_cl`` on each pool's full-size input (the output of a
     relu(conv + bias): many exact zeros and repeated values): exact against torch on the same values (the gradient to the FIRST
     maximum of a window), the bias gradient against fp64 sums."""
     name, c, (t, h, w), k, p = case
     seed = sum(map(ord, name))
     y = torch.relu(_randn((N, c, t, h, w), seed))
     y_cl = amp.ncdhw_to_cl_bf16(y)
-    pooled = amp.maxpool3d_bf16_fwd(y_cl, c, k, p)
+    pooled = inference.maxpool3d_bf16(y_cl, c, k, p)
     yr = y.clone().requires_grad_(True)
     ref = F.max_pool3d(yr, k, k, p)
     assert torch.equal(amp.cl_to_ncdhw_f32(pooled, c), ref.detach())

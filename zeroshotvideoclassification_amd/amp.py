@@ -17,10 +17,12 @@ scaling is needed for its exponent range, the scaler is supported all the same):
   packed to bf16 once per step; train-mode BatchNorm + ReLU + residual: ``zsv_bn_cl_fwd_train`` (csrc/train_bf16.hip);
 * input gradient: the same convolution kernel on the transposed, tap-flipped weights (a strided convolution's gradient is
   the stride-1 convolution of the zero-interleaved output gradient); BatchNorm / ReLU backward: ``zsv_bn_cl_bwd``;
-* weight gradient: fp32 accumulation of the bf16 operands.  The stride-1 "same" convolutions (1x3x3, 3x1x1, 3x3x3) run
-  ``zsv_conv3d_bf16_wgrad`` (csrc/wgrad_bf16.hip: the contraction runs over voxels, the operands are staged as they lie in
-  memory and read back through gfx950's transposed LDS read); strided convolutions, the 1x1x1 shortcuts and the clip
-  convolution convert the two operands to fp32 NCDHW (``zsv_cl_bf16_to_ncs_f32``) and use the fp32 kernels of the main path;
+* weight gradient: fp32 accumulation of the bf16 operands.  ``zsv_conv3d_bf16_wgrad`` (csrc/wgrad_bf16.hip: the contraction
+  runs over voxels, the operands are staged as they lie in memory and read back through gfx950's transposed LDS read) takes
+  every geometry it reports a workspace for (``zsv_conv3d_bf16_wgrad_workspace_bytes``): the stride-1 "same" 1x3x3 / 3x1x1 /
+  3x3x3 convolutions and, one gathered image per tap, their strided forms and the 1x1x1 shortcuts.  Where it reports none (the
+  clip convolution, other kernel shapes, tensors of 4 GiB and more, ``ZSV_BF16_NO_WGRAD``) the two operands are converted to
+  fp32 NCDHW (``zsv_cl_bf16_to_ncs_f32``) for the fp32 kernel of the main path;
 * the pooled 512-d feature, the MLP head, normalisation and the loss stay fp32 (``ops``), as under autocast's fp32 list.
 
 The whole trunk is ONE ``torch.autograd.Function`` (its forward keeps its own tape): autograd sees
@@ -31,7 +33,7 @@ from __future__ import annotations
 
 import os
 import threading
-from ctypes import byref, c_void_p
+from ctypes import byref
 from typing import List, Optional
 
 import torch
@@ -41,7 +43,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
 from ._lib import ConvDesc
-from .inference import _conv_bn_relu_chain, channel_pitch, clip_to_bf16, conv_bf16, meanpool_bf16, pack_conv
+from .inference import (ConvGeometry, c3d_layers, channel_pitch, clip_to_bf16, conv_bf16, maxpool3d_bf16, meanpool_bf16, pack_conv,
+                        run_blocks, video_resnet_ops)
 
 _state = threading.local()
 
@@ -137,11 +140,7 @@ def bn_cl_fwd_train(z: torch.Tensor, bn: nn.BatchNorm3d, residual: Optional[torc
                                            1 if relu else 0, y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ops._ptr(coef), ws.data_ptr(),
                                            nbytes, ops._stream()), "zsv_bn_cl_fwd_train")
     if track:
-        pending = getattr(_state, "nbt_pending", None)
-        if pending is not None:
-            pending.append(bn.num_batches_tracked)       # one _foreach_add_ at the end of the trunk instead of 37 one-element launches
-        else:
-            bn.num_batches_tracked.add_(1)
+        ops.count_batch(bn)          # (inside ops.batched_bn_counters: one launch at the end of the trunk instead of 37 one-element ones)
     if want_coef:
         return y, mean, invstd, coef
     return y, mean, invstd
@@ -258,38 +257,21 @@ def meanpool_bf16_bwd(dpooled: torch.Tensor, like: torch.Tensor, channels: int) 
 
 
 # ---- one Conv3d -> BatchNorm3d (-> + residual) (-> ReLU) unit -----------------------------------------------------------
-class _Unit:
+class _Unit(ConvGeometry):
+    who = "amp"
+
     def __init__(self, conv: nn.Conv3d, bn: Optional[nn.BatchNorm3d], relu: bool, plain: bool = False):
         """``plain``: C3D's ``relu(conv(x) + bias)`` (network.py:147-162): no BatchNorm, a bias."""
         if bn is None and not plain:
             raise RuntimeError("amp: every trunk convolution is followed by a BatchNorm3d in the reference's VideoResNet")
-        if (conv.bias is not None and not plain) or tuple(conv.dilation) != (1, 1, 1) or conv.groups != 1:
-            raise RuntimeError("amp: bias / dilation / groups are not used by the reference's trunks and not supported")
+        if conv.bias is not None and not plain:
+            raise RuntimeError("amp: a convolution bias is not used by the reference's VideoResNet and not supported")
+        super().__init__(conv)
         self.conv, self.bn, self.relu = conv, bn, relu
-        self.cout, self.cin = conv.weight.shape[0], conv.weight.shape[1]
-        self.kernel = tuple(conv.weight.shape[2:])
-        self.stride, self.padding = tuple(conv.stride), tuple(conv.padding)
-        self.folded = self.cin <= 4            # the clip itself: border materialised, kw folded into K (conv_bf16.hip)
-
-    def desc(self, n, t, h, w, folded_wo=None) -> ConvDesc:
-        """``h, w``: stored extents of the input (with the materialised border for the clip convolution)."""
-        kt, kh, kw = self.kernel
-        pt, ph, pw = self.padding
-        if self.folded:
-            ph = pw = 0
-        st, sh, sw = self.stride
-        to = (t + 2 * pt - kt) // st + 1
-        ho = (h + 2 * ph - kh) // sh + 1
-        wo = (w + 2 * pw - kw) // sw + 1 if folded_wo is None else folded_wo
-        return ConvDesc(n, self.cin, t, h, w, self.cout, to, ho, wo, kt, kh, kw, st, sh, sw, pt, ph, pw)
 
 
 class _Record:
     __slots__ = ("unit", "x", "z", "y", "mean", "invstd", "desc", "has_res", "clips", "coef", "frozen")
-
-
-def _units(mods) -> List[_Unit]:
-    return [_Unit(o._conv, o._bn, o.relu) for o in _conv_bn_relu_chain(list(mods), keep_modules=True)]
 
 
 class Bf16TrainPath:
@@ -302,28 +284,16 @@ class Bf16TrainPath:
         if not isinstance(trunk, resnet.VideoResNet):
             raise RuntimeError("amp: a resnet.VideoResNet trunk is expected")
         self.trunk = trunk
-        self.stem = _units(trunk.stem)
-        if not self.stem[0].folded:
-            raise RuntimeError("amp: the stem's first convolution must take the clip (<= 4 channels)")
-        self.blocks = []
-        for layer in (trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4):
-            for block in layer:
-                if not isinstance(block, resnet.BasicBlock):
-                    raise RuntimeError("amp: only BasicBlock trunks (the reference's *_18 models) are supported")
-                main = _units(list(block.conv1)) + _units(list(block.conv2))
-                main[-1].relu = True                 # out += residual; relu (resnet.py:110-111)
-                down = _units(list(block.downsample)) if block.downsample is not None else None
-                if down is not None and len(down) != 1:
-                    raise RuntimeError("amp: the shortcut is one 1x1x1 convolution + BatchNorm (resnet.py:266-273)")
-                self.blocks.append((main, down[0] if down else None))
-        self.features = self.blocks[-1][0][-1].cout
-        units = list(self.stem)
-        for main, down in self.blocks:
-            units += ([down] if down is not None else []) + main
-        self.units = units
+        self.stem, self.blocks = video_resnet_ops(trunk, _Unit, "amp")
+        if any(down is not None and len(down) != 1 for _, _, down in self.blocks):
+            raise RuntimeError("amp: the shortcut is one 1x1x1 convolution + BatchNorm (resnet.py:266-273)")
+        self.features = self.blocks[-1][1][-1].cout
+        self.units = list(self.stem)                 # in execution order (run_blocks)
+        for conv1, conv2, down in self.blocks:
+            self.units += (down or []) + conv1 + conv2
         # parameter order of the autograd Function: weight, gamma, beta per unit
         self.params = []
-        for u in units:
+        for u in self.units:
             self.params += [p for p in (u.conv.weight, u.bn.weight, u.bn.bias) if p is not None]      # (affine=False: no gamma / beta)
 
     # -- forward -------------------------------------------------------------------------------------------------------
@@ -361,23 +331,11 @@ class Bf16TrainPath:
         return y
 
     def forward(self, clips: torch.Tensor, tape):
-        first = self.stem[0]
-        n, _, t, h, w = clips.shape
-        kt, kh, kw = first.kernel
-        ph, pw = first.padding[1], first.padding[2]
-        wo = (w + 2 * pw - kw) // first.stride[2] + 1
-        hp, wp = h + 2 * ph, max(w + 2 * pw, (wo - 1) * first.stride[2] + 8)
-        x = clip_to_bf16(clips, ph, pw, hp, wp)
-        x = self._unit_fwd(first, x, tape, clips=clips, wo=wo)
+        x, wo = self.stem[0].clip_input(clips)
+        x = self._unit_fwd(self.stem[0], x, tape, clips=clips, wo=wo)
         for u in self.stem[1:]:
             x = self._unit_fwd(u, x, tape)
-        for main, down in self.blocks:
-            residual = x if down is None else self._unit_fwd(down, x, tape)
-            y = x
-            for u in main[:-1]:
-                y = self._unit_fwd(u, y, tape)
-            x = self._unit_fwd(main[-1], y, tape, residual=residual)
-        return x
+        return run_blocks(x, self.blocks, lambda u, x, residual: self._unit_fwd(u, x, tape, residual=residual))
 
     # -- backward pieces -----------------------------------------------------------------------------------------------
     @staticmethod
@@ -448,10 +406,11 @@ class Bf16TrainPath:
 
     @staticmethod
     def _wgrad(r: _Record, dz: torch.Tensor) -> torch.Tensor:
-        """fp32 accumulation of the bf16-rounded operands.  Stride-1 "same" convolutions (1x3x3, 3x1x1, 3x3x3: 90 % of the
-        weight-gradient FLOPs) run ``zsv_conv3d_bf16_wgrad`` on the channels-last bf16 tensors as they are; the strided
-        convolutions, the 1x1x1 shortcuts and the clip convolution convert the two operands to fp32 NCDHW
-        (``zsv_cl_bf16_to_ncs_f32``) and use the fp32 weight-gradient kernels of the main path."""
+        """fp32 accumulation of the bf16-rounded operands.  Every geometry ``zsv_conv3d_bf16_wgrad_workspace_bytes`` reports a
+        workspace for (the trunks' 1x3x3 / 3x1x1 / 3x3x3 convolutions, strided or not, and the 1x1x1 shortcuts) runs
+        ``zsv_conv3d_bf16_wgrad`` on the channels-last bf16 tensors as they are, on the side stream.  The clip convolution, and
+        whatever that query answers 0 for, converts the two operands to fp32 NCDHW (``zsv_cl_bf16_to_ncs_f32``; the clip is
+        fp32 already) for the fp32 weight-gradient kernel of the main path."""
         u, d = r.unit, r.desc
         lib = _lib.load()
         weight = u.conv.weight
@@ -512,10 +471,10 @@ class Bf16TrainPath:
             return dx, g, r
 
         dx = dfeat
-        for main, down in reversed(self.blocks):
+        for conv1, conv2, down in reversed(self.blocks):
             # tail unit: BatchNorm + residual + ReLU -- the masked gradient is also the residual branch's gradient
             dy, g, r_tail = unit_bwd(dx, want_g=True)
-            for _ in main[:-1]:
+            for _ in range(len(conv1) + len(conv2) - 1):
                 dy, _, _ = unit_bwd(dy)
             if down is not None:
                 dxd, _, _ = unit_bwd(g)
@@ -534,37 +493,15 @@ class Bf16TrainPathC3D:
     of the last pool, flattened in the module's (C, T, H, W) order, is this path's result)."""
 
     def __init__(self, model: nn.Module):
-        from .inference import Bf16EngineC3D
         self.model = model
-        self.layers = []
-        for conv_name, pool_name in Bf16EngineC3D.LAYERS:
-            conv = getattr(model, conv_name)
-            u = _Unit(conv, None, True, plain=True)
-            pool = getattr(model, pool_name) if pool_name else None
-            if pool is not None:
-                k, st, pd = pool.kernel_size, pool.stride, pool.padding
-                k = (k,) * 3 if isinstance(k, int) else tuple(k)
-                st = k if st is None else ((st,) * 3 if isinstance(st, int) else tuple(st))
-                pd = (pd,) * 3 if isinstance(pd, int) else tuple(pd)
-                if st != k:
-                    raise RuntimeError("amp: max-pools with stride != kernel are not used by the reference")
-                pool = (k, pd)
-            self.layers.append((u, pool))
-        if not self.layers[0][0].folded:
-            raise RuntimeError("amp: C3D's conv1 must take the clip (<= 4 channels)")
+        self.layers = [(_Unit(conv, None, True, plain=True), pool) for conv, pool in c3d_layers(model, "amp")]
         self.features = self.layers[-1][0].cout
         self.params = []
         for u, _ in self.layers:
             self.params += [u.conv.weight, u.conv.bias]
 
     def forward(self, clips: torch.Tensor, tape):
-        first = self.layers[0][0]
-        n, _, t, h, w = clips.shape
-        kt, kh, kw = first.kernel
-        ph, pw = first.padding[1], first.padding[2]
-        wo = (w + 2 * pw - kw) // first.stride[2] + 1
-        hp, wp = h + 2 * ph, max(w + 2 * pw, (wo - 1) * first.stride[2] + 8)
-        x = clip_to_bf16(clips, ph, pw, hp, wp)
+        x, wo = self.layers[0][0].clip_input(clips)
         for i, (u, pool) in enumerate(self.layers):
             nn_, t_, h_, w_, _ = x.shape
             d = u.desc(nn_, t_, h_, w_, wo if i == 0 else None)
@@ -577,7 +514,7 @@ class Bf16TrainPathC3D:
             x = y
             pooled = None
             if pool is not None:
-                pooled = maxpool3d_bf16_fwd(y, u.cout, pool[0], pool[1])
+                pooled = maxpool3d_bf16(y, u.cout, pool[0], pool[1])
                 x = pooled
             if tape is not None:
                 tape.append((r, pool, pooled))
@@ -601,9 +538,18 @@ class Bf16TrainPathC3D:
         return grads
 
 
-def maxpool3d_bf16_fwd(x, channels, kernel, padding):
-    from .inference import maxpool3d_bf16
-    return maxpool3d_bf16(x, channels, kernel, padding)
+def _new_tape(record: bool, params) -> Optional[list]:
+    """The tape of one forward of a trunk ``Function``, or None when nothing will ask for a backward (``record``: grad mode at the
+    call site -- inside a Function's forward it is always off; no tape under torch.no_grad())."""
+    return [] if record and any(p.requires_grad for p in params) else None
+
+
+def _backward_result(ctx, grads: Optional[dict]):
+    """What a trunk ``Function``'s backward returns for ``(clips, path, record, *path.params)``: ``grads`` ({parameter id:
+    gradient}, None: there was nothing to do) in ``path.params`` order, for the parameters autograd asks for."""
+    if grads is None:
+        return (None,) * (3 + ctx.n_params)
+    return (None, None, None) + tuple(grads.get(id(p)) if need else None for p, need in zip(ctx.path.params, ctx.needs_input_grad[3:]))
 
 
 class _C3DTrunkBf16(Function):
@@ -613,7 +559,7 @@ class _C3DTrunkBf16(Function):
     @staticmethod
     def forward(ctx, clips, path, record, *params):
         ops._require(clips)
-        tape = [] if record and any(p.requires_grad for p in params) else None
+        tape = _new_tape(record, params)
         with torch.cuda.device(clips.device):
             last = path.forward(clips.contiguous(), tape)
             n = last.shape[0]
@@ -628,14 +574,13 @@ class _C3DTrunkBf16(Function):
     def backward(ctx, dfeat):
         path, tape = ctx.path, ctx.tape
         if dfeat is None or tape is None:
-            return (None, None, None) + (None,) * ctx.n_params
+            return _backward_result(ctx, None)
         n, t, h, w, _ = ctx.last_shape
         with torch.cuda.device(dfeat.device):
             dlast = ncdhw_to_cl_bf16(dfeat.float().reshape(n, path.features, t, h, w))
             grads = path.backward(tape, dlast)
         ctx.tape = None
-        out = [grads.get(id(p)) if ctx.needs_input_grad[3 + i] else None for i, p in enumerate(path.params)]
-        return (None, None, None) + tuple(out)
+        return _backward_result(ctx, grads)
 
 
 def c3d_features(model: nn.Module, clips: torch.Tensor) -> torch.Tensor:
@@ -668,13 +613,8 @@ class _GraphedTrunk:
 
         def forward_body():
             tape = []
-            _state.nbt_pending = []
-            try:
+            with ops.batched_bn_counters():              # (ends inside the captured region: the counters advance on replay)
                 feat = path.forward(self.clips, tape)
-            finally:
-                pending, _state.nbt_pending = _state.nbt_pending, None
-            if pending:
-                torch._foreach_add_(pending, 1)
             return tape, feat, meanpool_bf16(feat, path.features)
 
         def backward_body(tape, feat, dpooled):
@@ -764,16 +704,10 @@ class _TrunkBf16(Function):
             ctx.graphed, ctx.generation, ctx.n_params = g, g.generation, len(params)
             ctx.set_materialize_grads(False)
             return pooled
-        # (`record`: grad mode at the call site -- inside a Function's forward it is always off; no tape under torch.no_grad())
-        tape = [] if record and any(p.requires_grad for p in params) else None
+        tape = _new_tape(record, params)
         with torch.cuda.device(clips.device):
-            _state.nbt_pending = []
-            try:
+            with ops.batched_bn_counters():
                 feat = path.forward(clips.contiguous(), tape)
-            finally:
-                pending, _state.nbt_pending = _state.nbt_pending, None
-            if pending:
-                torch._foreach_add_(pending, 1)
             pooled = meanpool_bf16(feat, path.features)
         ctx.path, ctx.tape, ctx.feat_like = path, tape, feat
         ctx.n_params = len(params)
@@ -785,22 +719,18 @@ class _TrunkBf16(Function):
     def backward(ctx, dpooled):
         if ctx.graphed is not None:
             if dpooled is None:
-                return (None, None, None) + (None,) * ctx.n_params
+                return _backward_result(ctx, None)
             with torch.cuda.device(dpooled.device):
                 out = ctx.graphed.backward(dpooled.float(), ctx.generation, ctx.needs_input_grad[3:])
             return (None, None, None) + tuple(out)
         path, tape = ctx.path, ctx.tape
         if dpooled is None or tape is None:
-            return (None, None, None) + (None,) * ctx.n_params
+            return _backward_result(ctx, None)
         with torch.cuda.device(dpooled.device):
             dfeat = meanpool_bf16_bwd(dpooled.float(), ctx.feat_like, path.features)
             grads = path.backward(tape, dfeat)
         ctx.tape = None
-        out = []
-        for i, p in enumerate(path.params):
-            g = grads.get(id(p)) if ctx.needs_input_grad[3 + i] else None
-            out.append(g)
-        return (None, None, None) + tuple(out)
+        return _backward_result(ctx, grads)
 
 
 def trunk_features(trunk: nn.Module, clips: torch.Tensor) -> torch.Tensor:

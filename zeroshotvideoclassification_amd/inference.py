@@ -17,6 +17,7 @@ weights change.  There is no CPU fallback.
 from __future__ import annotations
 
 from ctypes import byref
+from functools import lru_cache, partial
 from typing import List, Optional, Tuple
 
 import torch
@@ -27,15 +28,33 @@ from . import _lib, ops
 from ._lib import ConvDesc
 
 
-def _check_bf16(t: torch.Tensor, what: str) -> None:
+class _Format:
+    """One element format of the channels-last engines: the tensor dtype, the C entry points and the public functions' names in
+    messages (all formed here, once), and the format a clip convolution (Cin <= 4) reads -- an e4m3 clip convolution takes the
+    bf16 output of ``clip_to_bf16``."""
+
+    def __init__(self, name: str, dtype: torch.dtype, label: str, clip: Optional["_Format"] = None):
+        self.name, self.dtype, self.label, self.clip = name, dtype, label, clip or self
+        self.conv_name, self.meanpool_name = f"conv_{name}", f"meanpool_{name}"
+        self.pitch, self.meanpool = f"zsv_{name}_channel_pitch", f"zsv_meanpool_{name}"
+        self.blob_bytes, self.pack, self.fwd = (f"zsv_conv3d_{name}_{f}" for f in ("blob_bytes", "pack", "fwd"))
+
+
+FP8 = torch.float8_e4m3fn
+BF16 = _Format("bf16", torch.bfloat16, "bf16")
+E4M3 = _Format("fp8", FP8, "float8_e4m3fn", clip=BF16)
+
+
+def _check(t: torch.Tensor, fmt: _Format, op: str, what: str) -> None:
     if not t.is_cuda:
-        raise RuntimeError(f"{what}: MI355X HIP tensor expected, got {t.device} (there is no CPU fallback)")
-    if t.dtype != torch.bfloat16 or not t.is_contiguous():
-        raise RuntimeError(f"{what}: contiguous bf16 tensor expected")
+        raise RuntimeError(f"{op} {what}: MI355X HIP tensor expected, got {t.device} (there is no CPU fallback)")
+    if t.dtype != fmt.dtype or not t.is_contiguous():
+        raise RuntimeError(f"{op} {what}: contiguous {fmt.label} tensor expected")
 
 
-def channel_pitch(channels: int) -> int:
-    return int(_lib.load().zsv_bf16_channel_pitch(int(channels)))
+@lru_cache(maxsize=None)                   # (a pure function of its arguments, asked twice per convolution launch)
+def _pitch(fmt: _Format, channels: int) -> int:
+    return int(getattr(_lib.load(), fmt.pitch)(int(channels)))
 
 
 def clip_to_bf16(x: torch.Tensor, pad_h: int, pad_w: int, hp: int, wp: int) -> torch.Tensor:
@@ -49,50 +68,59 @@ def clip_to_bf16(x: torch.Tensor, pad_h: int, pad_w: int, hp: int, wp: int) -> t
     return out
 
 
-def pack_conv(d: ConvDesc, weight: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor]) -> torch.Tensor:
-    """Packed bf16 weights (x scale per produced channel) + fp32 shifts for ``conv_bf16``."""
+def _pack(fmt: _Format, d: ConvDesc, weight: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor]) -> torch.Tensor:
+    """Packed weights (x scale per produced channel) + fp32 shifts for ``_conv``; e4m3: quantised per produced channel (bf16 for
+    a clip convolution), with the fp32 dequantisation factors behind the shifts."""
     ops._require(weight, scale, shift)
     lib = _lib.load()
-    nbytes = lib.zsv_conv3d_bf16_blob_bytes(byref(d))
+    nbytes = getattr(lib, fmt.blob_bytes)(byref(d))
     if nbytes == 0:
-        raise RuntimeError("zsv_conv3d_bf16_blob_bytes: unsupported convolution geometry")
+        raise RuntimeError(f"{fmt.blob_bytes}: unsupported convolution geometry")
     blob = torch.empty(int(nbytes), dtype=torch.uint8, device=weight.device)
-    _lib.check(lib.zsv_conv3d_bf16_pack(byref(d), weight.contiguous().data_ptr(), ops._ptr(scale), ops._ptr(shift),
-                                        blob.data_ptr(), ops._stream()), "zsv_conv3d_bf16_pack")
+    _lib.check(getattr(lib, fmt.pack)(byref(d), weight.contiguous().data_ptr(), ops._ptr(scale), ops._ptr(shift), blob.data_ptr(),
+                                      ops._stream()), fmt.pack)
     return blob
 
 
-def conv_bf16(d: ConvDesc, x: torch.Tensor, blob: torch.Tensor, residual: Optional[torch.Tensor] = None,
-              relu: bool = False) -> torch.Tensor:
-    """y[N][To][Ho][Wo][Cp] = relu?(conv(x) * scale + shift (+ residual)) in bf16."""
-    _check_bf16(x, "conv_bf16 input")
-    expect = (d.N, d.Ti, d.Hi, d.Wi, channel_pitch(d.Cin))
+def _conv(fmt: _Format, d: ConvDesc, x: torch.Tensor, blob: torch.Tensor, residual: Optional[torch.Tensor] = None,
+          relu: bool = False) -> torch.Tensor:
+    """y[N][To][Ho][Wo][Cp] = relu?(conv(x) * scale + shift (+ residual)) in ``fmt`` (e4m3: saturating)."""
+    what = fmt.conv_name
+    if fmt.clip is not fmt and d.Cin <= 4:
+        _check(x, fmt.clip, what, "clip input")
+    else:
+        _check(x, fmt, what, "input")
+    expect = (d.N, d.Ti, d.Hi, d.Wi, _pitch(fmt, d.Cin))
     if tuple(x.shape) != expect:
-        raise RuntimeError(f"conv_bf16: input {tuple(x.shape)} does not match the descriptor {expect}")
-    y = torch.empty((d.N, d.To, d.Ho, d.Wo, channel_pitch(d.Cout)), dtype=torch.bfloat16, device=x.device)
+        raise RuntimeError(f"{what}: input {tuple(x.shape)} does not match the descriptor {expect}")
+    y = torch.empty((d.N, d.To, d.Ho, d.Wo, _pitch(fmt, d.Cout)), dtype=fmt.dtype, device=x.device)
     if residual is not None:
-        _check_bf16(residual, "conv_bf16 residual")
+        _check(residual, fmt, what, "residual")
         if residual.shape != y.shape:
-            raise RuntimeError(f"conv_bf16: residual {tuple(residual.shape)} != output {tuple(y.shape)}")
-    _lib.check(_lib.load().zsv_conv3d_bf16_fwd(byref(d), x.data_ptr(), blob.data_ptr(), ops._ptr(residual),
-                                               1 if relu else 0, y.data_ptr(), ops._stream()), "zsv_conv3d_bf16_fwd")
+            raise RuntimeError(f"{what}: residual {tuple(residual.shape)} != output {tuple(y.shape)}")
+    _lib.check(getattr(_lib.load(), fmt.fwd)(byref(d), x.data_ptr(), blob.data_ptr(), ops._ptr(residual), 1 if relu else 0,
+                                             y.data_ptr(), ops._stream()), fmt.fwd)
     return y
 
 
-def meanpool_bf16(x: torch.Tensor, channels: int) -> torch.Tensor:
-    """[N][T][H][W][Cp] bf16 -> (N, channels) fp32 mean over the voxels."""
-    _check_bf16(x, "meanpool_bf16 input")
+def _meanpool(fmt: _Format, x: torch.Tensor, channels: int) -> torch.Tensor:
+    """[N][T][H][W][Cp] -> (N, channels) fp32 mean over the voxels."""
+    _check(x, fmt, fmt.meanpool_name, "input")
     n = x.shape[0]
     s = x.shape[1] * x.shape[2] * x.shape[3]
     out = torch.empty((n, channels), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().zsv_meanpool_bf16(x.data_ptr(), n, s, channels, out.data_ptr(), ops._stream()),
-               "zsv_meanpool_bf16")
+    _lib.check(getattr(_lib.load(), fmt.meanpool)(x.data_ptr(), n, s, channels, out.data_ptr(), ops._stream()), fmt.meanpool)
     return out
+
+
+# the public per-format names: (d, weight, scale, shift) / (d, x, blob, residual=None, relu=False) / (x, channels) / (channels)
+pack_conv, conv_bf16, meanpool_bf16, channel_pitch = (partial(f, BF16) for f in (_pack, _conv, _meanpool, _pitch))
+pack_conv_fp8, conv_fp8, meanpool_fp8, fp8_channel_pitch = (partial(f, E4M3) for f in (_pack, _conv, _meanpool, _pitch))
 
 
 def maxpool3d_bf16(x: torch.Tensor, channels: int, kernel, padding) -> torch.Tensor:
     """nn.MaxPool3d(kernel, stride = kernel, padding) on [N][T][H][W][Cp] bf16 (network.py:148-163)."""
-    _check_bf16(x, "maxpool3d_bf16 input")
+    _check(x, BF16, "maxpool3d_bf16", "input")
     n, t, h, w, cp = x.shape
     kt, kh, kw = (int(v) for v in kernel)
     pt, ph, pw = (int(v) for v in padding)
@@ -101,65 +129,6 @@ def maxpool3d_bf16(x: torch.Tensor, channels: int, kernel, padding) -> torch.Ten
     _lib.check(_lib.load().zsv_maxpool3d_bf16(x.data_ptr(), n, channels, t, h, w, kt, kh, kw, pt, ph, pw, to, ho, wo, y.data_ptr(),
                                               ops._stream()), "zsv_maxpool3d_bf16")
     return y
-
-
-FP8 = torch.float8_e4m3fn
-
-
-def _check_fp8(t: torch.Tensor, what: str) -> None:
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: MI355X HIP tensor expected, got {t.device} (there is no CPU fallback)")
-    if t.dtype != FP8 or not t.is_contiguous():
-        raise RuntimeError(f"{what}: contiguous float8_e4m3fn tensor expected")
-
-
-def fp8_channel_pitch(channels: int) -> int:
-    return int(_lib.load().zsv_fp8_channel_pitch(int(channels)))
-
-
-def pack_conv_fp8(d: ConvDesc, weight: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor]) -> torch.Tensor:
-    """Packed e4m3 weights (w x scale, quantised per produced channel; bf16 for a clip convolution) + fp32 shifts + fp32
-    dequantisation factors for ``conv_fp8``."""
-    ops._require(weight, scale, shift)
-    lib = _lib.load()
-    nbytes = lib.zsv_conv3d_fp8_blob_bytes(byref(d))
-    if nbytes == 0:
-        raise RuntimeError("zsv_conv3d_fp8_blob_bytes: unsupported convolution geometry")
-    blob = torch.empty(int(nbytes), dtype=torch.uint8, device=weight.device)
-    _lib.check(lib.zsv_conv3d_fp8_pack(byref(d), weight.contiguous().data_ptr(), ops._ptr(scale), ops._ptr(shift),
-                                       blob.data_ptr(), ops._stream()), "zsv_conv3d_fp8_pack")
-    return blob
-
-
-def conv_fp8(d: ConvDesc, x: torch.Tensor, blob: torch.Tensor, residual: Optional[torch.Tensor] = None,
-             relu: bool = False) -> torch.Tensor:
-    """y[N][To][Ho][Wo][Cp] = sat_e4m3(relu?(conv(x) * wscale + shift (+ residual))); x is e4m3, or for a clip convolution
-    (Cin <= 4) the bf16 output of ``clip_to_bf16``."""
-    if d.Cin <= 4:
-        _check_bf16(x, "conv_fp8 clip input")
-    else:
-        _check_fp8(x, "conv_fp8 input")
-    expect = (d.N, d.Ti, d.Hi, d.Wi, fp8_channel_pitch(d.Cin))
-    if tuple(x.shape) != expect:
-        raise RuntimeError(f"conv_fp8: input {tuple(x.shape)} does not match the descriptor {expect}")
-    y = torch.empty((d.N, d.To, d.Ho, d.Wo, fp8_channel_pitch(d.Cout)), dtype=FP8, device=x.device)
-    if residual is not None:
-        _check_fp8(residual, "conv_fp8 residual")
-        if residual.shape != y.shape:
-            raise RuntimeError(f"conv_fp8: residual {tuple(residual.shape)} != output {tuple(y.shape)}")
-    _lib.check(_lib.load().zsv_conv3d_fp8_fwd(byref(d), x.data_ptr(), blob.data_ptr(), ops._ptr(residual),
-                                              1 if relu else 0, y.data_ptr(), ops._stream()), "zsv_conv3d_fp8_fwd")
-    return y
-
-
-def meanpool_fp8(x: torch.Tensor, channels: int) -> torch.Tensor:
-    """[N][T][H][W][Cp] e4m3 -> (N, channels) fp32 mean over the voxels."""
-    _check_fp8(x, "meanpool_fp8 input")
-    n = x.shape[0]
-    s = x.shape[1] * x.shape[2] * x.shape[3]
-    out = torch.empty((n, channels), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().zsv_meanpool_fp8(x.data_ptr(), n, s, channels, out.data_ptr(), ops._stream()), "zsv_meanpool_fp8")
-    return out
 
 
 def fold_bn(bn: Optional[nn.BatchNorm3d], conv: nn.Conv3d) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
@@ -177,31 +146,23 @@ def fold_bn(bn: Optional[nn.BatchNorm3d], conv: nn.Conv3d) -> Tuple[Optional[tor
     return scale.float().contiguous(), shift.float().contiguous()
 
 
-class _ConvOp:
-    """One folded convolution: geometry is resolved per input shape, the packed blob per layer."""
+class ConvGeometry:
+    """The extents of one ``nn.Conv3d`` and what follows from them: the kernel descriptor for a stored input, and for the clip
+    convolution (``folded``) the materialised border."""
 
-    def __init__(self, conv: nn.Conv3d, bn: Optional[nn.BatchNorm3d], relu: bool):
-        self.weight = conv.weight.detach().float().contiguous()
-        self.scale, self.shift = fold_bn(bn, conv)
-        self.stride = tuple(conv.stride)
-        self.padding = tuple(conv.padding)
-        self.relu = relu
-        self.cout, self.cin = self.weight.shape[0], self.weight.shape[1]
-        self.kernel = tuple(self.weight.shape[2:])
+    who = "inference"                          # the prefix of this class's error messages
+
+    def __init__(self, conv: nn.Conv3d):
         if tuple(conv.dilation) != (1, 1, 1) or conv.groups != 1:
-            raise RuntimeError("Bf16Engine: dilation / groups are not used by the reference and not supported")
-        self.folded = self.cin <= 4            # the clip itself: border materialised, kw folded into K
-        self._blob = None
+            raise RuntimeError(f"{self.who}: dilation / groups are not used by the reference and not supported")
+        self.cout, self.cin = conv.weight.shape[0], conv.weight.shape[1]
+        self.kernel = tuple(conv.weight.shape[2:])
+        self.stride, self.padding = tuple(conv.stride), tuple(conv.padding)
+        self.folded = self.cin <= 4            # the clip itself: border materialised, kw folded into K (conv_bf16.hip)
 
-    def input_border(self, h: int, w: int) -> Tuple[int, int, int, int]:
-        """(pad_h, pad_w, Hp, Wp) of the materialised border for the clip convolution."""
-        kt, kh, kw = self.kernel
-        ph, pw = self.padding[1], self.padding[2]
-        wo = (w + 2 * pw - kw) // self.stride[2] + 1
-        return ph, pw, h + 2 * ph, max(w + 2 * pw, (wo - 1) * self.stride[2] + 8)
-
-    def desc(self, n: int, t: int, h: int, w: int) -> ConvDesc:
-        """``h, w`` are the stored extents (border included for the clip convolution)."""
+    def desc(self, n: int, t: int, h: int, w: int, folded_wo: Optional[int] = None) -> ConvDesc:
+        """``h, w``: stored extents of the input (with the materialised border for the clip convolution, whose output width
+        ``folded_wo`` then comes from ``clip_input``)."""
         kt, kh, kw = self.kernel
         pt, ph, pw = self.padding
         if self.folded:
@@ -209,34 +170,43 @@ class _ConvOp:
         st, sh, sw = self.stride
         to = (t + 2 * pt - kt) // st + 1
         ho = (h + 2 * ph - kh) // sh + 1
-        wo = (w + 2 * pw - kw) // sw + 1
+        wo = (w + 2 * pw - kw) // sw + 1 if folded_wo is None else folded_wo
         return ConvDesc(n, self.cin, t, h, w, self.cout, to, ho, wo, kt, kh, kw, st, sh, sw, pt, ph, pw)
 
+    def _clip_wo(self, w: int) -> int:
+        return (w + 2 * self.padding[2] - self.kernel[2]) // self.stride[2] + 1
+
+    def input_border(self, h: int, w: int) -> Tuple[int, int, int, int]:
+        """(pad_h, pad_w, Hp, Wp) of the materialised border for the clip convolution."""
+        ph, pw = self.padding[1], self.padding[2]
+        return ph, pw, h + 2 * ph, max(w + 2 * pw, (self._clip_wo(w) - 1) * self.stride[2] + 8)
+
+    def clip_input(self, clips: torch.Tensor) -> Tuple[torch.Tensor, int]:
+        """(N, 3, T, H, W) fp32 -> (the clip in bf16 inside its border, the ``folded_wo`` of this convolution on it)."""
+        h, w = clips.shape[3:]
+        return clip_to_bf16(clips, *self.input_border(h, w)), self._clip_wo(w)
+
+
+class _ConvOp(ConvGeometry):
+    """One folded convolution: geometry is resolved per input shape, the packed blob per layer."""
+
+    def __init__(self, conv: nn.Conv3d, bn: Optional[nn.BatchNorm3d], relu: bool, fmt: _Format = BF16):
+        super().__init__(conv)
+        self.weight = conv.weight.detach().float().contiguous()
+        self.scale, self.shift = fold_bn(bn, conv)
+        self.relu, self.fmt = relu, fmt
+        self._blob = None
+
     def __call__(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, wo: Optional[int] = None) -> torch.Tensor:
         n, t, h, w, _ = x.shape
-        d = self.desc(n, t, h, w)
-        if wo is not None:
-            d.Wo = wo
+        d = self.desc(n, t, h, w, wo)
         if self._blob is None:
-            self._blob = pack_conv(d, self.weight, self.scale, self.shift)
-        return conv_bf16(d, x, self._blob, residual, self.relu)
+            self._blob = _pack(self.fmt, d, self.weight, self.scale, self.shift)
+        return _conv(self.fmt, d, x, self._blob, residual, self.relu)
 
 
-class _ConvOpFp8(_ConvOp):
-    """One folded convolution of ``Fp8Engine``: e4m3 weights with per-channel factors, e4m3 output."""
-
-    def __call__(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, wo: Optional[int] = None) -> torch.Tensor:
-        n, t, h, w, _ = x.shape
-        d = self.desc(n, t, h, w)
-        if wo is not None:
-            d.Wo = wo
-        if self._blob is None:
-            self._blob = pack_conv_fp8(d, self.weight, self.scale, self.shift)
-        return conv_fp8(d, x, self._blob, residual, self.relu)
-
-
-def _conv_bn_relu_chain(mods: List[nn.Module], keep_modules: bool = False, op_cls=_ConvOp) -> List[_ConvOp]:
-    """[Conv3d, BN?, ReLU?, Conv3d, ...] (nested Sequentials flattened) -> folded ops."""
+def conv_bn_relu_chain(mods, who: str) -> List[Tuple[nn.Conv3d, Optional[nn.BatchNorm3d], bool]]:
+    """[Conv3d, BN?, ReLU?, Conv3d, ...] (nested Sequentials flattened) -> (conv, bn or None, relu) triples."""
     flat: List[nn.Module] = []
 
     def walk(m):
@@ -247,12 +217,12 @@ def _conv_bn_relu_chain(mods: List[nn.Module], keep_modules: bool = False, op_cl
                 walk(c)
     for m in mods:
         walk(m)
-    out: List[_ConvOp] = []
+    out = []
     i = 0
     while i < len(flat):
         conv = flat[i]
         if not isinstance(conv, nn.Conv3d):
-            raise RuntimeError(f"Bf16Engine: expected a Conv3d, found {type(conv).__name__}")
+            raise RuntimeError(f"{who}: expected a Conv3d, found {type(conv).__name__}")
         i += 1
         bn = None
         if i < len(flat) and isinstance(flat[i], nn.BatchNorm3d):
@@ -262,69 +232,97 @@ def _conv_bn_relu_chain(mods: List[nn.Module], keep_modules: bool = False, op_cl
         if i < len(flat) and isinstance(flat[i], nn.ReLU):
             relu = True
             i += 1
-        op = op_cls(conv, bn, relu)
-        if keep_modules:
-            op._conv, op._bn = conv, bn
-        out.append(op)
+        out.append((conv, bn, relu))
     return out
+
+
+def video_resnet_ops(trunk: nn.Module, make, who: str):
+    """``stem, [(conv1, conv2, down or None)]``: a ``resnet.VideoResNet`` of BasicBlocks as lists of ``make(conv, bn, relu)``
+    objects (which carry a writable ``.relu``), in the order ``run_blocks`` executes them."""
+    from . import resnet
+
+    def chain(mods):
+        return [make(*triple) for triple in conv_bn_relu_chain(mods, who)]
+    if conv_bn_relu_chain(trunk.stem, who)[0][0].weight.shape[1] > 4:
+        raise RuntimeError(f"{who}: the stem's first convolution must take the clip (<= 4 channels)")
+    stem, blocks = chain(trunk.stem), []
+    for layer in (trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4):
+        for block in layer:
+            if not isinstance(block, resnet.BasicBlock):
+                raise RuntimeError(f"{who}: only BasicBlock trunks (the reference's *_18 models) are supported")
+            conv1, conv2 = chain(block.conv1), chain(block.conv2)
+            conv2[-1].relu = True                   # out += residual; relu (resnet.py:110-111)
+            blocks.append((conv1, conv2, chain(block.downsample) if block.downsample is not None else None))
+    return stem, blocks
+
+
+def run_blocks(x, blocks, call):
+    """The residual blocks of ``video_resnet_ops`` on ``x``; ``call(op, x, residual or None)`` runs one of their objects."""
+    for conv1, conv2, down in blocks:
+        residual = x
+        for op in down or ():
+            residual = call(op, residual, None)
+        y = x
+        for op in conv1:
+            y = call(op, y, None)
+        for op in conv2[:-1]:
+            y = call(op, y, None)
+        x = call(conv2[-1], y, residual)
+    return x
+
+
+def c3d_layers(model: nn.Module, who: str):
+    """``network.C3D``'s eight ``relu(conv(x) + bias)`` layers in order (network.py:147-163): (conv, (kernel, padding) of the
+    max-pool behind it or None)."""
+    if model.conv1.weight.shape[1] > 4:
+        raise RuntimeError(f"{who}: conv1 must take the clip (<= 4 channels)")
+    for conv, pool in (("conv1", "pool1"), ("conv2", "pool2"), ("conv3a", None), ("conv3b", "pool3"), ("conv4a", None),
+                       ("conv4b", "pool4"), ("conv5a", None), ("conv5b", "pool5")):
+        if pool is not None:
+            pool = getattr(model, pool)
+            k, pd = ops._triple(pool.kernel_size), ops._triple(pool.padding)
+            if pool.stride is not None and ops._triple(pool.stride) != k:
+                raise RuntimeError(f"{who}: max-pools with stride != kernel are not used by the reference")
+            pool = (k, pd)
+        yield getattr(model, conv), pool
+
+
+def _device_model(model: nn.Module, who: str, c3d: bool = False) -> nn.Module:
+    """The unwrapped model of an engine, after the two refusals that need no trunk walk (in this order)."""
+    from . import network, resnet
+    model = getattr(model, "module", model)
+    if c3d and not isinstance(model, network.C3D):
+        raise RuntimeError(f"{who} supports network.C3D")
+    if not c3d and not (isinstance(model, network.Model) and isinstance(model.model, resnet.VideoResNet)):
+        raise RuntimeError(f"{who} supports network.Model over a resnet.VideoResNet trunk")
+    if next(model.parameters()).device.type != "cuda":
+        raise RuntimeError(f"{who}: the model must live on the MI355X HIP device (there is no CPU fallback)")
+    return model
+
+
+def _call_op(op, x, residual):
+    return op(x, residual=residual)
 
 
 class Bf16Engine:
     """Eval-mode ``Model.forward`` (network.py:533-600) in bf16.  See the module docstring."""
 
-    _name, _op = "Bf16Engine", _ConvOp
+    _fmt = BF16
 
     def __init__(self, model: nn.Module):
-        from . import network, resnet
-        name, chain = self._name, (lambda mods: _conv_bn_relu_chain(mods, op_cls=self._op))
-        model = getattr(model, "module", model)
-        if not isinstance(model, network.Model) or not isinstance(model.model, resnet.VideoResNet):
-            raise RuntimeError(f"{name} supports network.Model over a resnet.VideoResNet trunk")
-        if next(model.parameters()).device.type != "cuda":
-            raise RuntimeError(f"{name}: the model must live on the MI355X HIP device (there is no CPU fallback)")
-        self.model = model
-        trunk = model.model
-        self.stem = chain(list(trunk.stem))
-        if not self.stem[0].folded:
-            raise RuntimeError(f"{name}: the stem's first convolution must take the clip (<= 4 channels)")
-        self.blocks = []
-        for layer in (trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4):
-            for block in layer:
-                if not isinstance(block, resnet.BasicBlock):
-                    raise RuntimeError(f"{name}: only BasicBlock trunks (the reference's *_18 models) are supported")
-                conv1 = chain(list(block.conv1))
-                conv2 = chain(list(block.conv2))
-                conv2[-1].relu = True                   # out += residual; relu (resnet.py:110-111)
-                down = chain(list(block.downsample)) if block.downsample is not None else None
-                self.blocks.append((conv1, conv2, down))
+        who = type(self).__name__
+        self.model = _device_model(model, who)
+        self.stem, self.blocks = video_resnet_ops(self.model.model, partial(_ConvOp, fmt=self._fmt), who)
         self.features = self.blocks[-1][1][-1].cout
-
-    def _pool(self, x: torch.Tensor) -> torch.Tensor:
-        return meanpool_bf16(x, self.features)
 
     @torch.no_grad()
     def trunk(self, clips: torch.Tensor) -> torch.Tensor:
         """(N, 3, T, H, W) fp32 -> pooled (N, 512) fp32 (VideoResNet.forward's first output)."""
-        first = self.stem[0]
-        n, _, t, h, w = clips.shape
-        pad_h, pad_w, hp, wp = first.input_border(h, w)
-        wo = (w + 2 * pad_w - first.kernel[2]) // first.stride[2] + 1
-        x = clip_to_bf16(clips, pad_h, pad_w, hp, wp)
-        x = first(x, wo=wo)
+        x, wo = self.stem[0].clip_input(clips)
+        x = self.stem[0](x, wo=wo)
         for op in self.stem[1:]:
             x = op(x)
-        for conv1, conv2, down in self.blocks:
-            residual = x
-            if down is not None:
-                for op in down:
-                    residual = op(residual)
-            y = x
-            for op in conv1:
-                y = op(y)
-            for op in conv2[:-1]:
-                y = op(y)
-            x = conv2[-1](y, residual=residual)
-        return self._pool(x)
+        return _meanpool(self._fmt, run_blocks(x, self.blocks, _call_op), self.features)
 
     @torch.no_grad()
     def __call__(self, x: torch.Tensor):
@@ -342,10 +340,7 @@ class Fp8Engine(Bf16Engine):
     (``zsv_clip_to_bf16``, the folded clip form) and writes e4m3; the mean pool reads e4m3 and writes the fp32 (N, 512) feature;
     the head and the normalisation stay fp32.  A clip's embedding does not depend on the other clips of its batch."""
 
-    _name, _op = "Fp8Engine", _ConvOpFp8
-
-    def _pool(self, x: torch.Tensor) -> torch.Tensor:
-        return meanpool_fp8(x, self.features)
+    _fmt = E4M3
 
 
 class Bf16EngineC3D:
@@ -354,47 +349,22 @@ class Bf16EngineC3D:
     shift), the pools are ``zsv_maxpool3d_bf16``; fc6 (+ ReLU), the clip mean, the regressor and the normalisation stay fp32
     (dropout is the identity in eval mode).  Same contract as the module: ``(bs, nc, 3, T, H, W) fp32 -> (bs, 300)``."""
 
-    LAYERS = (("conv1", "pool1"), ("conv2", "pool2"), ("conv3a", None), ("conv3b", "pool3"), ("conv4a", None), ("conv4b", "pool4"),
-              ("conv5a", None), ("conv5b", "pool5"))
-
     def __init__(self, model: nn.Module):
-        from . import network
-        model = getattr(model, "module", model)
-        if not isinstance(model, network.C3D):
-            raise RuntimeError("Bf16EngineC3D supports network.C3D")
-        if next(model.parameters()).device.type != "cuda":
-            raise RuntimeError("Bf16EngineC3D: the model must live on the MI355X HIP device (there is no CPU fallback)")
-        self.model = model
-        self.ops = []
-        for conv_name, pool_name in self.LAYERS:
-            op = _ConvOp(getattr(model, conv_name), None, True)           # network.py:147-162: relu(conv(x)), bias in the epilogue
-            pool = getattr(model, pool_name) if pool_name else None
-            if pool is not None:
-                k, st, pd = pool.kernel_size, pool.stride, pool.padding
-                k = (k,) * 3 if isinstance(k, int) else tuple(k)
-                st = k if st is None else ((st,) * 3 if isinstance(st, int) else tuple(st))
-                pd = (pd,) * 3 if isinstance(pd, int) else tuple(pd)
-                if st != k:
-                    raise RuntimeError("Bf16EngineC3D: max-pools with stride != kernel are not used by the reference")
-                pool = (k, pd)
-            self.ops.append((op, pool))
-        if not self.ops[0][0].folded:
-            raise RuntimeError("Bf16EngineC3D: conv1 must take the clip (<= 4 channels)")
+        self.model = _device_model(model, "Bf16EngineC3D", c3d=True)
+        # network.py:147-162: relu(conv(x)), bias in the epilogue
+        self.ops = [(_ConvOp(conv, None, True), pool) for conv, pool in c3d_layers(self.model, "Bf16EngineC3D")]
 
     @torch.no_grad()
     def features(self, clips: torch.Tensor) -> torch.Tensor:
         """(N, 3, T, H, W) fp32 -> (N, 8192) fp32 in the (C, T, H, W) order of ``view(-1, 8192)`` (network.py:165)."""
-        first = self.ops[0][0]
-        n, _, t, h, w = clips.shape
-        pad_h, pad_w, hp, wp = first.input_border(h, w)
-        wo = (w + 2 * pad_w - first.kernel[2]) // first.stride[2] + 1
-        x = clip_to_bf16(clips, pad_h, pad_w, hp, wp)
-        for i, (op, pool) in enumerate(self.ops):
-            x = op(x, wo=wo) if i == 0 else op(x)
+        x, wo = self.ops[0][0].clip_input(clips)
+        for op, pool in self.ops:
+            x = op(x, wo=wo)
+            wo = None
             if pool is not None:
                 x = maxpool3d_bf16(x, op.cout, pool[0], pool[1])
         c = self.ops[-1][0].cout
-        return x[..., :c].permute(0, 4, 1, 2, 3).reshape(n, -1).float()
+        return x[..., :c].permute(0, 4, 1, 2, 3).reshape(clips.shape[0], -1).float()
 
     @torch.no_grad()
     def __call__(self, x: torch.Tensor):
@@ -441,25 +411,8 @@ class Fp32Engine:
     same contract and structure as ``Bf16Engine``, fp32 NCDHW activations, no BatchNorm kernels."""
 
     def __init__(self, model: nn.Module):
-        from . import network, resnet
-        model = getattr(model, "module", model)
-        if not isinstance(model, network.Model) or not isinstance(model.model, resnet.VideoResNet):
-            raise RuntimeError("Fp32Engine supports network.Model over a resnet.VideoResNet trunk")
-        if next(model.parameters()).device.type != "cuda":
-            raise RuntimeError("Fp32Engine: the model must live on the MI355X HIP device (there is no CPU fallback)")
-        self.model = model
-        chain = lambda mods: [_ConvOpF32(o._conv, o._bn, o.relu) for o in _conv_bn_relu_chain(mods, keep_modules=True)]
-        trunk = model.model
-        self.stem = chain(list(trunk.stem))
-        self.blocks = []
-        for layer in (trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4):
-            for block in layer:
-                if not isinstance(block, resnet.BasicBlock):
-                    raise RuntimeError("Fp32Engine: only BasicBlock trunks (the reference's *_18 models) are supported")
-                conv1, conv2 = chain(list(block.conv1)), chain(list(block.conv2))
-                conv2[-1].relu = True                   # out += residual; relu (resnet.py:110-111)
-                down = chain(list(block.downsample)) if block.downsample is not None else None
-                self.blocks.append((conv1, conv2, down))
+        self.model = _device_model(model, "Fp32Engine")
+        self.stem, self.blocks = video_resnet_ops(self.model.model, _ConvOpF32, "Fp32Engine")
 
     @torch.no_grad()
     def trunk(self, clips: torch.Tensor) -> torch.Tensor:
@@ -467,18 +420,7 @@ class Fp32Engine:
         x = clips.contiguous()
         for op in self.stem:
             x = op(x)
-        for conv1, conv2, down in self.blocks:
-            residual = x
-            if down is not None:
-                for op in down:
-                    residual = op(residual)
-            y = x
-            for op in conv1:
-                y = op(y)
-            for op in conv2[:-1]:
-                y = op(y)
-            x = conv2[-1](y, residual=residual)
-        return ops.mean_pool(x)
+        return ops.mean_pool(run_blocks(x, self.blocks, _call_op))
 
     @torch.no_grad()
     def __call__(self, x: torch.Tensor):

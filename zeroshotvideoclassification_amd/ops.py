@@ -977,10 +977,7 @@ def bn_module_deferred(x, bn: torch.nn.Module, stats=None):
     if bn.momentum is None:
         raise RuntimeError("deferred BatchNorm: training mode needs a momentum (momentum=None is not supported)")
     if bn.track_running_stats and bn.num_batches_tracked is not None:
-        if _NBT_PENDING is not None:
-            _NBT_PENDING.append(bn.num_batches_tracked)
-        else:
-            bn.num_batches_tracked.add_(1)
+        count_batch(bn)
     rm = bn.running_mean if bn.track_running_stats else None
     rv = bn.running_var if bn.track_running_stats else None
     return _BatchNormDeferred.apply(x, bn.weight, bn.bias, rm, rv, float(bn.momentum), float(bn.eps), stats)
@@ -992,27 +989,31 @@ def conv3d_pre(x, coef, weight, stride=1, padding=0, want_stats=False):
     return (y, stats) if want_stats else y
 
 
-_NBT_PENDING = None      # list of num_batches_tracked buffers to increment when the enclosing forward ends
-
-
 class batched_bn_counters:
     """Within this context the ``num_batches_tracked += 1`` of every training-mode BatchNorm
-    (37 one-element kernels in R(2+1)D-18) is deferred and applied as one ``_foreach_add_`` on exit."""
+    (37 one-element kernels in R(2+1)D-18) is deferred and applied as one ``_foreach_add_`` on exit, in this thread (the list
+    lives on ``_call_state``) and before the context ends, so a graph captured around it holds the increment.  A nested context
+    collects and applies its own."""
 
     def __enter__(self):
-        global _NBT_PENDING
-        self.outer = _NBT_PENDING
-        if self.outer is None:
-            _NBT_PENDING = []
+        self.outer = getattr(_call_state, "nbt_pending", None)
+        _call_state.nbt_pending = []
         return self
 
     def __exit__(self, *exc):
-        global _NBT_PENDING
-        if self.outer is None:
-            pending, _NBT_PENDING = _NBT_PENDING, None
-            if pending:
-                torch._foreach_add_(pending, 1)
+        pending, _call_state.nbt_pending = _call_state.nbt_pending, self.outer
+        if pending:
+            torch._foreach_add_(pending, 1)
         return False
+
+
+def count_batch(bn: torch.nn.Module) -> None:
+    """``bn.num_batches_tracked += 1``: now, or with the others when a ``batched_bn_counters`` context ends."""
+    pending = getattr(_call_state, "nbt_pending", None)
+    if pending is not None:
+        pending.append(bn.num_batches_tracked)
+    else:
+        bn.num_batches_tracked.add_(1)
 
 
 def bn_module_act(x, bn: torch.nn.Module, residual=None, relu=False, stats=None, skip_link=None):
@@ -1023,10 +1024,7 @@ def bn_module_act(x, bn: torch.nn.Module, residual=None, relu=False, stats=None,
         raise RuntimeError("cumulative-average BatchNorm (momentum=None) is not supported")
     use_batch_stats = bn.training or (bn.running_mean is None and bn.running_var is None)
     if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
-        if _NBT_PENDING is not None:
-            _NBT_PENDING.append(bn.num_batches_tracked)         # one fused increment per forward
-        else:
-            bn.num_batches_tracked.add_(1)
+        count_batch(bn)
     rm = bn.running_mean if (bn.track_running_stats or not use_batch_stats) else None
     rv = bn.running_var if (bn.track_running_stats or not use_batch_stats) else None
     return batch_norm_act(x, bn.weight, bn.bias, rm, rv, residual, use_batch_stats, bn.momentum, bn.eps, relu, stats,
