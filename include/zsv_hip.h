@@ -437,6 +437,51 @@ int zsv_adam_multi_scaled(const zsv_adam_tensor* table_device, int32_t count, in
 int zsv_scaler_update(zsv_scaler_state* state_device, float growth_factor, float backoff_factor,
                       int32_t growth_interval, void* stream);
 
+/* ---- weight decay and global-norm gradient clipping for the multi-tensor Adam step ---------------------------------
+ * torch.optim.Adam(weight_decay=) / torch.optim.AdamW, torch.nn.utils.clip_grad_norm_ (norm_type 2) and
+ * GradScaler.unscale_ over the same descriptor tables as zsv_adam_multi.  A clipped step is three launches:
+ *   zsv_grad_norm_multi     one pass over the gradients: sum of squares per 4096-element chunk (+ the non-finite check)
+ *   zsv_grad_norm_finalize  fixed-order sum of the partials in double -> {total_norm, clip_coef} in device memory
+ *   zsv_adamw_multi[_scaled] the update, reading clip_coef on the device (the gradients in memory are not rewritten)
+ * No floating-point atomics: equal gradients give equal norm bits and equal parameter bits on every run. */
+typedef struct zsv_clip_record {
+    float total_norm;   /* 2-norm of all (unscaled) gradients, before clipping */
+    float clip_coef;    /* min(1, max_norm / (total_norm + 1e-6)) */
+} zsv_clip_record;
+/* Bytes of the partials buffer for `total_chunks` chunks (one float per chunk), summed over every table that
+ * contributes to one norm. */
+size_t zsv_grad_norm_workspace_bytes(int64_t total_chunks);
+/* partials[chunk_offset + c] = sum of g^2 over chunk c of the table, c in [0, total_chunks).  Several parameter groups are
+ * several tables: launch once per table with chunk_offset = the chunks of the tables before it.  With a non-NULL
+ * `state_device`, found_inf is set exactly as zsv_grad_check_multi sets it, so one read of the gradients serves both. */
+int zsv_grad_norm_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, int64_t chunk_offset,
+                        void* partials_device, size_t partials_bytes, zsv_scaler_state* state_device, void* stream);
+/* total_norm = sqrt(sum of partials[0 .. total_chunks)) (summed in double, fixed order), times (float)(1 / (double)scale)
+ * when `state_device` is non-NULL (the gradients in memory are scaled); clip_coef = min(1, max_norm / (total_norm + 1e-6)).
+ * max_norm > 0; +inf gives the norm alone (clip_coef 1). */
+int zsv_grad_norm_finalize(const void* partials_device, int64_t total_chunks, float max_norm,
+                           const zsv_scaler_state* state_device, zsv_clip_record* record_device, void* stream);
+/* GradScaler.unscale_: g *= (float)(1 / (double)scale) in place (the table's `g` is written), found_inf |= any
+ * non-finite gradient. */
+int zsv_grad_unscale_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks,
+                           zsv_scaler_state* state_device, void* stream);
+/* zsv_adam_multi with weight decay and clipping.  Per element, in this order:
+ *   g = g_mem * clip_coef                       (clip_device may be NULL: 1)
+ *   L2 (decoupled == 0):   g += weight_decay * p                                  torch.optim.Adam(weight_decay=)
+ *   exp_avg, exp_avg_sq as in zsv_adam_multi
+ *   decoupled != 0:        p *= (float)(1 - lr * weight_decay)  (formed in double) torch.optim.AdamW
+ *   p -= step_size * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^step) + eps) */
+int zsv_adamw_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr, float beta1,
+                    float beta2, float eps, double weight_decay, int32_t decoupled, const zsv_clip_record* clip_device,
+                    int32_t step, void* stream);
+/* The same under the loss scaler: skipped entirely (decay included) when found_inf is set; g = g_mem * (1 / scale) *
+ * clip_coef, or g_mem * clip_coef when `grads_unscaled` != 0 (zsv_grad_unscale_multi has already run on this table);
+ * step number = steps_done + 1 read on the device. */
+int zsv_adamw_multi_scaled(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr, float beta1,
+                           float beta2, float eps, double weight_decay, int32_t decoupled,
+                           const zsv_clip_record* clip_device, const zsv_scaler_state* state_device,
+                           int32_t grads_unscaled, void* stream);
+
 /* ---- weight panels packed ahead of the call ---------------------------------------------------------------------------
  * Every forward / dgrad entry point above first re-lays its weights out (a "panel": the direct kernel's [block][tap][16][m]
  * image, the Winograd kernels' transformed weights, the stride-2 dgrad's tap-major image) in a small launch of its own: 76

@@ -1,0 +1,86 @@
+"""Host side of weight decay / gradient clipping in ``optim.FusedAdam``: constructor validation, the C ABI surface and the
+state-dict compatibility.  Nothing here touches a device."""
+import inspect
+import os
+import re
+
+import pytest
+import torch
+
+from zeroshotvideoclassification_amd import _lib, optim
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("zsv_grad_norm_workspace_bytes", "zsv_grad_norm_multi", "zsv_grad_norm_finalize", "zsv_grad_unscale_multi",
+               "zsv_adamw_multi", "zsv_adamw_multi_scaled")
+
+
+def _ps():
+    return [torch.nn.Parameter(torch.ones(3)), torch.nn.Parameter(torch.ones(2, 2))]
+
+
+@pytest.mark.parametrize("kw", [
+    {"weight_decay": -0.1}, {"weight_decay": float("nan")}, {"weight_decay": float("inf")},
+    {"max_grad_norm": 0.0}, {"max_grad_norm": -1.0}, {"max_grad_norm": float("nan")}, {"max_grad_norm": float("inf")},
+])
+def test_constructor_rejects_bad_values_before_touching_a_device(kw):
+    with pytest.raises(ValueError):
+        optim.FusedAdam(_ps(), lr=1e-3, **kw)
+
+
+def test_constructor_rejects_a_bad_group_value():
+    a, b = _ps()
+    with pytest.raises(ValueError):
+        optim.FusedAdam([{"params": [a]}, {"params": [b], "weight_decay": -1.0}], lr=1e-3)
+
+
+def test_defaults_and_group_options():
+    sig = inspect.signature(optim.FusedAdam.__init__)
+    assert list(sig.parameters)[1:] == ["params", "lr", "betas", "eps", "weight_decay", "decoupled_weight_decay", "max_grad_norm",
+                                        "grad_buckets"]
+    assert sig.parameters["weight_decay"].default == 0.0 and sig.parameters["decoupled_weight_decay"].default is False
+    assert sig.parameters["max_grad_norm"].default is None
+    a, b = _ps()
+    opt = optim.FusedAdam([{"params": [a], "weight_decay": 0.1}, {"params": [b], "decoupled_weight_decay": False}], lr=1e-3,
+                          decoupled_weight_decay=True, max_grad_norm=2)
+    assert [g["weight_decay"] for g in opt.param_groups] == [0.1, 0.0]
+    assert [g["decoupled_weight_decay"] for g in opt.param_groups] == [True, False]
+    assert opt.max_grad_norm == 2.0
+    with pytest.raises(RuntimeError, match="max_grad_norm"):
+        opt.grad_norm                                          # nothing stepped yet
+    assert hasattr(optim.LossScaler, "unscale_")
+
+
+def test_new_symbols_are_declared_and_have_prototypes():
+    header = open(os.path.join(ROOT, "include", "zsv_hip.h")).read()
+    declared = set(re.findall(r"\b(zsv_[a-z0-9_]+)\s*\(", header))
+    for sym in NEW_SYMBOLS:
+        assert sym in declared, sym
+        assert sym in _lib.SIGNATURES, sym
+    assert "typedef struct zsv_clip_record" in header
+    # the entry points that tests call raw keep their prototypes
+    assert _lib.SIGNATURES["zsv_adam_multi"][1] == [_lib._P, _lib.c_int32, _lib.c_int64] + [_lib.c_float] * 4 + [_lib.c_int32, _lib._P]
+    assert len(_lib.SIGNATURES["zsv_adam_multi_scaled"][1]) == 9 and len(_lib.SIGNATURES["zsv_grad_check_multi"][1]) == 5
+    if os.path.isfile(_lib.LIB_PATH):
+        lib = _lib.load()
+        assert lib.zsv_grad_norm_workspace_bytes(0) == 0 and lib.zsv_grad_norm_workspace_bytes(7) >= 28
+        # argument checks need no device: NULL tables and bad arguments are refused before any launch
+        assert lib.zsv_grad_norm_multi(None, 1, 1, 0, None, 0, None, None) != 0
+        assert lib.zsv_grad_norm_finalize(None, 1, 1.0, None, None, None) != 0
+        assert lib.zsv_adamw_multi(None, 1, 1, 1e-3, 0.9, 0.999, 1e-8, 0.1, 1, None, 1, None) != 0
+
+
+def test_state_dict_round_trip_and_old_state_dicts():
+    opt = optim.FusedAdam(_ps(), lr=1e-3, weight_decay=0.02, decoupled_weight_decay=True, max_grad_norm=1.0)
+    sd = opt.state_dict()
+    assert sd["param_groups"][0]["weight_decay"] == 0.02 and sd["param_groups"][0]["decoupled_weight_decay"] is True
+    other = optim.FusedAdam(_ps(), lr=1e-3)
+    other.load_state_dict(sd)
+    assert other.param_groups[0]["weight_decay"] == 0.02 and other.param_groups[0]["decoupled_weight_decay"] is True
+    # a state dict written before the options existed: the missing keys take the defaults
+    old = optim.FusedAdam(_ps(), lr=1e-3).state_dict()
+    for g in old["param_groups"]:
+        del g["weight_decay"], g["decoupled_weight_decay"]
+    fresh = optim.FusedAdam(_ps(), lr=5e-4, weight_decay=0.3, decoupled_weight_decay=True)
+    fresh.load_state_dict(old)
+    assert fresh.param_groups[0]["lr"] == 1e-3
+    assert fresh.param_groups[0]["weight_decay"] == 0.0 and fresh.param_groups[0]["decoupled_weight_decay"] is False

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZSV_LIB_PATH") or os.path.join(_HERE, "libzsv_hip.so")   # (override: A/B of two builds)
@@ -116,6 +116,13 @@ SIGNATURES = {
     "zsv_grad_check_multi": (c_int, [_P, c_int32, c_int64, _P, _P]),
     "zsv_adam_multi_scaled": (c_int, [_P, c_int32, c_int64, c_float, c_float, c_float, c_float, _P, _P]),
     "zsv_scaler_update": (c_int, [_P, c_float, c_float, c_int32, _P]),
+    "zsv_grad_norm_workspace_bytes": (c_size_t, [c_int64]),
+    "zsv_grad_norm_multi": (c_int, [_P, c_int32, c_int64, c_int64, _P, c_size_t, _P, _P]),
+    "zsv_grad_norm_finalize": (c_int, [_P, c_int64, c_float, _P, _P, _P]),
+    "zsv_grad_unscale_multi": (c_int, [_P, c_int32, c_int64, _P, _P]),
+    "zsv_adamw_multi": (c_int, [_P, c_int32, c_int64, c_double, c_float, c_float, c_float, c_double, c_int32, _P, c_int32, _P]),
+    "zsv_adamw_multi_scaled": (c_int, [_P, c_int32, c_int64, c_double, c_float, c_float, c_float, c_double, c_int32, _P, _P,
+                                       c_int32, _P]),
     "zsv_adam_step": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, _P]),
     "zsv_conv3d_panel_query": (c_int, [POINTER(ConvDesc), c_int32, c_int32, POINTER(c_size_t)]),
     "zsv_conv3d_panel_job": (c_int, [POINTER(ConvDesc), c_int32, c_int32, _P, _P, c_size_t, _P]),

@@ -1,0 +1,210 @@
+// optim.hip -- weight decay and global-norm gradient clipping for the multi-tensor Adam step (include/zsv_hip.h).
+//
+//   torch                                          here
+//   clip_grad_norm_(params, max_norm)              grad_norm_multi (sum of squares per 4096-element chunk, + the non-finite
+//                                                  check of the loss scaler) and grad_norm_finalize (fixed-order sum in double,
+//                                                  1/scale, {total_norm, clip_coef}); the coefficient is applied on the
+//                                                  gradient's way into the update, the gradients in memory are not rewritten
+//   Adam(weight_decay=) / AdamW                    adamw_multi / adamw_multi_scaled
+//   GradScaler.unscale_                            grad_unscale_multi
+//
+// All of them walk the zsv_adam_tensor table of zsv_adam_multi (elementwise_pool.hip) the same way: one workgroup of 256
+// threads per chunk, a binary search over first_chunk.  No floating-point atomics: every sum has a fixed order, so the same
+// gradients give the same norm bits and the same parameter bits on every run.
+#include "zsv_common.h"
+#include "zsv_hip.h"
+
+#include <math.h>
+
+namespace zsv {
+constexpr int OPT_CHUNK = 4096;                       // = ADAM_CHUNK of elementwise_pool.hip
+
+// last tensor whose first_chunk <= chunk
+__device__ __forceinline__ zsv_adam_tensor find_tensor(const zsv_adam_tensor* __restrict__ table, int count, long chunk) {
+    int lo = 0, hi = count - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
+    }
+    return table[lo];
+}
+
+__device__ __forceinline__ bool non_finite(float g) { return !(fabsf(g) <= 3.402823466e38f); }     // inf or NaN
+
+// partials[blockIdx.x] = sum of g^2 over the chunk: <= 16 serial adds per lane, then a fixed 8-level tree over 256 lanes.
+__global__ __launch_bounds__(256) void grad_norm_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count,
+                                                              float* __restrict__ partials, zsv_scaler_state* __restrict__ st) {
+    __shared__ float red[4];
+    const long chunk = blockIdx.x;
+    const zsv_adam_tensor t = find_tensor(table, count, chunk);
+    const long base = (chunk - t.first_chunk) * OPT_CHUNK;
+    const long end = min(t.n, base + OPT_CHUNK);
+    float s = 0.f;
+    bool bad = false;
+    for (long i = base + threadIdx.x; i < end; i += 256) {
+        const float g = t.g[i];
+        bad |= non_finite(g);
+        s += g * g;
+    }
+    if (st != nullptr && __any(bad) && (threadIdx.x & 63) == 0) st->found_inf = 1;   // benign race: every writer stores 1
+    const float total = block_sum_256<float>(s, red);
+    if (threadIdx.x == 0) partials[chunk] = total;
+}
+
+// One workgroup: lane k sums partials[k], partials[k + 256], ... in double, then the same fixed tree.
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const float* __restrict__ partials, long total_chunks,
+                                                                 float max_norm, const zsv_scaler_state* __restrict__ st,
+                                                                 zsv_clip_record* __restrict__ record) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (long i = threadIdx.x; i < total_chunks; i += 256) s += (double)partials[i];
+    const double sum = block_sum_256<double>(s, red);
+    if (threadIdx.x != 0) return;
+    float norm = (float)sqrt(sum);
+    if (st != nullptr) norm *= (float)(1.0 / (double)st->scale);      // the gradients in memory are scaled
+    const float coef = max_norm / (norm + 1e-6f);                     // clip_grad_norm_: max_norm / (total_norm + 1e-6),
+    record->total_norm = norm;                                        // clamped to at most 1 (a NaN stays a NaN)
+    record->clip_coef = coef > 1.f ? 1.f : coef;
+}
+
+__global__ __launch_bounds__(256) void grad_unscale_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count,
+                                                                 zsv_scaler_state* __restrict__ st) {
+    const float inv_scale = (float)(1.0 / (double)st->scale);
+    const long chunk = blockIdx.x;
+    const zsv_adam_tensor t = find_tensor(table, count, chunk);
+    const long base = (chunk - t.first_chunk) * OPT_CHUNK;
+    const long end = min(t.n, base + OPT_CHUNK);
+    float* g = const_cast<float*>(t.g);
+    bool bad = false;
+    for (long i = base + threadIdx.x; i < end; i += 256) {
+        const float gi = g[i];
+        bad |= non_finite(gi);
+        g[i] = gi * inv_scale;
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) st->found_inf = 1;
+}
+
+struct AdamwArgs {
+    float b1, b2, eps;
+    float wd_l2;            // L2 mode: g += wd_l2 * p                (0 otherwise)
+    float decay_factor;     // decoupled mode: p *= decay_factor      (1 otherwise)
+    int decoupled;
+    const zsv_clip_record* clip;
+};
+
+// g = g_mem * inv_scale * clip_coef; L2: g += wd * p; moments; decoupled: p *= 1 - lr * wd; Adam update.
+__device__ __forceinline__ void adamw_chunk(const zsv_adam_tensor* __restrict__ table, int count, const AdamwArgs& a,
+                                            float inv_scale, float step_size, float inv_sqrt_bc2) {
+    const float clip = a.clip != nullptr ? a.clip->clip_coef : 1.f;
+    const long chunk = blockIdx.x;
+    const zsv_adam_tensor t = find_tensor(table, count, chunk);
+    const long base = (chunk - t.first_chunk) * OPT_CHUNK;
+    const long end = min(t.n, base + OPT_CHUNK);
+    for (long i = base + threadIdx.x; i < end; i += 256) {
+        float pi = t.p[i];
+        float gi = t.g[i] * inv_scale;                 // two separate fp32 products, as unscale_ and clip_grad_norm_ store them
+        gi = gi * clip;
+        if (!a.decoupled) gi = gi + a.wd_l2 * pi;      // grad.add(param, alpha=weight_decay)
+        const float mi = a.b1 * t.exp_avg[i] + (1.f - a.b1) * gi;
+        const float vi = a.b2 * t.exp_avg_sq[i] + (1.f - a.b2) * gi * gi;
+        t.exp_avg[i] = mi;
+        t.exp_avg_sq[i] = vi;
+        if (a.decoupled) pi *= a.decay_factor;         // param.mul_(1 - lr * weight_decay)
+        t.p[i] = pi - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + a.eps));
+    }
+}
+
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count, AdamwArgs a,
+                                                          float step_size, float inv_sqrt_bc2) {
+    adamw_chunk(table, count, a, 1.f, step_size, inv_sqrt_bc2);
+}
+
+__global__ __launch_bounds__(256) void adamw_multi_scaled_kernel(const zsv_adam_tensor* __restrict__ table, int count, AdamwArgs a,
+                                                                 double lr, const zsv_scaler_state* __restrict__ st,
+                                                                 int grads_unscaled) {
+    if (st->found_inf) return;                                     // scaler.step skips optimizer.step, weight decay included
+    const float inv_scale = grads_unscaled ? 1.f : (float)(1.0 / (double)st->scale);
+    const int step = st->steps_done + 1;
+    const float step_size = (float)(lr / (1.0 - pow((double)a.b1, (double)step)));
+    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.b2, (double)step)));
+    adamw_chunk(table, count, a, inv_scale, step_size, inv_sqrt_bc2);
+}
+
+static inline bool bad_table(int32_t count, int64_t total_chunks) {
+    return count <= 0 || total_chunks <= 0 || total_chunks > 0x7fffffffL;
+}
+
+static inline bool make_args(AdamwArgs& a, double lr, float beta1, float beta2, float eps, double weight_decay, int32_t decoupled,
+                             const zsv_clip_record* clip) {
+    if (!(lr >= 0.0) || !(weight_decay >= 0.0) || !isfinite(lr) || !isfinite(weight_decay)) return false;
+    a.b1 = beta1;
+    a.b2 = beta2;
+    a.eps = eps;
+    a.decoupled = decoupled != 0 && weight_decay != 0.0;
+    a.wd_l2 = a.decoupled ? 0.f : (float)weight_decay;
+    a.decay_factor = a.decoupled ? (float)(1.0 - lr * weight_decay) : 1.f;
+    a.clip = clip;
+    return true;
+}
+}  // namespace zsv
+
+using namespace zsv;
+
+extern "C" size_t zsv_grad_norm_workspace_bytes(int64_t total_chunks) {
+    return total_chunks > 0 ? (size_t)total_chunks * sizeof(float) : 0;
+}
+
+extern "C" int zsv_grad_norm_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, int64_t chunk_offset,
+                                   void* partials_device, size_t partials_bytes, zsv_scaler_state* state_device, void* stream) {
+    if (!table_device || !partials_device) return ZSV_E_NULL;
+    if (bad_table(count, total_chunks) || chunk_offset < 0) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
+    if (partials_bytes < zsv_grad_norm_workspace_bytes(chunk_offset + total_chunks)) return ZSV_E_WORKSPACE;
+    hipLaunchKernelGGL(grad_norm_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device, count,
+                       (float*)partials_device + chunk_offset, state_device);
+    return launch_status();
+}
+
+extern "C" int zsv_grad_norm_finalize(const void* partials_device, int64_t total_chunks, float max_norm,
+                                      const zsv_scaler_state* state_device, zsv_clip_record* record_device, void* stream) {
+    if (!partials_device || !record_device) return ZSV_E_NULL;
+    if (total_chunks <= 0 || total_chunks > 0x7fffffffL || !(max_norm > 0.f)) return ZSV_E_BAD_SHAPE;
+    hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partials_device,
+                       (long)total_chunks, max_norm, state_device, record_device);
+    return launch_status();
+}
+
+extern "C" int zsv_grad_unscale_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks,
+                                      zsv_scaler_state* state_device, void* stream) {
+    if (!table_device || !state_device) return ZSV_E_NULL;
+    if (bad_table(count, total_chunks)) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
+    hipLaunchKernelGGL(grad_unscale_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
+                       count, state_device);
+    return launch_status();
+}
+
+extern "C" int zsv_adamw_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr, float beta1,
+                               float beta2, float eps, double weight_decay, int32_t decoupled,
+                               const zsv_clip_record* clip_device, int32_t step, void* stream) {
+    if (!table_device) return ZSV_E_NULL;
+    if (bad_table(count, total_chunks) || step <= 0) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
+    AdamwArgs a;
+    if (!make_args(a, lr, beta1, beta2, eps, weight_decay, decoupled, clip_device)) return ZSV_E_BAD_SHAPE;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device, count, a,
+                       (float)(lr / bc1), (float)(1.0 / sqrt(bc2)));
+    return launch_status();
+}
+
+extern "C" int zsv_adamw_multi_scaled(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr,
+                                      float beta1, float beta2, float eps, double weight_decay, int32_t decoupled,
+                                      const zsv_clip_record* clip_device, const zsv_scaler_state* state_device,
+                                      int32_t grads_unscaled, void* stream) {
+    if (!table_device || !state_device) return ZSV_E_NULL;
+    if (bad_table(count, total_chunks)) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
+    AdamwArgs a;
+    if (!make_args(a, lr, beta1, beta2, eps, weight_decay, decoupled, clip_device)) return ZSV_E_BAD_SHAPE;
+    hipLaunchKernelGGL(adamw_multi_scaled_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
+                       count, a, lr, state_device, grads_unscaled);
+    return launch_status();
+}

@@ -22,9 +22,26 @@ like torch does.
 actually taken) in device memory: the non-finite check (``zsv_grad_check_multi``), the skip-on-inf Adam step
 with the 1/scale folded into the gradient read (``zsv_adam_multi_scaled``) and the scale update
 (``zsv_scaler_update``) are three launches and no host synchronisation.
+
+Fine-tuning options (csrc/optim.hip), all off by default -- with ``weight_decay == 0`` in every group and
+``max_grad_norm is None`` the step calls ``zsv_adam_multi`` / ``zsv_adam_multi_scaled`` exactly as before:
+
+* ``weight_decay`` / ``decoupled_weight_decay`` per parameter group: ``torch.optim.Adam(weight_decay=)`` (L2, the decay joins
+  the gradient) or ``torch.optim.AdamW`` (decoupled, ``p *= 1 - lr * wd``), inside the same single launch
+  (``zsv_adamw_multi`` / ``zsv_adamw_multi_scaled``);
+* ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_`` over every parameter of every group.  One extra read of the
+  gradients (``zsv_grad_norm_multi``: sum of squares per chunk, which also serves as the scaler's non-finite check), one
+  small launch that sums the partials in a fixed order in double and leaves ``{total_norm, clip_coef}`` on the device
+  (``zsv_grad_norm_finalize``), and the update multiplies each gradient by ``clip_coef`` as it reads it.  ``.grad`` is NOT
+  rewritten (torch's ``clip_grad_norm_`` rewrites it).  ``FusedAdam.grad_norm`` is the device-resident total norm;
+* ``LossScaler.unscale_(optimizer)``: ``GradScaler.unscale_`` (``zsv_grad_unscale_multi``) for loops that keep torch's literal
+  ``unscale_`` + ``clip_grad_norm_`` + ``step`` recipe.
+
+No floating-point atomics: the same gradients give the same norm bits and the same parameter bits on every run.
 """
 from __future__ import annotations
 
+import math
 import struct
 from ctypes import c_void_p
 from typing import Optional
@@ -54,6 +71,7 @@ class LossScaler:
         host.view(torch.float32)[0] = float(init_scale)
         self._state = host.to(self.device)
         self._scale = self._state.view(torch.float32)[0:1]
+        self._unscaled = set()                            # id() of the optimizers unscale_() has run on since update()
 
     @property
     def state_ptr(self) -> int:
@@ -69,8 +87,22 @@ class LossScaler:
             raise RuntimeError("LossScaler.step drives optim.FusedAdam (the check, unscale and skip run inside its kernels)")
         optimizer.step(scaler=self)
 
+    def unscale_(self, optimizer) -> None:
+        """``GradScaler.unscale_(optimizer)``: the gradients of ``optimizer`` are multiplied by 1/scale in place and
+        ``found_inf`` is set if any is non-finite (``zsv_grad_unscale_multi``, no host synchronisation).  The following
+        ``step(optimizer)`` does not unscale again; a second call before ``update()`` raises, as torch's does.  For
+        ``scaler.unscale_(opt); torch.nn.utils.clip_grad_norm_(...); scaler.step(opt)``; ``FusedAdam(max_grad_norm=)``
+        is the fused route, which needs no ``unscale_``."""
+        if not isinstance(optimizer, FusedAdam):
+            raise RuntimeError("LossScaler.unscale_ drives optim.FusedAdam")
+        if id(optimizer) in self._unscaled:
+            raise RuntimeError("unscale_() has already been called on this optimizer since the last update().")
+        optimizer._unscale(self)
+        self._unscaled.add(id(optimizer))
+
     def update(self) -> None:
         """``scaler.update()`` (main.py:203)."""
+        self._unscaled.clear()
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().zsv_scaler_update(self.state_ptr, self.growth_factor, self.backoff_factor,
                                                      self.growth_interval, _stream()), "zsv_scaler_update")
@@ -111,10 +143,35 @@ class LossScaler:
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_buckets=None):
+    """``torch.optim.Adam`` / ``torch.optim.AdamW`` in one launch per parameter group (module docstring).
+
+    ``weight_decay`` and ``decoupled_weight_decay`` are per parameter group, like ``lr``: ``decoupled_weight_decay=False``
+    is ``Adam(weight_decay=)`` (L2: ``g += wd * p``), ``True`` is ``AdamW`` (``p *= 1 - lr * wd``).  Parameters without a
+    gradient are skipped, decay included, as torch does; a step the ``LossScaler`` skips applies no decay either.
+
+    ``max_grad_norm`` belongs to the optimizer and spans all groups: the gradients are scaled by
+    ``min(1, max_grad_norm / (total_norm + 1e-6))`` -- ``clip_grad_norm_`` with ``norm_type=2`` over all parameters -- on
+    their way into the update.  ``.grad`` itself is not rewritten (torch's ``clip_grad_norm_`` rewrites it).  With
+    ``grad_buckets=`` the norm is that of the averaged gradients, identical on every rank."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False,
+                 max_grad_norm=None, grad_buckets=None):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1):
             raise ValueError("invalid Adam hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        self._check_decay(weight_decay)
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (math.isfinite(max_grad_norm) and max_grad_norm > 0):
+                raise ValueError(f"max_grad_norm must be a finite positive number or None, not {max_grad_norm}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      decoupled_weight_decay=bool(decoupled_weight_decay)))
+        for group in self.param_groups:
+            self._check_decay(group["weight_decay"])
+            if not (math.isfinite(group["lr"]) and group["lr"] >= 0):
+                raise ValueError(f"invalid learning rate {group['lr']}")
+        self.max_grad_norm = max_grad_norm
+        self._clip = None                                 # zsv_clip_record {total_norm, clip_coef} on the device
+        self._partials = None                             # one float per gradient chunk (zsv_grad_norm_multi)
         self._ring = [[None, None] for _ in range(4)]     # (pinned staging buffer, copy-done event)
         self._next = 0
         self.grad_buckets = grad_buckets                  # ddp.GradientSync (or None)
@@ -122,6 +179,20 @@ class FusedAdam(torch.optim.Optimizer):
         self._host_steps = 0                              # steps taken without a scaler
         self._resumed = False                             # state came from load_state_dict (a scaler may then join late)
         self._scaler: Optional[LossScaler] = None
+
+    @staticmethod
+    def _check_decay(weight_decay):
+        if not (isinstance(weight_decay, (int, float)) and math.isfinite(weight_decay) and weight_decay >= 0):
+            raise ValueError(f"weight_decay must be a finite number >= 0, not {weight_decay}")
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """2-norm of all gradients of the last ``step()`` (unscaled, before clipping) as a 0-d device tensor; reading it
+        does not synchronise.  Valid after a step when ``max_grad_norm`` is set.  On a step the scaler skipped it holds
+        what the non-finite gradients gave (inf or NaN)."""
+        if self._clip is None:
+            raise RuntimeError("FusedAdam.grad_norm is available after step() of an optimizer built with max_grad_norm=")
+        return self._clip[0]
 
     # -- descriptor tables ------------------------------------------------------------------------
     def _ensure_state(self, p):
@@ -227,28 +298,15 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        if scaler is not None and self._scaler is None:
-            if self._host_steps:
-                if not self._resumed:
-                    raise RuntimeError("FusedAdam: a LossScaler must drive the optimizer from its first step "
-                                       "(the count of steps taken lives in the scaler's device state)")
-                # resumed from a checkpoint (load_state_dict): the scaler takes over the loaded step count unless its own
-                # loaded state already carries one
-                if scaler.state()["steps_done"] == 0:
-                    scaler._seed_steps_done(self._host_steps)
-                elif scaler.state()["steps_done"] != self._host_steps:
-                    raise RuntimeError("FusedAdam: the loaded optimizer and scaler states disagree on the steps taken")
-            self._scaler = scaler
-        if self._scaler is not None and scaler is not self._scaler:
-            raise RuntimeError("FusedAdam: this optimizer is driven by a LossScaler; step through scaler.step(optimizer)")
+        self._adopt(scaler)
         lib = _lib.load()
         launched = False
-        work = []
-        for group in self.param_groups:
-            built = self._static_table(group) or self._dynamic_table(group)
-            if built is not None:
-                work.append((group, built))
-        if scaler is not None:
+        work = self._tables()
+        unscaled = scaler is not None and id(self) in scaler._unscaled      # LossScaler.unscale_ has run on these gradients
+        if self.max_grad_norm is not None or unscaled or any(g["weight_decay"] != 0 for g in self.param_groups):
+            launched = self._step_decay_clip(lib, work, scaler, unscaled)
+            work = []
+        elif scaler is not None:
             # GradScaler.step checks EVERY gradient before the optimizer touches anything: an inf in the last group must
             # skip the first group's update too
             for _, (table, count, chunks, _keep) in work:
@@ -279,8 +337,100 @@ class FusedAdam(torch.optim.Optimizer):
             _lib.note_raw_write()                  # parameters updated through raw pointers
         return loss
 
+    def _adopt(self, scaler: Optional[LossScaler]) -> None:
+        if scaler is not None and self._scaler is None:
+            if self._host_steps:
+                if not self._resumed:
+                    raise RuntimeError("FusedAdam: a LossScaler must drive the optimizer from its first step "
+                                       "(the count of steps taken lives in the scaler's device state)")
+                # resumed from a checkpoint (load_state_dict): the scaler takes over the loaded step count unless its own
+                # loaded state already carries one
+                if scaler.state()["steps_done"] == 0:
+                    scaler._seed_steps_done(self._host_steps)
+                elif scaler.state()["steps_done"] != self._host_steps:
+                    raise RuntimeError("FusedAdam: the loaded optimizer and scaler states disagree on the steps taken")
+            self._scaler = scaler
+        if self._scaler is not None and scaler is not self._scaler:
+            raise RuntimeError("FusedAdam: this optimizer is driven by a LossScaler; step through scaler.step(optimizer)")
+
+    def _tables(self):
+        work = []
+        for group in self.param_groups:
+            built = self._static_table(group) or self._dynamic_table(group)
+            if built is not None:
+                work.append((group, built))
+        return work
+
+    def _unscale(self, scaler: LossScaler) -> None:
+        """``LossScaler.unscale_``: g *= 1/scale in place + the non-finite check, one launch per parameter group."""
+        self._adopt(scaler)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is not None and not p.grad.is_contiguous():
+                    raise RuntimeError("LossScaler.unscale_ rewrites the gradients in place and needs them contiguous")
+        lib = _lib.load()
+        for _, (table, count, chunks, keep) in self._tables():
+            with torch.cuda.device(table.device):
+                _lib.check(lib.zsv_grad_unscale_multi(table.data_ptr(), count, chunks, scaler.state_ptr, _stream()),
+                           "zsv_grad_unscale_multi")
+            table.record_stream(torch.cuda.current_stream())
+            del keep
+        _lib.note_raw_write()                      # gradients rewritten through raw pointers
+
+    def _step_decay_clip(self, lib, work, scaler: Optional[LossScaler], unscaled: bool) -> bool:
+        """The step with weight decay and / or clipping: [norm pass per group, finalize,] one update launch per group."""
+        if not work:
+            return False
+        state_ptr = scaler.state_ptr if scaler is not None else None
+        scaled_in_memory = scaler is not None and not unscaled
+        clip_ptr = None
+        if self.max_grad_norm is not None:
+            dev = work[0][1][0].device
+            total = sum(chunks for _, (_, _, chunks, _) in work)
+            nbytes = int(lib.zsv_grad_norm_workspace_bytes(total))
+            if self._clip is None or self._clip.device != dev:
+                self._clip = torch.zeros(2, dtype=torch.float32, device=dev)
+            if self._partials is None or self._partials.device != dev or self._partials.numel() * 4 < nbytes:
+                self._partials = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+            offset = 0
+            with torch.cuda.device(dev):
+                for _, (table, count, chunks, _keep) in work:
+                    # with a scaler this read of the gradients is the non-finite check as well (all groups before any update)
+                    _lib.check(lib.zsv_grad_norm_multi(table.data_ptr(), count, chunks, offset, self._partials.data_ptr(),
+                                                       self._partials.numel() * 4, state_ptr if scaled_in_memory else None,
+                                                       _stream()), "zsv_grad_norm_multi")
+                    offset += chunks
+                _lib.check(lib.zsv_grad_norm_finalize(self._partials.data_ptr(), total, self.max_grad_norm,
+                                                      state_ptr if scaled_in_memory else None, self._clip.data_ptr(),
+                                                      _stream()), "zsv_grad_norm_finalize")
+            clip_ptr = self._clip.data_ptr()
+        elif scaled_in_memory:
+            for _, (table, count, chunks, _keep) in work:
+                with torch.cuda.device(table.device):
+                    _lib.check(lib.zsv_grad_check_multi(table.data_ptr(), count, chunks, state_ptr, _stream()),
+                               "zsv_grad_check_multi")
+        for group, (table, count, chunks, keep) in work:
+            lr, (b1, b2), eps = float(group["lr"]), group["betas"], float(group["eps"])
+            wd, decoupled = float(group["weight_decay"]), int(bool(group["decoupled_weight_decay"]))
+            self._check_decay(wd)
+            with torch.cuda.device(table.device):
+                if scaler is not None:
+                    _lib.check(lib.zsv_adamw_multi_scaled(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps, wd,
+                                                          decoupled, clip_ptr, state_ptr, int(unscaled), _stream()),
+                               "zsv_adamw_multi_scaled")
+                else:
+                    _lib.check(lib.zsv_adamw_multi(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps, wd,
+                                                   decoupled, clip_ptr, self._host_steps + 1, _stream()), "zsv_adamw_multi")
+            table.record_stream(torch.cuda.current_stream())
+            del keep
+        return True
+
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
+        for group in self.param_groups:            # a state dict saved before these options existed: the defaults
+            group.setdefault("weight_decay", 0.0)
+            group.setdefault("decoupled_weight_decay", False)
+            self._check_decay(group["weight_decay"])
         steps = [int(st["step"].item()) for st in self.state.values() if "step" in st]
         if steps and min(steps) != max(steps):
             raise RuntimeError("FusedAdam: the loaded per-parameter step counts differ")

@@ -100,7 +100,9 @@ def train_step(model: torch.nn.Module, optimizer: torch.optim.Optimizer, criteri
     the update and halves the scale.  ``autocast=True`` runs forward and loss inside ``amp.autocast()`` -- main.py:172's
     ``with autocast():`` -- i.e. the VideoResNet trunks in bf16 (``amp``: bf16 activations and products, fp32 accumulation,
     statistics, parameters, gradients and loss); the default is the fp32 step of BASELINE configs 1-3, which is what the
-    reference's CPU path runs (autocast is a no-op there).  ``pacer`` (a ``StepPacer``) bounds the host's lead over the device."""
+    reference's CPU path runs (autocast is a no-op there).  ``pacer`` (a ``StepPacer``) bounds the host's lead over the device.
+    Weight decay and gradient clipping need no argument here: the optimizer carries them (``optim.FusedAdam(weight_decay=,
+    decoupled_weight_decay=, max_grad_norm=)``; the norm of the step is ``optimizer.grad_norm``, a device tensor)."""
     if pacer is not None:
         pacer.wait()
     optimizer.zero_grad(set_to_none=True)
