@@ -482,6 +482,24 @@ int zsv_adamw_multi_scaled(const zsv_adam_tensor* table_device, int32_t count, i
                            const zsv_clip_record* clip_device, const zsv_scaler_state* state_device,
                            int32_t grads_unscaled, void* stream);
 
+/* ---- gradient accumulation over several backward passes (ddp.GradientSync, begin_step(passes=k)) ---------------------
+ * Folds a set of freshly produced gradient tensors into their slices of a flat accumulator (a gradient bucket) in ONE
+ * launch.  `table_device`: `count` descriptors sorted by first_chunk, chunks of 4096 elements exactly as for
+ * zsv_adam_multi.  `acc` and `g` need only be 4-byte aligned, each on its own (bucket slices start at element offsets);
+ * no element outside [acc, acc + n) is written and none outside [g, g + n) is read.
+ *   assign != 0: acc = scale * g        (first pass of a step: no zero-fill pass over the bucket)
+ *   assign == 0: acc = acc + scale * g  (computed as fl(acc + fl(scale * g)): no contraction into an fma)
+ * No atomics: the result is bit-reproducible.  Non-finite gradients are data: they propagate into acc as IEEE
+ * arithmetic says (the loss scaler's check then sees them in the accumulated bucket). */
+typedef struct zsv_accum_tensor {
+    float* acc;
+    const float* g;
+    int64_t n;
+    int64_t first_chunk;
+} zsv_accum_tensor;
+int zsv_grad_accum_multi(const zsv_accum_tensor* table_device, int32_t count, int64_t total_chunks, float scale,
+                         int32_t assign, void* stream);
+
 /* ---- weight panels packed ahead of the call ---------------------------------------------------------------------------
  * Every forward / dgrad entry point above first re-lays its weights out (a "panel": the direct kernel's [block][tap][16][m]
  * image, the Winograd kernels' transformed weights, the stride-2 dgrad's tap-major image) in a small launch of its own: 76

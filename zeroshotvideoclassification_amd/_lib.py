@@ -123,6 +123,7 @@ SIGNATURES = {
     "zsv_adamw_multi": (c_int, [_P, c_int32, c_int64, c_double, c_float, c_float, c_float, c_double, c_int32, _P, c_int32, _P]),
     "zsv_adamw_multi_scaled": (c_int, [_P, c_int32, c_int64, c_double, c_float, c_float, c_float, c_double, c_int32, _P, _P,
                                        c_int32, _P]),
+    "zsv_grad_accum_multi": (c_int, [_P, c_int32, c_int64, c_float, c_int32, _P]),
     "zsv_adam_step": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, _P]),
     "zsv_conv3d_panel_query": (c_int, [POINTER(ConvDesc), c_int32, c_int32, POINTER(c_size_t)]),
     "zsv_conv3d_panel_job": (c_int, [POINTER(ConvDesc), c_int32, c_int32, _P, _P, c_size_t, _P]),

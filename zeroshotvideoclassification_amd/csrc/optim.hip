@@ -7,6 +7,8 @@
 //                                                  gradient's way into the update, the gradients in memory are not rewritten
 //   Adam(weight_decay=) / AdamW                    adamw_multi / adamw_multi_scaled
 //   GradScaler.unscale_                            grad_unscale_multi
+//   k x loss.backward() accumulating into .grad    grad_accum_multi (table of {acc, g}: acc = [acc +] scale * g, one launch per
+//                                                  gradient bucket and backward pass; ddp.GradientSync)
 //
 // All of them walk the zsv_adam_tensor table of zsv_adam_multi (elementwise_pool.hip) the same way: one workgroup of 256
 // threads per chunk, a binary search over first_chunk.  No floating-point atomics: every sum has a fixed order, so the same
@@ -130,6 +132,77 @@ __global__ __launch_bounds__(256) void adamw_multi_scaled_kernel(const zsv_adam_
     adamw_chunk(table, count, a, inv_scale, step_size, inv_sqrt_bc2);
 }
 
+// ---- gradient accumulation: acc = [acc +] scale * g over a table of {accumulator slice, fresh gradient} ---------------------
+// One workgroup per 4096-element chunk, as above.  An HBM-bound streaming pass (read g, read-modify-write acc), so the body
+// moves 16 bytes per lane: the accumulator slices start at arbitrary ELEMENT offsets of a flat bucket and the gradients are
+// allocations of their own, i.e. the two pointers of an entry are only 4-byte aligned and differently so.  Per chunk:
+//   head   0-3 scalar elements up to the first 16-byte boundary of `acc`
+//   body   aligned float4 on `acc`; `g` as an aligned float4 when it happens to be aligned there too (wave-uniform test),
+//          else as four dword loads
+//   tail   0-3 scalar elements
+// `g` is read once per pass and never again: non-temporal loads, so its lines do not push the kernels running next to this
+// pass (the backward still in flight on the other queue) out of the cache.  No element outside [acc, acc + n) is touched.
+// fl(acc + fl(scale * g)) with the contraction into an fma switched off: the sum has the bits torch's mul + add gives.
+typedef float acc_v4f __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float accum_one(float a, float g, float scale, bool assign) {
+#pragma clang fp contract(off)
+    const float sg = scale * g;
+    return assign ? sg : a + sg;
+}
+
+__global__ __launch_bounds__(256) void grad_accum_multi_kernel(const zsv_accum_tensor* __restrict__ table, int count, float scale,
+                                                               int assign) {
+    const long chunk = blockIdx.x;
+    int lo = 0, hi = count - 1;                       // last tensor whose first_chunk <= chunk
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
+    }
+    const zsv_accum_tensor t = table[lo];
+    const long base = (chunk - t.first_chunk) * OPT_CHUNK;
+    if (base >= t.n) return;
+    const int len = (int)min((long)OPT_CHUNK, t.n - base);
+    float* __restrict__ acc = t.acc + base;
+    const float* __restrict__ g = t.g + base;
+    const bool set = assign != 0;
+
+    const int head = min(len, (int)(((16u - (unsigned)((uintptr_t)acc & 15u)) & 15u) >> 2));
+    const int nvec = (len - head) >> 2;
+    const int tail0 = head + 4 * nvec;                // [tail0, len): 0-3 elements
+    if ((int)threadIdx.x < head) {
+        const int i = threadIdx.x;
+        acc[i] = accum_one(set ? 0.f : acc[i], __builtin_nontemporal_load(g + i), scale, set);
+    }
+    if ((int)threadIdx.x < len - tail0) {
+        const int i = tail0 + threadIdx.x;
+        acc[i] = accum_one(set ? 0.f : acc[i], __builtin_nontemporal_load(g + i), scale, set);
+    }
+    acc_v4f* __restrict__ av = reinterpret_cast<acc_v4f*>(acc + head);
+    const float* __restrict__ gb = g + head;
+    const bool g_aligned = ((uintptr_t)gb & 15u) == 0;        // same for every lane of the chunk
+#pragma unroll 2
+    for (int v = threadIdx.x; v < nvec; v += 256) {
+        acc_v4f gv;
+        if (g_aligned) {
+            gv = __builtin_nontemporal_load(reinterpret_cast<const acc_v4f*>(gb) + v);
+        } else {
+            gv[0] = __builtin_nontemporal_load(gb + 4 * v);
+            gv[1] = __builtin_nontemporal_load(gb + 4 * v + 1);
+            gv[2] = __builtin_nontemporal_load(gb + 4 * v + 2);
+            gv[3] = __builtin_nontemporal_load(gb + 4 * v + 3);
+        }
+        acc_v4f a;
+        if (set) a = acc_v4f{0.f, 0.f, 0.f, 0.f}; else a = av[v];
+        acc_v4f r;
+        r[0] = accum_one(a[0], gv[0], scale, set);
+        r[1] = accum_one(a[1], gv[1], scale, set);
+        r[2] = accum_one(a[2], gv[2], scale, set);
+        r[3] = accum_one(a[3], gv[3], scale, set);
+        av[v] = r;
+    }
+}
+
 static inline bool bad_table(int32_t count, int64_t total_chunks) {
     return count <= 0 || total_chunks <= 0 || total_chunks > 0x7fffffffL;
 }
@@ -206,5 +279,14 @@ extern "C" int zsv_adamw_multi_scaled(const zsv_adam_tensor* table_device, int32
     if (!make_args(a, lr, beta1, beta2, eps, weight_decay, decoupled, clip_device)) return ZSV_E_BAD_SHAPE;
     hipLaunchKernelGGL(adamw_multi_scaled_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
                        count, a, lr, state_device, grads_unscaled);
+    return launch_status();
+}
+
+extern "C" int zsv_grad_accum_multi(const zsv_accum_tensor* table_device, int32_t count, int64_t total_chunks, float scale,
+                                    int32_t assign, void* stream) {
+    if (!table_device) return ZSV_E_NULL;
+    if (bad_table(count, total_chunks)) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
+    hipLaunchKernelGGL(grad_accum_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
+                       count, scale, (int)assign);
     return launch_status();
 }

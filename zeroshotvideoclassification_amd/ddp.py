@@ -24,6 +24,18 @@ copied back), so ``optim.FusedAdam(..., grad_buckets=sync)`` walks the all-reduc
 descriptor table built once, and ``torch.optim.Adam`` sees ordinary ``.grad`` tensors.
 ``GradientSync(model, local=True)`` keeps the bucketing without any collective (one process, one GPU).
 
+Gradient accumulation: ``begin_step(passes=k)`` declares k backward passes (micro-batches) per optimizer step; ``end_pass()``
+closes each but the last, ``finish_step()`` the last (``train.train_step(micro_batches=k)`` drives all of it).  The bucket is the
+accumulator: when a bucket completes in pass j the side stream folds the fresh gradients into it with ONE
+``zsv_grad_accum_multi`` launch (csrc/optim.hip; ``acc = scale * g`` in the first pass, so the bucket is never zero-filled,
+``acc += scale * g`` after it; scale = 1/world), ``end_pass()`` drops ``.grad`` of the live parameters so the next backward
+hands over fresh tensors, the all-reduce runs once per optimizer step (in pass k), ``.grad`` become the bucket views in
+``finish_step()`` as always and ``FusedAdam``'s table stays static.  k micro-batches of 22 followed by one step is what
+DataParallel computes over k replicas (each with its own BatchNorm batch statistics); the running statistics are updated k
+times, as torch does under accumulation.  If the very first step has k > 1, the live set and the bucket layout are fixed at the
+end of its first pass.  CPU tensors (gloo) accumulate with ``_foreach_copy_`` / ``_foreach_add_``.  ``passes=1`` is the path
+described above, unchanged.
+
 With equal shards, the mean over ranks of per-rank mean-MSE gradients equals the full-batch
 mean-MSE gradient DataParallel computes.  Works on CPU tensors with the gloo backend (tests).
 """
@@ -31,12 +43,15 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional
 
+import struct
 import weakref
+from ctypes import c_void_p
 
 import torch
 import torch.distributed as dist
 
 from . import _lib
+from ._tables import PinnedRing, chunks as _chunks
 
 DEFAULT_BUCKET_BYTES = 25 * 1024 * 1024
 
@@ -77,6 +92,14 @@ class _Bucket:
             off += p.numel()
         self.pending = len(params)
         self.work = None
+        # static half of the zsv_grad_accum_multi table: (accumulator slice address, n, first_chunk) per non-empty parameter
+        self.slices, first = [], 0
+        if self.flat.is_cuda:
+            for i, v in enumerate(self.views):
+                if v.numel():
+                    self.slices.append((i, v.data_ptr(), v.numel(), first))
+                    first += _chunks(v.numel())
+        self.chunks = first
 
 
 class GradientSync:
@@ -98,8 +121,11 @@ class GradientSync:
         self._buckets: Optional[List[_Bucket]] = None
         self._bucket_of: Dict[int, _Bucket] = {}
         self._in_step = False
+        self._passes = 1                         # backward passes of the current step (begin_step(passes=))
+        self._pass = 0                           # index of the pass in flight
         self._cuda = any(p.is_cuda for p in self.params)
         self._side = torch.cuda.Stream() if self._cuda else None
+        self._ring = PinnedRing(8)               # accumulate tables: one upload per bucket and pass
         # (ops._dw_read_early: a post-accumulate hook normally reads `.grad` on the backward stream, so the weight-gradient side
         # stream is joined before it runs; THIS hook joins that stream itself in `_launch`, and says so to keep the overlap)
         owner = weakref.ref(self)
@@ -163,7 +189,12 @@ class GradientSync:
         return [] if self._buckets is None else [b.numel for b in self._buckets]
 
     # -- per step ------------------------------------------------------------------------
-    def begin_step(self) -> None:
+    def begin_step(self, passes: int = 1) -> None:
+        """``passes``: the number of backward passes (micro-batches) whose gradients this optimizer step sums; each but the
+        last is closed with ``end_pass()``, the last with ``finish_step()``."""
+        if isinstance(passes, bool) or not isinstance(passes, int) or passes < 1:
+            raise ValueError(f"begin_step: passes must be an integer >= 1, not {passes!r}")
+        self._passes, self._pass = passes, 0
         self._in_step = True
         self._arrival = []
         self.bytes_reduced_last_step = 0
@@ -183,8 +214,9 @@ class GradientSync:
             raise RuntimeError("a parameter that produced no gradient in the first step produced one now; "
                                "rebuild GradientSync (the live set is fixed after discovery)")
         if b.pending <= 0:
-            raise RuntimeError("a gradient arrived for a bucket that was already reduced this step: two backward "
-                               "passes per begin_step() (gradient accumulation) are not supported")
+            raise RuntimeError("a gradient arrived for a bucket that was already complete in this pass: a second backward "
+                               "pass must be declared (begin_step(passes=k) with end_pass() between the passes; "
+                               "train_step(micro_batches=k))")
         b.pending -= 1
         if b.pending == 0:
             self._launch(b)
@@ -192,9 +224,13 @@ class GradientSync:
     @torch.no_grad()
     def _launch(self, b: _Bucket) -> None:
         """Pack the bucket's gradients into its flat buffer, sum over ranks, scale by 1/world -- on the side
-        stream.  Nothing is copied back: ``finish_step`` points each ``.grad`` at its slice of the buffer."""
+        stream.  Nothing is copied back: ``finish_step`` points each ``.grad`` at its slice of the buffer.
+        In a step of several passes the bucket is the accumulator (``_accumulate``) and only the last pass exchanges it."""
         grads = [p.grad for p in b.params]
         scale = 1.0 / self.world
+        if self._passes > 1:
+            self._launch_pass(b, grads, scale)
+            return
         if self._cuda:
             ready = torch.cuda.Event()
             ready.record(torch.cuda.current_stream())
@@ -216,20 +252,95 @@ class GradientSync:
                 b.flat.mul_(scale)
         self.bytes_reduced_last_step += b.numel * b.flat.element_size()
 
+    def _launch_pass(self, b: _Bucket, grads, scale: float) -> None:
+        """Pass j of k > 1: bucket (+)= this pass's gradients; the collective runs in pass k only.  On HIP tensors 1/world
+        goes into every pass as the kernel's ``scale`` (no ``mul_`` pass over the bucket after the all-reduce); CPU tensors
+        (gloo) keep ``mul_``."""
+        first, last = self._pass == 0, self._pass == self._passes - 1
+        if self._cuda:
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream())
+            self._side.wait_event(ready)
+            from . import ops
+            ops.join_wgrad_streams(self._side)
+            with torch.cuda.stream(self._side):
+                self._accumulate(b, grads, scale, first)
+                if last and self.world > 1:
+                    b.work = dist.all_reduce(b.flat, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
+                    b.work.wait()
+                for g in grads:
+                    g.record_stream(self._side)
+        else:
+            if first:
+                torch._foreach_copy_(b.views, grads)
+            else:
+                torch._foreach_add_(b.views, grads)
+            if last and self.world > 1:
+                dist.all_reduce(b.flat, op=dist.ReduceOp.SUM, group=self.group)
+                b.flat.mul_(scale)
+        if last:
+            self.bytes_reduced_last_step += b.numel * b.flat.element_size()
+
+    def _accumulate(self, b: _Bucket, grads, scale: float, assign: bool) -> None:
+        """One ``zsv_grad_accum_multi`` launch on the current (side) stream: every slice of the bucket = [itself +] scale * its
+        gradient.  The gradients are fresh allocations every pass, so the table is built and uploaded per launch."""
+        dev = b.flat.device
+        entries, keep = [], []
+        for i, acc, n, first in b.slices:
+            g = grads[i]
+            if g is None or not g.is_cuda or g.dtype != torch.float32 or b.flat.dtype != torch.float32 or g.numel() != n:
+                raise RuntimeError("GradientSync: gradient accumulation needs dense fp32 gradients on the HIP device "
+                                   "(no fallback)")
+            if not g.is_contiguous():
+                g = g.contiguous()
+                keep.append(g)
+            entries.append(struct.pack("<QQqq", acc, g.data_ptr(), n, first))
+        if not entries:
+            return
+        with torch.cuda.device(dev):
+            table = self._ring.upload(bytearray(b"".join(entries)), dev)
+            _lib.check(_lib.load().zsv_grad_accum_multi(table.data_ptr(), len(entries), b.chunks, float(scale), int(bool(assign)),
+                                                        c_void_p(torch.cuda.current_stream().cuda_stream)),
+                       "zsv_grad_accum_multi")
+        del keep, table                            # allocated on this stream: reused only behind the launch
+
+    def end_pass(self) -> None:
+        """Call after every backward pass of a ``begin_step(passes=k)`` step except the last (after
+        ``ops.join_wgrad_streams()``).  Checks that the pass produced every live gradient, drops ``.grad`` of the live
+        parameters (the next backward hands over fresh gradients instead of adding into the old ones) and re-arms the
+        buckets.  If this is the very first pass, it fixes the live set and the bucket layout."""
+        if not self._in_step:
+            raise RuntimeError("end_pass() without begin_step()")
+        if self._pass >= self._passes - 1:
+            raise RuntimeError(f"end_pass() after the last of the {self._passes} declared passes: call finish_step() "
+                               "(or declare more with begin_step(passes=k) / train_step(micro_batches=k))")
+        self._close_pass()
+        for b in self._buckets:
+            for p in b.params:
+                p.grad = None
+            b.pending = len(b.params)
+        self._pass += 1
+
     def finish_step(self) -> None:
         """Call after ``loss.backward()`` and before ``optimizer.step()``."""
         if not self._in_step:
             raise RuntimeError("finish_step() without begin_step()")
+        if self._pass != self._passes - 1:
+            raise RuntimeError(f"finish_step() after {self._pass + 1} of the {self._passes} backward passes declared with "
+                               "begin_step(passes=k) / train_step(micro_batches=k)")
         self._in_step = False
+        self._close_pass()
+        self._adopt_bucket_views()
+
+    def _close_pass(self) -> None:
         if self._buckets is None:
-            # first step: the live set and the production order are now known.  Ranks must agree
+            # first pass ever: the live set and the production order are now known.  Ranks must agree
             # on them (same model, same graph) -- checked cheaply through the count.
             order = list(self._arrival)
             if self.local:
                 self._build_buckets(order)
                 for b in self._buckets:
                     self._launch(b)
-                self._adopt_bucket_views()
                 return
             count = torch.tensor([len(order)], dtype=torch.int64, device=self.params[0].device)
             lo, hi = count.clone(), count.clone()
@@ -250,14 +361,13 @@ class GradientSync:
                 raise RuntimeError("ranks disagree on which parameters receive gradients (same count, different set)")
             order = [int(i) for i in ref.tolist()]
             self._build_buckets(order)
-            for b in self._buckets:                # no overlap in the discovery step
+            for b in self._buckets:                # no overlap in the discovery pass
                 self._launch(b)
         else:
             late = [b for b in self._buckets if b.pending != 0]
             if late:
                 missing = sum(b.pending for b in late)
                 raise RuntimeError(f"{missing} live parameters produced no gradient this step")
-        self._adopt_bucket_views()
 
     def _adopt_bucket_views(self) -> None:
         if self._cuda:

@@ -49,8 +49,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-
-_CHUNK = 4096
+from ._tables import CHUNK as _CHUNK, PinnedRing
 
 
 def _stream():
@@ -172,8 +171,7 @@ class FusedAdam(torch.optim.Optimizer):
         self.max_grad_norm = max_grad_norm
         self._clip = None                                 # zsv_clip_record {total_norm, clip_coef} on the device
         self._partials = None                             # one float per gradient chunk (zsv_grad_norm_multi)
-        self._ring = [[None, None] for _ in range(4)]     # (pinned staging buffer, copy-done event)
-        self._next = 0
+        self._ring = PinnedRing(4)                        # staging for the per-step descriptor tables
         self.grad_buckets = grad_buckets                  # ddp.GradientSync (or None)
         self._static = None                               # (layout_version, table, count, chunks, [(p, grad ptr)], flats)
         self._host_steps = 0                              # steps taken without a scaler
@@ -209,21 +207,7 @@ class FusedAdam(torch.optim.Optimizer):
             raise RuntimeError("FusedAdam needs contiguous fp32 parameters on a HIP device (no CPU fallback)")
 
     def _upload(self, raw: bytearray, dev) -> torch.Tensor:
-        # The host runs ahead of the GPU, so a pinned staging buffer may not be rewritten until the
-        # copy queued from it has executed: rotate over a small ring guarded by events (a pageable
-        # copy would be safe too, but torch synchronises the stream for it and the run-ahead is lost).
-        nbytes = len(raw)
-        slot = self._ring[self._next % len(self._ring)]
-        self._next += 1
-        if slot[0] is None or slot[0].numel() < nbytes:
-            slot[0] = torch.empty(max(nbytes, 48 * 512), dtype=torch.uint8).pin_memory()
-        if slot[1] is not None:
-            slot[1].synchronize()
-        slot[0][:nbytes].copy_(torch.frombuffer(raw, dtype=torch.uint8))
-        table = slot[0][:nbytes].to(dev, non_blocking=True)
-        slot[1] = torch.cuda.Event()
-        slot[1].record(torch.cuda.current_stream(dev))
-        return table
+        return self._ring.upload(raw, dev)                # pinned ring guarded by events (_tables.PinnedRing)
 
     def _dynamic_table(self, group):
         entries, first, keep = [], 0, []

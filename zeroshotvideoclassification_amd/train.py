@@ -92,7 +92,8 @@ class StepPacer:
 
 def train_step(model: torch.nn.Module, optimizer: torch.optim.Optimizer, criterion, x: torch.Tensor,
                z: torch.Tensor, grad_sync=None, scaler=None, pacer: Optional[StepPacer] = None,
-               autocast: bool = False, graph: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               autocast: bool = False, graph: Optional[bool] = None,
+               micro_batches: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """One iteration of main.py:170-203.  ``grad_sync`` (a ``ddp.GradientSync``) all-reduces the
     gradients across ranks, overlapped with backward, before the optimizer step.  ``scaler`` (an
     ``optim.LossScaler`` or a ``torch.cuda.amp.GradScaler``) reproduces main.py:195-203:
@@ -102,7 +103,21 @@ def train_step(model: torch.nn.Module, optimizer: torch.optim.Optimizer, criteri
     statistics, parameters, gradients and loss); the default is the fp32 step of BASELINE configs 1-3, which is what the
     reference's CPU path runs (autocast is a no-op there).  ``pacer`` (a ``StepPacer``) bounds the host's lead over the device.
     Weight decay and gradient clipping need no argument here: the optimizer carries them (``optim.FusedAdam(weight_decay=,
-    decoupled_weight_decay=, max_grad_norm=)``; the norm of the step is ``optimizer.grad_norm``, a device tensor)."""
+    decoupled_weight_decay=, max_grad_norm=)``; the norm of the step is ``optimizer.grad_norm``, a device tensor).
+
+    ``micro_batches=k`` accumulates the gradient over k consecutive parts of ``x`` / ``z`` (sizes as equal as possible, larger
+    first) before ONE optimizer step: each part has its own forward, BatchNorm batch statistics and backward of
+    ``(n_j / N) * loss_j`` -- what ``nn.DataParallel`` over k replicas computes (main.py:61-63,126), and torch's literal
+    accumulation recipe.  The running statistics are updated k times and ``num_batches_tracked`` advances by k, as under
+    torch accumulation (DataParallel keeps replica 0's update only).  One loss scale and one non-finite check per step: a
+    non-finite gradient in any part skips the whole step.  Clipping and weight decay act on the accumulated gradient.
+    Returns the concatenated embeddings and ``sum_j (n_j / N) * loss_j`` (the loss of the whole batch for a mean-reduced
+    criterion).  With a ``grad_sync`` the flat buckets are the accumulators (one ``zsv_grad_accum_multi`` launch per bucket
+    and part, one exchange per step); ``GradientSync(model, local=True)`` is the intended single-GPU path.  Without one the
+    loop relies on autograd's own accumulation into ``.grad`` (torch add kernels)."""
+    if micro_batches != 1:
+        return _train_step_accumulated(model, optimizer, criterion, x, z, grad_sync, scaler, pacer, autocast, graph,
+                                       micro_batches)
     if pacer is not None:
         pacer.wait()
     optimizer.zero_grad(set_to_none=True)
@@ -128,6 +143,58 @@ def train_step(model: torch.nn.Module, optimizer: torch.optim.Optimizer, criteri
     if pacer is not None:
         pacer.mark()
     return y.detach(), loss.detach()
+
+
+def micro_batch_sizes(n: int, k: int) -> list:
+    """``n`` samples in ``k`` consecutive parts, as equal as possible, the larger ones first."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"micro_batches must be an integer >= 1, not {k!r}")
+    if k > n:
+        raise ValueError(f"micro_batches={k} exceeds the {n} samples of the batch")
+    base, extra = divmod(n, k)
+    return [base + 1] * extra + [base] * (k - extra)
+
+
+def _train_step_accumulated(model, optimizer, criterion, x, z, grad_sync, scaler, pacer, autocast, graph, micro_batches):
+    """``train_step(micro_batches=k)`` for k > 1 (see there)."""
+    total = int(x.shape[0])
+    sizes = micro_batch_sizes(total, micro_batches)
+    if int(z.shape[0]) != total:
+        raise ValueError(f"train_step: {total} clips but {int(z.shape[0])} targets")
+    if pacer is not None:
+        pacer.wait()
+    optimizer.zero_grad(set_to_none=True)
+    if grad_sync is not None:
+        grad_sync.begin_step(passes=micro_batches)
+    ys, loss_sum = [], None
+    parts = zip(torch.split(x, sizes), torch.split(z, sizes))
+    for j, (xj, zj) in enumerate(parts):
+        if autocast:
+            from . import amp
+            with amp.autocast(graph=graph):
+                yj = embed(model, xj)
+                loss = criterion(yj, zj)
+        else:
+            yj = embed(model, xj)
+            loss = criterion(yj, zj)
+        loss = loss * (sizes[j] / total)
+        (scaler.scale(loss) if scaler is not None else loss).backward()
+        ops.join_wgrad_streams()
+        if grad_sync is not None:
+            if j + 1 < micro_batches:
+                grad_sync.end_pass()
+            else:
+                grad_sync.finish_step()
+        ys.append(yj.detach())
+        loss_sum = loss.detach() if loss_sum is None else loss_sum + loss.detach()
+    if scaler is not None:
+        scaler.step(optimizer)
+        scaler.update()
+    else:
+        optimizer.step()
+    if pacer is not None:
+        pacer.mark()
+    return torch.cat(ys), loss_sum
 
 
 def nearest_classes(embed_: torch.Tensor, class_embed: torch.Tensor, k: int = 5) -> torch.Tensor:
