@@ -500,6 +500,60 @@ typedef struct zsv_accum_tensor {
 int zsv_grad_accum_multi(const zsv_accum_tensor* table_device, int32_t count, int64_t total_chunks, float scale,
                          int32_t assign, void* stream);
 
+/* ---- weight averaging (EMA / SWA) fused into the Adam step: torch.optim.swa_utils.AveragedModel on the device ----------
+ * A "shadow" holds the running average of a parameter (or of a BatchNorm running statistic).  The count of optimizer
+ * steps averaged so far lives in device memory, so neither the "first averaged step copies" rule nor a step the loss
+ * scaler skips needs the host.  Per element, with p the value the update has just produced:
+ *   n_averaged == 0:           avg = p                                   (AveragedModel's first update: an exact copy)
+ *   w = ema_weight             when ema_weight >= 0: EMA, the caller passes (float)(1.0 - decay)
+ *   w = 1.f / (n_averaged + 1) when ema_weight <  0: equal-weight running mean (SWA)
+ *   avg = w < 0.5 ? avg + w * (p - avg) : p - (p - avg) * (1 - w)        (torch.lerp(avg, p, w))
+ * All fp32, chunked by 4096 elements, no atomics: the same inputs give the same bits on every run. */
+typedef struct zsv_avg_state {
+    int32_t n_averaged;   /* optimizer steps averaged so far (skipped steps do not count) */
+} zsv_avg_state;
+/* zsv_adam_multi / zsv_adam_multi_scaled / zsv_adamw_multi / zsv_adamw_multi_scaled with the average folded in:
+ * `shadows_device` is a device array of `count` pointers, parallel to the table (shadows_device[i] has table[i].n elements,
+ * 4-byte aligned); each launch updates p, exp_avg and exp_avg_sq to the very bits its plain form gives and then applies
+ * the rule above to the shadow with the new p.  They read `avg_state_device` and do not advance it (zsv_avg_advance).
+ * Under the loss scaler a launch that returns on found_inf leaves the shadows untouched. */
+int zsv_adam_multi_avg(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, float lr, float beta1,
+                       float beta2, float eps, int32_t step, float* const* shadows_device,
+                       const zsv_avg_state* avg_state_device, float ema_weight, void* stream);
+int zsv_adam_multi_scaled_avg(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, float lr,
+                              float beta1, float beta2, float eps, const zsv_scaler_state* state_device,
+                              float* const* shadows_device, const zsv_avg_state* avg_state_device, float ema_weight,
+                              void* stream);
+int zsv_adamw_multi_avg(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr, float beta1,
+                        float beta2, float eps, double weight_decay, int32_t decoupled, const zsv_clip_record* clip_device,
+                        int32_t step, float* const* shadows_device, const zsv_avg_state* avg_state_device,
+                        float ema_weight, void* stream);
+int zsv_adamw_multi_scaled_avg(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr,
+                               float beta1, float beta2, float eps, double weight_decay, int32_t decoupled,
+                               const zsv_clip_record* clip_device, const zsv_scaler_state* state_device,
+                               int32_t grads_unscaled, float* const* shadows_device,
+                               const zsv_avg_state* avg_state_device, float ema_weight, void* stream);
+/* A pair of equally long fp32 arrays for zsv_avg_multi (a = the live value, read; b = its shadow) and zsv_swap_multi.
+ * `a` and `b` need only be 4-byte aligned, each on its own (shadows are slices of a flat buffer); tables are sorted by
+ * first_chunk exactly as for zsv_adam_multi.  No element outside [b, b + n) -- and, for the swap, [a, a + n) -- is written. */
+typedef struct zsv_pair_tensor {
+    float* a;
+    float* b;
+    int64_t n;
+    int64_t first_chunk;
+} zsv_pair_tensor;
+/* The averaging rule over a table, b = rule(b, a): for values no Adam launch produces (BatchNorm running statistics).
+ * `scaler_state_device` may be NULL; when its found_inf is set the launch writes nothing.  Reads `avg_state_device`. */
+int zsv_avg_multi(const zsv_pair_tensor* table_device, int32_t count, int64_t total_chunks,
+                  const zsv_avg_state* avg_state_device, float ema_weight, const zsv_scaler_state* scaler_state_device,
+                  void* stream);
+/* n_averaged += (scaler_state_device == NULL || !found_inf): once per optimizer step, after every launch of the step that
+ * reads the counter and before zsv_scaler_update clears the flag.  One thread. */
+int zsv_avg_advance(zsv_avg_state* avg_state_device, const zsv_scaler_state* scaler_state_device, void* stream);
+/* Exchanges a[i] and b[i] in place over a table, one launch: the averaged values move INTO the live tensors (whose
+ * addresses everything else is keyed on) and back, exactly. */
+int zsv_swap_multi(const zsv_pair_tensor* table_device, int32_t count, int64_t total_chunks, void* stream);
+
 /* ---- weight panels packed ahead of the call ---------------------------------------------------------------------------
  * Every forward / dgrad entry point above first re-lays its weights out (a "panel": the direct kernel's [block][tap][16][m]
  * image, the Winograd kernels' transformed weights, the stride-2 dgrad's tap-major image) in a small launch of its own: 76

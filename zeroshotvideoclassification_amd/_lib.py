@@ -124,6 +124,16 @@ SIGNATURES = {
     "zsv_adamw_multi_scaled": (c_int, [_P, c_int32, c_int64, c_double, c_float, c_float, c_float, c_double, c_int32, _P, _P,
                                        c_int32, _P]),
     "zsv_grad_accum_multi": (c_int, [_P, c_int32, c_int64, c_float, c_int32, _P]),
+    # the four Adam launches with weight averaging: their own arguments up to the stream, then shadows, avg state, ema_weight
+    "zsv_adam_multi_avg": (c_int, [_P, c_int32, c_int64, c_float, c_float, c_float, c_float, c_int32, _P, _P, c_float, _P]),
+    "zsv_adam_multi_scaled_avg": (c_int, [_P, c_int32, c_int64, c_float, c_float, c_float, c_float, _P, _P, _P, c_float, _P]),
+    "zsv_adamw_multi_avg": (c_int, [_P, c_int32, c_int64, c_double, c_float, c_float, c_float, c_double, c_int32, _P, c_int32,
+                                    _P, _P, c_float, _P]),
+    "zsv_adamw_multi_scaled_avg": (c_int, [_P, c_int32, c_int64, c_double, c_float, c_float, c_float, c_double, c_int32, _P, _P,
+                                           c_int32, _P, _P, c_float, _P]),
+    "zsv_avg_multi": (c_int, [_P, c_int32, c_int64, _P, c_float, _P, _P]),
+    "zsv_avg_advance": (c_int, [_P, _P, _P]),
+    "zsv_swap_multi": (c_int, [_P, c_int32, c_int64, _P]),
     "zsv_adam_step": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, _P]),
     "zsv_conv3d_panel_query": (c_int, [POINTER(ConvDesc), c_int32, c_int32, POINTER(c_size_t)]),
     "zsv_conv3d_panel_job": (c_int, [POINTER(ConvDesc), c_int32, c_int32, _P, _P, c_size_t, _P]),

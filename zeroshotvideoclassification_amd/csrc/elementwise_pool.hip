@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "zsv_hip.h"
 #include "zsv_common.h"
+#include "adam_update.h"
 
 namespace zsv {
 
@@ -403,7 +404,8 @@ extern "C" int zsv_adam_step(float* p, const float* g, float* exp_avg, float* ex
 }
 
 // ---- multi-tensor Adam: one launch for every parameter tensor of the model ---------------------
-// table[i] = {p, g, exp_avg, exp_avg_sq, n, first_chunk}; a chunk is 256 threads x 16 elements.
+// table[i] = {p, g, exp_avg, exp_avg_sq, n, first_chunk}; a chunk is 256 threads x 16 elements.  The per-element update is
+// adam_element (adam_update.h), shared with the weight-averaging forms of optim.hip.
 namespace zsv {
 constexpr int ADAM_CHUNK = 4096;
 __global__ __launch_bounds__(256) void adam_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count, float b1,
@@ -418,14 +420,8 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const zsv_adam_tensor* 
     const zsv_adam_tensor t = table[lo];
     const long base = (chunk - t.first_chunk) * ADAM_CHUNK;
     const long end = min(t.n, base + ADAM_CHUNK);
-    for (long i = base + threadIdx.x; i < end; i += 256) {
-        const float gi = t.g[i];
-        const float mi = b1 * t.exp_avg[i] + (1.f - b1) * gi;
-        const float vi = b2 * t.exp_avg_sq[i] + (1.f - b2) * gi * gi;
-        t.exp_avg[i] = mi;
-        t.exp_avg_sq[i] = vi;
-        t.p[i] -= step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-    }
+    for (long i = base + threadIdx.x; i < end; i += 256)
+        adam_element<false>(t, i, t.g[i], b1, b2, eps, step_size, inv_sqrt_bc2, nullptr, AvgWeight{});
 }
 }  // namespace zsv
 
@@ -483,14 +479,8 @@ __global__ __launch_bounds__(256) void adam_multi_scaled_kernel(const zsv_adam_t
     const zsv_adam_tensor t = table[lo];
     const long base = (chunk - t.first_chunk) * ADAM_CHUNK;
     const long end = min(t.n, base + ADAM_CHUNK);
-    for (long i = base + threadIdx.x; i < end; i += 256) {
-        const float gi = t.g[i] * inv_scale;
-        const float mi = b1 * t.exp_avg[i] + (1.f - b1) * gi;
-        const float vi = b2 * t.exp_avg_sq[i] + (1.f - b2) * gi * gi;
-        t.exp_avg[i] = mi;
-        t.exp_avg_sq[i] = vi;
-        t.p[i] -= step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-    }
+    for (long i = base + threadIdx.x; i < end; i += 256)
+        adam_element<false>(t, i, t.g[i] * inv_scale, b1, b2, eps, step_size, inv_sqrt_bc2, nullptr, AvgWeight{});
 }
 
 __global__ void scaler_update_kernel(zsv_scaler_state* st, float growth, float backoff, int interval) {

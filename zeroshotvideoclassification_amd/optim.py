@@ -38,9 +38,17 @@ Fine-tuning options (csrc/optim.hip), all off by default -- with ``weight_decay 
   ``unscale_`` + ``clip_grad_norm_`` + ``step`` recipe.
 
 No floating-point atomics: the same gradients give the same norm bits and the same parameter bits on every run.
+
+``WeightAverage(optimizer, decay=)`` keeps an exponential moving average (``decay=None``: an equal-weight running mean, SWA) of
+every parameter of a ``FusedAdam`` -- ``torch.optim.swa_utils.AveragedModel`` folded into the optimizer's own launch: the
+``*_avg`` forms of the four update kernels apply the average with the new parameter value still in a register, the count of
+averaged steps is device state (a step the scaler skips averages nothing, and the host never learns which it was), and
+``applied()`` swaps the averaged values INTO the live tensors for evaluation.  Without a ``WeightAverage`` the step launches
+what it always did.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import struct
 from ctypes import c_void_p
@@ -177,6 +185,7 @@ class FusedAdam(torch.optim.Optimizer):
         self._host_steps = 0                              # steps taken without a scaler
         self._resumed = False                             # state came from load_state_dict (a scaler may then join late)
         self._scaler: Optional[LossScaler] = None
+        self._average: Optional["WeightAverage"] = None   # set by WeightAverage(optimizer): the update launches average too
 
     @staticmethod
     def _check_decay(weight_decay):
@@ -210,7 +219,7 @@ class FusedAdam(torch.optim.Optimizer):
         return self._ring.upload(raw, dev)                # pinned ring guarded by events (_tables.PinnedRing)
 
     def _dynamic_table(self, group):
-        entries, first, keep = [], 0, []
+        entries, first, keep, live = [], 0, [], []
         for p in group["params"]:
             if p.grad is None:
                 continue
@@ -223,10 +232,13 @@ class FusedAdam(torch.optim.Optimizer):
             n = p.numel()
             entries.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), n, first))
             keep.append(g)
+            live.append(p)
             first += (n + _CHUNK - 1) // _CHUNK
         if not entries:
             return None
         raw = bytearray(b"".join(struct.pack("<QQQQqq", *e) for e in entries))
+        if self._average is not None:
+            raw += self._average._shadow_pointers(live)   # the shadow-pointer array rides behind the table (_avg_args)
         table = self._upload(raw, keep[0].device)
         return table, len(entries), first, keep
 
@@ -262,6 +274,8 @@ class FusedAdam(torch.optim.Optimizer):
                     expect.append((p, gptr))
                     first += (n + _CHUNK - 1) // _CHUNK
             raw = bytearray(b"".join(struct.pack("<QQQQqq", *e) for e in entries))
+            if self._average is not None:
+                raw += self._average._shadow_pointers([p for p, _ in expect])       # once per layout, like the table
             dev = expect[0][0].device
             table = torch.frombuffer(raw, dtype=torch.uint8).to(dev)          # once per layout: a blocking copy is fine
             self._static = (sync.layout_version, table, len(entries), first, expect, flats)
@@ -285,6 +299,9 @@ class FusedAdam(torch.optim.Optimizer):
         self._adopt(scaler)
         lib = _lib.load()
         launched = False
+        avg = self._average
+        if avg is not None:
+            avg._check_live()
         work = self._tables()
         unscaled = scaler is not None and id(self) in scaler._unscaled      # LossScaler.unscale_ has run on these gradients
         if self.max_grad_norm is not None or unscaled or any(g["weight_decay"] != 0 for g in self.param_groups):
@@ -300,7 +317,15 @@ class FusedAdam(torch.optim.Optimizer):
         for group, (table, count, chunks, keep) in work:
             lr, (b1, b2), eps = float(group["lr"]), group["betas"], float(group["eps"])
             with torch.cuda.device(table.device):
-                if scaler is not None:
+                if avg is not None and scaler is not None:
+                    _lib.check(lib.zsv_adam_multi_scaled_avg(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps,
+                                                             scaler.state_ptr, *self._avg_args(table, count), _stream()),
+                               "zsv_adam_multi_scaled_avg")
+                elif avg is not None:
+                    _lib.check(lib.zsv_adam_multi_avg(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps,
+                                                      self._host_steps + 1, *self._avg_args(table, count), _stream()),
+                               "zsv_adam_multi_avg")
+                elif scaler is not None:
                     _lib.check(lib.zsv_adam_multi_scaled(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps,
                                                          scaler.state_ptr, _stream()), "zsv_adam_multi_scaled")
                 else:
@@ -312,6 +337,8 @@ class FusedAdam(torch.optim.Optimizer):
             launched = True
         del work
         if launched:
+            if avg is not None:
+                avg._after_update(lib, scaler)     # BatchNorm statistics, then n_averaged += !found_inf (before scaler.update())
             if scaler is None:
                 self._host_steps += 1
                 for group in self.param_groups:
@@ -336,6 +363,10 @@ class FusedAdam(torch.optim.Optimizer):
             self._scaler = scaler
         if self._scaler is not None and scaler is not self._scaler:
             raise RuntimeError("FusedAdam: this optimizer is driven by a LossScaler; step through scaler.step(optimizer)")
+
+    def _avg_args(self, table, count):
+        """(shadow-pointer array, averaging state, EMA weight) of a launch: the pointers sit behind the ``count`` descriptors."""
+        return table.data_ptr() + 48 * count, self._average._state_ptr(table.device), self._average._ema_weight
 
     def _tables(self):
         work = []
@@ -398,7 +429,16 @@ class FusedAdam(torch.optim.Optimizer):
             wd, decoupled = float(group["weight_decay"]), int(bool(group["decoupled_weight_decay"]))
             self._check_decay(wd)
             with torch.cuda.device(table.device):
-                if scaler is not None:
+                if self._average is not None and scaler is not None:
+                    _lib.check(lib.zsv_adamw_multi_scaled_avg(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps, wd,
+                                                              decoupled, clip_ptr, state_ptr, int(unscaled),
+                                                              *self._avg_args(table, count), _stream()),
+                               "zsv_adamw_multi_scaled_avg")
+                elif self._average is not None:
+                    _lib.check(lib.zsv_adamw_multi_avg(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps, wd,
+                                                       decoupled, clip_ptr, self._host_steps + 1,
+                                                       *self._avg_args(table, count), _stream()), "zsv_adamw_multi_avg")
+                elif scaler is not None:
                     _lib.check(lib.zsv_adamw_multi_scaled(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps, wd,
                                                           decoupled, clip_ptr, state_ptr, int(unscaled), _stream()),
                                "zsv_adamw_multi_scaled")
@@ -434,3 +474,198 @@ class FusedAdam(torch.optim.Optimizer):
                 if "step" in st:
                     st["step"].fill_(done)
         return super().state_dict()
+
+
+class WeightAverage:
+    """A running average of the weights for evaluation, kept by the optimizer's own launches.
+
+    ``decay`` in ``[0, 1)`` is an exponential moving average (``torch.optim.swa_utils.AveragedModel`` with
+    ``get_ema_multi_avg_fn(decay)``); ``decay=None`` the equal-weight running mean of SWA (``AveragedModel``'s default).  Every
+    parameter of the optimizer's groups gets a shadow, a view of ONE flat fp32 buffer per device initialised to the parameters;
+    from then on each ``optimizer.step()`` -- directly, through ``LossScaler.step`` or inside ``train.train_step`` -- averages
+    once: the first averaged step copies, later ones lerp, a step the scaler skips changes nothing (all decided on the device:
+    ``n_averaged`` is a device counter, and reading it is the only thing here that synchronises).  A parameter that never
+    receives a gradient keeps ``avg == p``.
+
+    With ``model=`` the shadows are named like ``model.state_dict()``, and with ``buffers=True`` the model's floating-point
+    buffers (BatchNorm ``running_mean`` / ``running_var``) are averaged as well, in one more launch per step
+    (``zsv_avg_multi``).  Integer buffers (``num_batches_tracked``) are NOT shadowed and keep their live value under
+    ``applied()`` -- ``AveragedModel(use_buffers=True)`` lerps them with truncation.
+
+    ``applied()`` exchanges live and averaged values in place (``zsv_swap_multi``): no address changes, so cached weight panels,
+    inference engines and captured graphs stay valid and only rebuild their contents.  Data parallel: every rank applies the
+    same update to equal parameters, so the shadows are equal without a collective."""
+
+    def __init__(self, optimizer, decay: Optional[float] = 0.999, model: Optional[torch.nn.Module] = None, buffers: bool = True):
+        if not isinstance(optimizer, FusedAdam):
+            raise TypeError("WeightAverage averages inside optim.FusedAdam's update launch; got " + type(optimizer).__name__)
+        if decay is not None:
+            if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not (0.0 <= decay < 1.0):
+                raise ValueError(f"decay must be None (equal-weight) or a number in [0, 1), not {decay!r}")
+        if optimizer._average is not None:
+            raise RuntimeError("this FusedAdam already has a WeightAverage (one per optimizer)")
+        self._set_decay(decay)
+        self._applied = False
+        own = getattr(model, "module", model) if model is not None else None
+        params = [p for group in optimizer.param_groups for p in group["params"]]
+        if own is not None:
+            names = {id(p): k for k, p in own.named_parameters()}
+            missing = [i for i, p in enumerate(params) if id(p) not in names]
+            if missing:
+                raise ValueError(f"WeightAverage: optimizer parameters {missing} are not parameters of `model`")
+            keys = [names[id(p)] for p in params]
+        else:
+            keys = list(range(len(params)))
+        for p in params:
+            FusedAdam._check_param(p)
+        live = list(zip(keys, params))
+        self._n_params = len(live)
+        if own is not None and buffers:
+            for k, b in own.named_buffers():
+                if not b.is_floating_point():
+                    continue                                # num_batches_tracked: stays live (class docstring)
+                if not b.is_cuda or b.dtype != torch.float32 or not b.is_contiguous():
+                    raise RuntimeError(f"WeightAverage: buffer {k} must be a contiguous fp32 tensor on a HIP device")
+                live.append((k, b))
+        # one flat buffer and one zsv_avg_state {int32 n_averaged} per device; entries: (key, live tensor, shadow view)
+        totals = {}
+        for _, t in live:
+            totals[t.device] = totals.get(t.device, 0) + t.numel()
+        self._flat = {dev: torch.empty(n, dtype=torch.float32, device=dev) for dev, n in totals.items()}
+        self._state = {dev: torch.zeros(1, dtype=torch.int32, device=dev) for dev in totals}
+        self._entries, offsets = [], {dev: 0 for dev in totals}
+        with torch.no_grad():
+            for k, t in live:
+                off, n = offsets[t.device], t.numel()
+                shadow = self._flat[t.device][off:off + n].view_as(t)
+                shadow.copy_(t.detach())
+                offsets[t.device] = off + n
+                self._entries.append((k, t, shadow))
+        self._shadow_of = {id(t): shadow for _, t, shadow in self._entries}
+        self._pair_tables = {}                              # (device, buffers only?) -> (live pointers, table, count, chunks)
+        self.optimizer = optimizer
+        optimizer._average = self
+        optimizer._static = None                            # the bucket table is rebuilt with the shadow pointers behind it
+
+    def _set_decay(self, decay) -> None:
+        self.decay = None if decay is None else float(decay)
+        # zsv_* ema_weight: (float)(1 - decay) -- the double is rounded once, by the call -- or negative for equal-weight
+        self._ema_weight = -1.0 if decay is None else 1.0 - self.decay
+
+    @property
+    def n_averaged(self) -> torch.Tensor:
+        """Optimizer steps averaged so far, a 0-d int32 device tensor (skipped steps do not count)."""
+        return next(iter(self._state.values()))[0]
+
+    def shadows(self) -> dict:
+        """``{key: averaged tensor}``: views of the flat buffer(s), keyed like ``state_dict()['shadows']``."""
+        return {k: shadow for k, _, shadow in self._entries}
+
+    # -- what FusedAdam.step calls ------------------------------------------------------------------
+    def _state_ptr(self, dev) -> int:
+        return self._state[dev].data_ptr()
+
+    def _shadow_pointers(self, params) -> bytes:
+        try:
+            return b"".join(struct.pack("<Q", self._shadow_of[id(p)].data_ptr()) for p in params)
+        except KeyError:
+            raise RuntimeError("WeightAverage: a parameter joined the optimizer after the average was built") from None
+
+    def _check_live(self) -> None:
+        if self._applied:
+            raise RuntimeError("optimizer.step() inside WeightAverage.applied(): the live tensors hold the averaged values")
+
+    def _pair_table(self, dev, buffers_only: bool):
+        """Device table of zsv_pair_tensor {live, shadow, n, first_chunk}; rebuilt only when a live tensor has moved."""
+        rows = [(t, shadow) for _, t, shadow in (self._entries[self._n_params:] if buffers_only else self._entries)
+                if t.device == dev and t.numel()]
+        if not rows:
+            return None
+        ptrs = tuple(t.data_ptr() for t, _ in rows)
+        cached = self._pair_tables.get((dev, buffers_only))
+        if cached is None or cached[0] != ptrs:
+            raw, first = bytearray(), 0
+            for t, shadow in rows:
+                if t.device != shadow.device or t.numel() != shadow.numel() or not t.is_contiguous():
+                    raise RuntimeError("WeightAverage: a shadowed tensor changed its device, size or layout")
+                raw += struct.pack("<QQqq", t.data_ptr(), shadow.data_ptr(), t.numel(), first)
+                first += (t.numel() + _CHUNK - 1) // _CHUNK
+            cached = (ptrs, torch.frombuffer(raw, dtype=torch.uint8).to(dev), len(rows), first)
+            self._pair_tables[(dev, buffers_only)] = cached
+        return cached[1:]
+
+    def _after_update(self, lib, scaler: Optional[LossScaler]) -> None:
+        state_ptr = scaler.state_ptr if scaler is not None else None
+        for dev, state in self._state.items():
+            with torch.cuda.device(dev):
+                built = self._pair_table(dev, True)
+                if built is not None:
+                    table, count, chunks = built
+                    _lib.check(lib.zsv_avg_multi(table.data_ptr(), count, chunks, state.data_ptr(), self._ema_weight, state_ptr,
+                                                 _stream()), "zsv_avg_multi")
+                _lib.check(lib.zsv_avg_advance(state.data_ptr(), state_ptr, _stream()), "zsv_avg_advance")
+
+    # -- evaluation on the averaged weights ---------------------------------------------------------
+    def _swap(self) -> None:
+        lib = _lib.load()
+        for dev in self._state:
+            built = self._pair_table(dev, False)
+            if built is None:
+                continue
+            table, count, chunks = built
+            with torch.cuda.device(dev):
+                _lib.check(lib.zsv_swap_multi(table.data_ptr(), count, chunks, _stream()), "zsv_swap_multi")
+        _lib.note_raw_write()                               # parameters and buffers rewritten through raw pointers
+
+    @contextlib.contextmanager
+    def applied(self):
+        """Inside the context the live tensors hold the averaged values (and the shadows the live ones); exit restores
+        both bit for bit.  Not re-entrant, and ``optimizer.step()`` inside it raises.  Meant for evaluation: a training-mode
+        forward inside the context would update the AVERAGED BatchNorm statistics."""
+        if self._applied:
+            raise RuntimeError("WeightAverage.applied() is already active (it cannot be nested)")
+        self._swap()
+        self._applied = True
+        try:
+            yield self
+        finally:
+            self._swap()
+            self._applied = False
+
+    # -- state ------------------------------------------------------------------------------------------
+    def averaged_state_dict(self, model: torch.nn.Module) -> dict:
+        """``model.state_dict()`` (no prefix) with every shadowed tensor replaced by its average; the rest is live."""
+        if self._applied:
+            raise RuntimeError("WeightAverage.averaged_state_dict() inside applied(): live and averaged values are exchanged")
+        own = getattr(model, "module", model)
+        return {k: self._shadow_of.get(id(v), v).detach() for k, v in own.state_dict(keep_vars=True).items()}
+
+    def state_dict(self) -> dict:
+        """``{"n_averaged", "decay", "shadows"}``; the shadows (host copies) are keyed by ``state_dict`` name when the
+        average was built with ``model=``, by position in the optimizer otherwise.  One host sync."""
+        if self._applied:
+            raise RuntimeError("WeightAverage.state_dict() inside applied(): live and averaged values are exchanged")
+        return {"n_averaged": int(self.n_averaged.item()), "decay": self.decay,
+                "shadows": {k: shadow.detach().cpu().clone() for k, _, shadow in self._entries}}
+
+    def load_state_dict(self, state: dict) -> None:
+        """Resume: the shadows are copied back into the flat buffer(s), the counter is uploaded, ``decay`` is the saved one."""
+        if self._applied:
+            raise RuntimeError("WeightAverage.load_state_dict() inside applied()")
+        decay = state["decay"]
+        if decay is not None and not (0.0 <= float(decay) < 1.0):
+            raise ValueError(f"decay must be None or a number in [0, 1), not {decay!r}")
+        saved = state["shadows"]
+        own = [k for k, _, _ in self._entries]
+        if set(saved) != set(own):
+            raise KeyError(f"WeightAverage.load_state_dict: missing {sorted(set(own) - set(saved), key=str)}, "
+                           f"unexpected {sorted(set(saved) - set(own), key=str)}")
+        with torch.no_grad():
+            for k, _, shadow in self._entries:
+                if tuple(saved[k].shape) != tuple(shadow.shape):
+                    raise ValueError(f"WeightAverage.load_state_dict: shape of {k!r} is {tuple(saved[k].shape)}, "
+                                     f"expected {tuple(shadow.shape)}")
+                shadow.copy_(saved[k])
+            for st in self._state.values():
+                st.fill_(int(state["n_averaged"]))
+        self._set_decay(decay)

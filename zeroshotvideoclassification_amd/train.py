@@ -31,10 +31,14 @@ from . import _lib, ops
 _PREFIX = "module."       # nn.DataParallel's prefix in saved checkpoints (main.py:116,126,363)
 
 
-def load_weights(model: torch.nn.Module, path: str) -> int:
+def load_weights(model: torch.nn.Module, path: str, key: str = "state_dict") -> int:
     """main.py:114-124: strip the ``module.`` prefix, keep the keys the model has, load the rest
-    from the model itself.  Returns the number of tensors taken from the checkpoint."""
-    weights = torch.load(path, map_location="cpu", weights_only=False)["state_dict"]
+    from the model itself.  Returns the number of tensors taken from the checkpoint.  ``key="state_dict_avg"`` loads the
+    averaged weights ``save_checkpoint(average=)`` stored next to the live ones."""
+    checkpoint = torch.load(path, map_location="cpu", weights_only=False)
+    if key not in checkpoint:
+        raise KeyError(f"{path} has no {key!r}: it holds {sorted(checkpoint, key=str)}")
+    weights = checkpoint[key]
     own = getattr(model, "module", model)
     model_dict = own.state_dict()
     j = len(_PREFIX)
@@ -45,11 +49,16 @@ def load_weights(model: torch.nn.Module, path: str) -> int:
     return len(weights)
 
 
-def save_checkpoint(model: torch.nn.Module, path: str, opt=None, accuracy: float = 0.0) -> None:
-    """main.py:361-365: the saved keys carry the ``module.`` prefix whether or not the model is wrapped."""
+def save_checkpoint(model: torch.nn.Module, path: str, opt=None, accuracy: float = 0.0, average=None) -> None:
+    """main.py:361-365: the saved keys carry the ``module.`` prefix whether or not the model is wrapped.  ``average``
+    (``optim.WeightAverage``) adds ``"state_dict_avg"``: a complete state dict of the same format with the averaged tensors
+    substituted and everything else live.  The reference's loader reads only ``['state_dict']`` and is unaffected."""
     own = getattr(model, "module", model)
     state = {_PREFIX + k: v.detach().cpu() for k, v in own.state_dict().items()}
-    torch.save({"state_dict": state, "opt": opt, "accuracy": accuracy}, path)
+    checkpoint = {"state_dict": state, "opt": opt, "accuracy": accuracy}
+    if average is not None:
+        checkpoint["state_dict_avg"] = {_PREFIX + k: v.cpu() for k, v in average.averaged_state_dict(own).items()}
+    torch.save(checkpoint, path)
 
 
 def embed(model: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
@@ -267,7 +276,7 @@ def _gather_rows(t: torch.Tensor, group) -> torch.Tensor:
 def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], class_embed: torch.Tensor,
              device: Optional[torch.device] = None, splits: int = 10, dtype: Optional[torch.dtype] = None,
              group=None, sharded: Optional[bool] = None, local_batches: bool = False,
-             sync_state: bool = True) -> dict:
+             sync_state: bool = True, average=None) -> dict:
     """main.py:224-313 for one test set.  ``batches`` yields ``(X, labels, Z, ...)``; samples with
     label -1 (failed loads, auxiliary_dataset.py:502-505) are dropped like main.py:246-248.
     ``dtype=torch.bfloat16`` runs the forward on the bf16 engine (``inference.Bf16Engine``, the
@@ -286,7 +295,14 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], 
     buffers (``sync_state``; one flat broadcast per dtype): all samples are scored by ONE model -- the one rank 0
     would checkpoint (main.py:361-365).  NOTE: this overwrites the other ranks' BatchNorm running statistics, mid-training
     too -- what ``nn.DataParallel`` does implicitly every forward.  ``sync_state=False`` skips the broadcast when the caller knows the
-    replicas are identical (e.g. right after ``load_weights`` on every rank)."""
+    replicas are identical (e.g. right after ``load_weights`` on every rank).
+
+    ``average`` (``optim.WeightAverage``): the evaluation runs on the averaged weights, swapped into the live tensors for
+    its duration (``with average.applied():``)."""
+    if average is not None:
+        with average.applied():
+            return evaluate(model, batches, class_embed, device=device, splits=splits, dtype=dtype, group=group, sharded=sharded,
+                            local_batches=local_batches, sync_state=sync_state)
     import torch.distributed as dist
     if sharded is None:
         sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
