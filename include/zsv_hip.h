@@ -395,6 +395,26 @@ int zsv_clip_transform(const uint8_t* frames_u8, int32_t N, int32_t T, int32_t H
                        int32_t Hres, int32_t Wres, float inv_scale, int32_t crop,
                        const int32_t* crop_flip_params_device, float* out, void* stream);
 
+/* ---- camera-motion clips from still images (main.py --dataset sun2both) ---------------------- */
+/* ImageDataset.extract_camera_motion (auxiliary/auxiliary_stillimages.py:130-137) on the device: every frame is
+ * img[top:top+side, left:left+side] through crop_transform (:56-62) = PIL's antialiased bilinear uint8 resample to
+ * crop x crop (two integer passes, horizontal first, 22-bit coefficients), then ((u8/255) - mean_c) / std_c in fp32
+ * with the Kinetics mean / std of :60-61.  Bit-identical to the reference, not a tolerance.
+ * image_table_device: B x {pointer, H, W} int64 on the device, each image (H, W, 3) uint8 contiguous, sizes may
+ * differ; frame_table_device: B*n_clips*T x {top, left, side} int32 on the device, frame f of image b lands at
+ * clip f / T, time f % T (the reshape + transpose(1, 2) of :137); out: (B, n_clips, 3, T, crop, crop) fp32.
+ * max_side = the largest side in the frame table; crop <= max_side <= 8 * crop (17 taps per axis), otherwise
+ * ZSV_E_BAD_SHAPE before any launch.  The frame table itself lives on the device: the caller checks that every
+ * window lies inside its image and crop <= side <= max_side (preprocess.StillImageClips does); a frame that breaks
+ * this is never read and its output becomes NaN. */
+int zsv_still_image_clips(const int64_t* image_table_device, const int32_t* frame_table_device, int32_t B,
+                          int32_t n_clips, int32_t T, int32_t crop, int32_t max_side, float* out, void* stream);
+/* The integer coefficient table of one side -> crop resample, from the device code zsv_still_image_clips uses
+ * (PIL's precompute_coeffs + normalize_coeffs_8bpc behind Resize at auxiliary_stillimages.py:58; computed in
+ * fp64 without contraction).  coeffs: [crop][ksize] int32 with ksize = 2 * ceil(side / crop) + 1, zero past each
+ * window; bounds: [crop][2] int32 = (first, count).  crop <= side <= 8 * crop. */
+int zsv_resample_coeffs(int32_t side, int32_t crop, int32_t* coeffs, int32_t* bounds, void* stream);
+
 /* The same update for every parameter tensor of a model in ONE launch (the reference's
  * optimizer.step(), main.py:200, is ~113 tensors).  `table_device` is a device array of `count`
  * descriptors sorted by first_chunk; a chunk is 4096 elements; first_chunk = running sum of

@@ -8,6 +8,11 @@ reference transforms one ``(T, H, W, 3)`` uint8 clip on a CPU worker and ships f
 HIP kernel writing the ``(N, 3, T, 112, 112)`` model input.  Random crop / flip parameters are
 drawn on the host with Python's ``random`` exactly like ``RandomCrop.get_params`` /
 ``RandomHorizontalFlip`` (transforms.py:137-147,192-195), one draw per clip.
+
+``StillImageClips`` is the same move for the still-image source (``main.py --dataset sun2both``,
+``auxiliary/auxiliary_stillimages.py:92-138``): the uint8 images are uploaded once and one HIP launch
+crops, resamples (PIL's antialiased bilinear, bit for bit) and normalises every frame of every
+camera-motion clip of the batch.
 """
 from __future__ import annotations
 
@@ -15,6 +20,7 @@ import random
 from ctypes import c_void_p
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -83,3 +89,120 @@ class ClipTransform:
 
 def get_transform(is_validation, crop_size=112):
     return ClipTransform(is_validation, crop_size)
+
+
+# ---- still images (auxiliary/auxiliary_stillimages.py) ---------------------------------------------------------------
+MAX_SIDE_RATIO = 8          # side / crop the kernel supports (17 taps per axis); the reference never exceeds 512 / 112
+
+
+def prepare_still_image(img: np.ndarray) -> np.ndarray:
+    """The channel handling of ``extract_camera_motion`` (auxiliary_stillimages.py:105-112) that has a defined
+    result: a grey ``(H, W)`` or one-channel ``(H, W, 1)`` image is repeated to three channels, RGBA loses its
+    alpha, RGB passes through; anything else raises (the reference's two-channel branch at :108-109 cannot run).
+    Returns a contiguous ``(H, W, 3)`` uint8 array.
+
+    NOT done here: the rescale of :93-103 (short side below 172 is enlarged by an integer factor, above 512 reduced
+    to 512, through ``skimage.transform.resize``).  That is loader work next to the image decode; do it before this
+    call for images outside 172 ... 512."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8:
+        raise ValueError(f"expected a uint8 image, got {img.dtype}")
+    if img.ndim == 2:
+        img = img[:, :, None]
+    if img.ndim != 3 or img.shape[2] not in (1, 3, 4):
+        raise ValueError(f"expected a (H, W), (H, W, 1), (H, W, 3) or (H, W, 4) image, got {img.shape}")
+    if img.shape[2] == 1:
+        img = np.repeat(img, 3, axis=2)
+    return np.ascontiguousarray(img[:, :, :3])
+
+
+def _draw_window(h: int, w: int, crop: int):
+    top = np.random.randint(0, max(h - crop, 1))
+    left = np.random.randint(0, max(w - crop, 1))
+    side = np.random.randint(crop, max(min(h - top, w - left), crop + 1))
+    return top, left, side
+
+
+def camera_motion_trajectory(h: int, w: int, crop: int, frames: int) -> np.ndarray:
+    """The window trajectory of ``extract_camera_motion`` (auxiliary_stillimages.py:118-127): a start and an end
+    window, each drawn as top, left, side with ``np.random.randint`` (six draws, in the reference's order), joined
+    by ``np.linspace(...).astype(int)``.  Under the same ``np.random.seed`` this is the reference's trajectory.
+    Returns ``(frames, 3)`` int rows ``(top, left, side)``."""
+    start, end = _draw_window(h, w, crop), _draw_window(h, w, crop)
+    return np.ascontiguousarray(np.stack([np.linspace(a, b, frames).astype(int) for a, b in zip(start, end)]).T)
+
+
+class StillImageClips:
+    """``ImageDataset.extract_camera_motion`` for a batch of images in one HIP launch
+    (``ImageDataset(..., clip_len=8, n_clips=1, crop_size=112)``, auxiliary_stillimages.py:33-34)."""
+
+    def __init__(self, clip_len: int = 8, n_clips: int = 1, crop_size: int = 112):
+        self.clip_len, self.n_clips, self.crop_size = int(clip_len), int(n_clips), int(crop_size)
+        if self.clip_len <= 0 or self.n_clips <= 0 or self.crop_size <= 0:
+            raise ValueError("clip_len, n_clips and crop_size must be positive")
+
+    def __call__(self, images: Sequence[torch.Tensor], trajectories: Optional[Sequence] = None) -> torch.Tensor:
+        """``images``: a sequence of ``(H, W, 3)`` uint8 tensors on one HIP device (``prepare_still_image`` output,
+        sizes may differ).  ``trajectories``: one ``(n_clips * clip_len, 3)`` int array of ``(top, left, side)`` per
+        image; drawn with ``camera_motion_trajectory`` (``np.random``) in image order when not given.
+        Returns ``(B, n_clips, 3, clip_len, crop, crop)`` fp32, the input of ``Model.forward``."""
+        crop, frames = self.crop_size, self.n_clips * self.clip_len
+        images = list(images)
+        if not images:
+            raise RuntimeError("expected at least one image")
+        for img in images:
+            if not isinstance(img, torch.Tensor) or img.dim() != 3 or img.shape[-1] != 3 or img.dtype != torch.uint8:
+                raise RuntimeError("expected (H, W, 3) uint8 images")
+            if not img.is_cuda:
+                raise RuntimeError("StillImageClips runs on an MI355X HIP device only (no CPU fallback; "
+                                   "the CPU restatement lives in tests/still_image_oracle.py)")
+            if img.device != images[0].device:
+                raise RuntimeError("all images must live on one device")
+        if trajectories is None:
+            trajectories = [camera_motion_trajectory(int(img.shape[0]), int(img.shape[1]), crop, frames) for img in images]
+        if len(trajectories) != len(images):
+            raise RuntimeError("one trajectory per image expected")
+        table = np.empty((len(images), frames, 3), dtype=np.int32)
+        for b, (img, traj) in enumerate(zip(images, trajectories)):
+            traj = np.asarray(traj)
+            if traj.shape != (frames, 3) or traj.dtype.kind not in "iu":
+                raise RuntimeError(f"expected an integer ({frames}, 3) trajectory of (top, left, side) per image")
+            top, left, side = traj[:, 0], traj[:, 1], traj[:, 2]
+            if (side < crop).any():
+                raise RuntimeError("window side smaller than the crop")
+            if (side > MAX_SIDE_RATIO * crop).any():
+                raise RuntimeError(f"window side larger than {MAX_SIDE_RATIO} x the crop")
+            if (top < 0).any() or (left < 0).any() or (top + side > img.shape[0]).any() or (left + side > img.shape[1]).any():
+                raise RuntimeError("window outside the image")
+            table[b] = traj
+        device = images[0].device
+        images = [img.contiguous() for img in images]            # (a copy made here is freed in stream order, after the launch)
+        itab = torch.tensor([[img.data_ptr(), img.shape[0], img.shape[1]] for img in images], dtype=torch.int64)
+        # pinned + non_blocking: a pageable upload would drain the stream every call (the host could no longer run ahead)
+        itab = itab.pin_memory().to(device, non_blocking=True)
+        ftab = torch.from_numpy(table).pin_memory().to(device, non_blocking=True)
+        out = torch.empty((len(images), self.n_clips, 3, self.clip_len, crop, crop), dtype=torch.float32, device=device)
+        with torch.cuda.device(device):
+            _lib.check(_lib.load().zsv_still_image_clips(itab.data_ptr(), ftab.data_ptr(), len(images), self.n_clips, self.clip_len,
+                                                         crop, int(table[:, :, 2].max()), out.data_ptr(),
+                                                         c_void_p(torch.cuda.current_stream().cuda_stream)),
+                       "zsv_still_image_clips")
+        return out
+
+
+def resample_coeffs(side: int, crop: int, device="cuda"):
+    """The integer tables of one ``side -> crop`` resample as the kernel derives them (``zsv_resample_coeffs``):
+    ``(coeffs (crop, ksize) int32, bounds (crop, 2) int32 = (first, count))`` on ``device``."""
+    side, crop = int(side), int(crop)
+    if crop <= 0 or side < crop or side > MAX_SIDE_RATIO * crop:
+        raise RuntimeError(f"expected crop <= side <= {MAX_SIDE_RATIO} x crop")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("resample_coeffs runs on an MI355X HIP device only (no CPU fallback)")
+    ksize = 2 * -(-side // crop) + 1
+    coeffs = torch.empty((crop, ksize), dtype=torch.int32, device=device)
+    bounds = torch.empty((crop, 2), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().zsv_resample_coeffs(side, crop, coeffs.data_ptr(), bounds.data_ptr(),
+                                                   c_void_p(torch.cuda.current_stream().cuda_stream)), "zsv_resample_coeffs")
+    return coeffs, bounds
