@@ -318,6 +318,19 @@ int zsv_conv3d_fp8_fwd(const zsv_conv_desc* d, const void* x, const void* blob, 
                        void* stream);
 /* [N][S][Cp] e4m3 -> (N, C) fp32 mean over the S voxels (resnet.py:251-254 avgpool + flatten). */
 int zsv_meanpool_fp8(const void* x, int32_t N, int32_t S, int32_t C, float* out, void* stream);
+/* network.C3D in e4m3 (inference.Fp8EngineC3D).  C3D has no normalisation, so layer l stores true / a_l with one
+ * static power-of-two scale a_l per layer taken from calibration clips; the convolutions above do the arithmetic unchanged
+ * (pack with scale[m] = a_{l-1} / a_l and shift[m] = bias[m] / a_l).
+ * zsv_maxpool3d_fp8: nn.MaxPool3d with kernel == stride (network.py:148-163: C3D's five pools) on channels-last e4m3
+ *   [N][T][H][W][Cp], Cp = zsv_fp8_channel_pitch(C); the rules of zsv_maxpool3d_bf16 (-inf padding, 2 * pad <= kernel).  The
+ *   codes are compared as sign-magnitude integers: the result is exact (one of the inputs), pad channels are written as zero;
+ *   what comes out for the two NaN codes (which the saturating epilogue never writes) is unspecified.
+ * zsv_absmax_bf16: *amax = max(*amax, max_i |x_i|) over `count` bf16 values (the calibration pass over network.py:147-162's
+ *   relu(conv(x)) outputs on the bf16 engine): one read, no temporary, no host synchronisation; *amax is a device scalar >= 0
+ *   that several calls fold into (integer maximum of the bit patterns: deterministic); inf / NaN inputs give inf / NaN. */
+int zsv_maxpool3d_fp8(const void* x, int32_t N, int32_t C, int32_t Ti, int32_t Hi, int32_t Wi, int32_t kT, int32_t kH, int32_t kW,
+                      int32_t pT, int32_t pH, int32_t pW, int32_t To, int32_t Ho, int32_t Wo, void* y, void* stream);
+int zsv_absmax_bf16(const void* x, int64_t count, float* amax, void* stream);
 
 /* ---- bf16 TRAINING step: the reference's mixed-precision step (main.py:172 `with autocast():`, main.py:137,195-203
  * GradScaler) on channels-last bf16 activations [R = N*T*H*W][Cp] (the layout of the bf16 convolution above).  Under

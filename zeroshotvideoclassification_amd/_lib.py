@@ -93,6 +93,8 @@ SIGNATURES = {
     "zsv_conv3d_fp8_pack": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "zsv_conv3d_fp8_fwd": (c_int, [POINTER(ConvDesc), _P, _P, _P, c_int, _P, _P]),
     "zsv_meanpool_fp8": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P]),
+    "zsv_maxpool3d_fp8": (c_int, [_P] + [c_int32] * 14 + [_P, _P]),
+    "zsv_absmax_bf16": (c_int, [_P, c_int64, _P, _P]),
     "zsv_bn_cl_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "zsv_bn_cl_fwd_train": (c_int, [_P, _P, c_int64, c_int32, _P, _P, _P, _P, c_float, c_float, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "zsv_bn_cl_fwd_train_stats": (c_int, [_P, _P, c_int64, c_int32, _P, _P, _P, _P, c_float, c_float, c_int, _P, _P, _P, _P, _P, c_int32, _P,

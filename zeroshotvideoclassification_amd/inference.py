@@ -1,6 +1,7 @@
 """bf16 evaluation engine: the reference's eval loop body (main.py:224-252, BASELINE config 5)
 with the VideoResNet trunk run in bf16 on ``zsv_conv3d_bf16_fwd``; ``Fp8Engine`` is the same walk in
-OCP e4m3 (``float8_e4m3fn``) on ``zsv_conv3d_fp8_fwd``.
+OCP e4m3 (``float8_e4m3fn``) on ``zsv_conv3d_fp8_fwd``.  ``Bf16EngineC3D`` / ``Fp8EngineC3D`` are the
+same pair for ``network.C3D``, the e4m3 one with calibrated activation scales (``calibrate_fp8``).
 
 ``Bf16Engine(model)`` walks a ``network.Model`` whose trunk is a ``resnet.VideoResNet``
 (R(2+1)D-18 / R3D-18 / MC3-18), folds every eval-mode ``BatchNorm3d`` into the convolution in
@@ -16,6 +17,7 @@ weights change.  There is no CPU fallback.
 """
 from __future__ import annotations
 
+import math
 from ctypes import byref
 from functools import lru_cache, partial
 from typing import List, Optional, Tuple
@@ -37,6 +39,7 @@ class _Format:
         self.name, self.dtype, self.label, self.clip = name, dtype, label, clip or self
         self.conv_name, self.meanpool_name = f"conv_{name}", f"meanpool_{name}"
         self.pitch, self.meanpool = f"zsv_{name}_channel_pitch", f"zsv_meanpool_{name}"
+        self.maxpool_name, self.maxpool = f"maxpool3d_{name}", f"zsv_maxpool3d_{name}"
         self.blob_bytes, self.pack, self.fwd = (f"zsv_conv3d_{name}_{f}" for f in ("blob_bytes", "pack", "fwd"))
 
 
@@ -118,17 +121,29 @@ pack_conv, conv_bf16, meanpool_bf16, channel_pitch = (partial(f, BF16) for f in 
 pack_conv_fp8, conv_fp8, meanpool_fp8, fp8_channel_pitch = (partial(f, E4M3) for f in (_pack, _conv, _meanpool, _pitch))
 
 
-def maxpool3d_bf16(x: torch.Tensor, channels: int, kernel, padding) -> torch.Tensor:
-    """nn.MaxPool3d(kernel, stride = kernel, padding) on [N][T][H][W][Cp] bf16 (network.py:148-163)."""
-    _check(x, BF16, "maxpool3d_bf16", "input")
+def _maxpool3d(fmt: _Format, x: torch.Tensor, channels: int, kernel, padding) -> torch.Tensor:
+    """nn.MaxPool3d(kernel, stride = kernel, padding) on [N][T][H][W][Cp] in ``fmt`` (network.py:148-163)."""
+    _check(x, fmt, fmt.maxpool_name, "input")
     n, t, h, w, cp = x.shape
     kt, kh, kw = (int(v) for v in kernel)
     pt, ph, pw = (int(v) for v in padding)
     to, ho, wo = (t + 2 * pt - kt) // kt + 1, (h + 2 * ph - kh) // kh + 1, (w + 2 * pw - kw) // kw + 1
-    y = torch.empty((n, to, ho, wo, cp), dtype=torch.bfloat16, device=x.device)
-    _lib.check(_lib.load().zsv_maxpool3d_bf16(x.data_ptr(), n, channels, t, h, w, kt, kh, kw, pt, ph, pw, to, ho, wo, y.data_ptr(),
-                                              ops._stream()), "zsv_maxpool3d_bf16")
+    y = torch.empty((n, to, ho, wo, cp), dtype=fmt.dtype, device=x.device)
+    _lib.check(getattr(_lib.load(), fmt.maxpool)(x.data_ptr(), n, channels, t, h, w, kt, kh, kw, pt, ph, pw, to, ho, wo, y.data_ptr(),
+                                                 ops._stream()), fmt.maxpool)
     return y
+
+
+maxpool3d_bf16, maxpool3d_fp8 = partial(_maxpool3d, BF16), partial(_maxpool3d, E4M3)      # (x, channels, kernel, padding)
+
+
+def absmax_bf16(x: torch.Tensor, amax: torch.Tensor) -> None:
+    """``amax[0] = max(amax[0], max |x|)`` over a contiguous bf16 tensor, on the device: one read, no host synchronisation.
+    ``amax`` is one fp32 element >= 0 on the same device (a slot of a larger tensor will do); calls fold."""
+    _check(x, BF16, "absmax_bf16", "input")
+    if not amax.is_cuda or amax.dtype != torch.float32 or amax.numel() != 1:
+        raise RuntimeError("absmax_bf16 amax: one fp32 element on the MI355X HIP device expected")
+    _lib.check(_lib.load().zsv_absmax_bf16(x.data_ptr(), x.numel(), amax.data_ptr(), ops._stream()), "zsv_absmax_bf16")
 
 
 def fold_bn(bn: Optional[nn.BatchNorm3d], conv: nn.Conv3d) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
@@ -349,22 +364,38 @@ class Bf16EngineC3D:
     shift), the pools are ``zsv_maxpool3d_bf16``; fc6 (+ ReLU), the clip mean, the regressor and the normalisation stay fp32
     (dropout is the identity in eval mode).  Same contract as the module: ``(bs, nc, 3, T, H, W) fp32 -> (bs, 300)``."""
 
-    def __init__(self, model: nn.Module):
-        self.model = _device_model(model, "Bf16EngineC3D", c3d=True)
-        # network.py:147-162: relu(conv(x)), bias in the epilogue
-        self.ops = [(_ConvOp(conv, None, True), pool) for conv, pool in c3d_layers(self.model, "Bf16EngineC3D")]
+    _fmt = BF16
 
-    @torch.no_grad()
-    def features(self, clips: torch.Tensor) -> torch.Tensor:
-        """(N, 3, T, H, W) fp32 -> (N, 8192) fp32 in the (C, T, H, W) order of ``view(-1, 8192)`` (network.py:165)."""
+    def __init__(self, model: nn.Module):
+        who = type(self).__name__
+        self.model = _device_model(model, who, c3d=True)
+        # network.py:147-162: relu(conv(x)), bias in the epilogue
+        self.ops = [(_ConvOp(conv, None, True, self._fmt), pool) for conv, pool in c3d_layers(self.model, who)]
+
+    def _walk(self, clips: torch.Tensor, visit=None) -> torch.Tensor:
+        """The eight layers and five pools on (N, 3, T, H, W) fp32 clips; ``visit(l, y)`` sees layer l's output before its pool."""
         x, wo = self.ops[0][0].clip_input(clips)
-        for op, pool in self.ops:
+        for l, (op, pool) in enumerate(self.ops):
             x = op(x, wo=wo)
             wo = None
+            if visit is not None:
+                visit(l, x)
             if pool is not None:
-                x = maxpool3d_bf16(x, op.cout, pool[0], pool[1])
+                x = _maxpool3d(self._fmt, x, op.cout, pool[0], pool[1])
+        return x
+
+    def _values(self, x: torch.Tensor) -> torch.Tensor:
+        return x.float()
+
+    @torch.no_grad()
+    def features(self, clips: torch.Tensor, taps: Optional[list] = None) -> torch.Tensor:
+        """(N, 3, T, H, W) fp32 -> (N, 8192) fp32 in the (C, T, H, W) order of ``view(-1, 8192)`` (network.py:165).  With a list
+        as ``taps`` every layer's output before its pool (channels-last, in the engine's format) is appended to it."""
+        x = self._walk(clips, None if taps is None else (lambda l, y: taps.append(y)))
         c = self.ops[-1][0].cout
-        return x[..., :c].permute(0, 4, 1, 2, 3).reshape(clips.shape[0], -1).float()
+        if x.dtype == FP8:
+            x = x.view(torch.uint8)                 # the codes as bytes: decoded by ``_values`` behind the strided copy
+        return self._values(x[..., :c].permute(0, 4, 1, 2, 3).reshape(clips.shape[0], -1))
 
     @torch.no_grad()
     def __call__(self, x: torch.Tensor):
@@ -376,6 +407,113 @@ class Bf16EngineC3D:
         a = m.fc6(a.contiguous(), relu=True)                           # network.py:166 (dropout: identity in eval mode)
         a = a.reshape(bs, nc, -1).mean(1).reshape(bs, -1)              # network.py:174-176
         return F.normalize(m.regressor(a), dim=-1)                     # network.py:178-179
+
+
+# ---- network.C3D in e4m3: one static power-of-two activation scale per layer -------------------------------
+_NO_FP8_SCALES = ("C3D has no fp8 (float8_e4m3fn) engine until its eight activation scales are known (it has no BatchNorm to bound "
+                  "its activations): call inference.calibrate_fp8(model, clips) first, or inference.set_fp8_scales(model, scales) "
+                  "with scales kept from an earlier calibration")
+_SCALES_ATTR = "_zsv_fp8_scales"
+
+
+def fp8_scale(amax: float, headroom: float = 4.0) -> float:
+    """The power-of-two scale a layer whose largest calibrated |activation| is ``amax`` is stored with:
+    ``2 ** ceil(log2(amax * headroom / 448))``, so the stored ``amax / scale`` is at most ``448 / headroom`` (112 by default:
+    two binades below saturation, thirteen normal binades below that).  ``amax == 0`` gives 1."""
+    amax, headroom = float(amax), float(headroom)
+    if not math.isfinite(amax) or amax < 0.0:
+        raise ValueError(f"fp8_scale: amax must be finite and >= 0, got {amax}")
+    if not math.isfinite(headroom) or headroom <= 0.0:
+        raise ValueError(f"fp8_scale: headroom must be finite and > 0, got {headroom}")
+    v = amax * headroom / 448.0
+    if v == 0.0:
+        return 1.0
+    m, e = math.frexp(v)                        # v = m * 2**e with 0.5 <= m < 1: ceil(log2(v)) without a rounded logarithm
+    return math.ldexp(1.0, e - 1 if m == 0.5 else e)
+
+
+def _c3d(model: nn.Module, who: str) -> nn.Module:
+    from . import network
+    model = getattr(model, "module", model)
+    if not isinstance(model, network.C3D):
+        raise RuntimeError(f"{who} supports network.C3D")
+    return model
+
+
+def _checked_scales(scales) -> Tuple[float, ...]:
+    try:
+        out = tuple(float(v) for v in scales)
+    except TypeError:
+        raise ValueError(f"fp8 scales: eight finite positive numbers expected, got {scales!r}") from None
+    if len(out) != 8 or not all(math.isfinite(v) and v > 0.0 for v in out):
+        raise ValueError(f"fp8 scales: eight finite positive numbers expected, got {out}")
+    return out
+
+
+def set_fp8_scales(model: nn.Module, scales) -> None:
+    """Keep the eight activation scales of ``calibrate_fp8`` on the (unwrapped) ``network.C3D``: in its ``__dict__``, not in its
+    ``state_dict`` -- the reference's checkpoint format stays as it is; carry them next to a checkpoint (INTEGRATION)."""
+    _c3d(model, "set_fp8_scales").__dict__[_SCALES_ATTR] = _checked_scales(scales)
+
+
+def fp8_scales(model: nn.Module) -> Optional[Tuple[float, ...]]:
+    """The stored activation scales of a ``network.C3D``, or None before ``calibrate_fp8`` / ``set_fp8_scales``."""
+    return _c3d(model, "fp8_scales").__dict__.get(_SCALES_ATTR)
+
+
+@torch.no_grad()
+def calibrate_fp8(model: nn.Module, clips, headroom: float = 4.0) -> Tuple[float, ...]:
+    """Take the eight activation scales of ``Fp8EngineC3D`` from calibration clips -- ``(N, 3, T, H, W)``,
+    ``(bs, nc, 3, T, H, W)`` or an iterable of such -- store them on the model (``set_fp8_scales``) and return them.  The clips
+    run through the bf16 engine's operators; each ``relu(conv + bias)`` output is read once more by ``zsv_absmax_bf16`` into its
+    slot of one 8-float device tensor, which the host reads once at the end.  Several batches give the element-wise maximum
+    of their separate calibrations."""
+    own = _device_model(model, "calibrate_fp8", c3d=True)
+    if own.training:
+        raise RuntimeError("calibrate_fp8: the model must be in eval mode")
+    engine = engine_for(own, torch.bfloat16)
+    device = next(own.parameters()).device
+    amax = torch.zeros(8, dtype=torch.float32, device=device)
+    for batch in ([clips] if isinstance(clips, torch.Tensor) else clips):
+        if batch.dim() == 6:
+            batch = batch.reshape(-1, *batch.shape[2:])
+        engine._walk(batch.to(device, torch.float32), lambda l, y: absmax_bf16(y, amax[l:l + 1]))
+    scales = tuple(fp8_scale(v, headroom) for v in amax.tolist())          # (the one host read)
+    set_fp8_scales(own, scales)
+    return scales
+
+
+@lru_cache(maxsize=None)
+def _e4m3_values(device: torch.device) -> torch.Tensor:
+    return torch.arange(256, dtype=torch.uint8).view(FP8).float().to(device)
+
+
+class Fp8EngineC3D(Bf16EngineC3D):
+    """Eval-mode ``network.C3D.forward`` (network.py:147-179) in OCP e4m3: ``Bf16EngineC3D``'s walk and contract with
+    layer l's activation stored as ``true / scales[l]``, one static power of two per layer (``calibrate_fp8``; default: the scales
+    stored on the model).  The convolution kernels are ``Fp8Engine``'s, unchanged: layer l is packed with
+    ``scale = scales[l-1] / scales[l]`` (1 in front of the clip) and ``shift = bias / scales[l]``, and ReLU and the max-pool
+    (``zsv_maxpool3d_fp8``) commute with a positive factor.  The clip convolution keeps bf16 operands and writes e4m3; the
+    (N, 8192) feature is dequantised by ``scales[-1]``; fc6 and everything behind it stay fp32.  Static scales: a clip's
+    embedding does not depend on the other clips of its batch."""
+
+    _fmt = E4M3
+
+    def __init__(self, model: nn.Module, scales=None):
+        scales = fp8_scales(model) if scales is None else _checked_scales(scales)
+        if scales is None:
+            raise RuntimeError(_NO_FP8_SCALES)
+        super().__init__(model)
+        self.scales = scales
+        before = 1.0
+        for (op, _), a in zip(self.ops, scales):
+            op.scale = torch.full((op.cout,), before / a, dtype=torch.float32, device=op.weight.device)
+            if op.shift is not None:
+                op.shift = (op.shift / a).contiguous()
+            before = a
+
+    def _values(self, x: torch.Tensor) -> torch.Tensor:
+        return _e4m3_values(x.device)[x.long()] * self.scales[-1]
 
 
 class _ConvOpF32:
@@ -431,7 +569,8 @@ class Fp32Engine:
 
 def engine_for(model: nn.Module, dtype: torch.dtype = torch.bfloat16, rebuild: bool = False):
     """The model's inference engine for ``dtype`` (bf16: ``Bf16Engine``, fp32: ``Fp32Engine``, ``torch.float8_e4m3fn``:
-    ``Fp8Engine``, VideoResNet trunks only), rebuilt only when a
+    ``Fp8Engine``, or ``Fp8EngineC3D`` for a ``network.C3D`` with stored activation scales -- ``calibrate_fp8``; the scales are
+    part of what the cached engine is keyed on), rebuilt only when a
     trunk parameter or BatchNorm buffer may have been written since it was built, e.g. once per epoch for the
     three test sets of main.py:352-358.  "Written" = the tensors' identity / version counters (torch-side
     writes) AND ``_lib.raw_write_generation()``: the HIP BatchNorm running-statistics update, ``FusedAdam``,
@@ -443,6 +582,11 @@ def engine_for(model: nn.Module, dtype: torch.dtype = torch.bfloat16, rebuild: b
     trunk = own if is_c3d else own.model
     tensors = list(trunk.parameters()) + list(trunk.buffers())
     key = (_lib.raw_write_generation(),) + tuple((id(t), t.data_ptr(), t._version) for t in tensors)
+    if dtype == FP8 and is_c3d:
+        scales = fp8_scales(own)
+        if scales is None:
+            raise RuntimeError(_NO_FP8_SCALES)
+        key += (scales,)
     cache = own.__dict__.setdefault("_zsv_engines", {})
     cached = None if rebuild else cache.get(dtype)
     if cached is None or cached[0] != key:
@@ -452,10 +596,8 @@ def engine_for(model: nn.Module, dtype: torch.dtype = torch.bfloat16, rebuild: b
             raise RuntimeError("no folded fp32 engine for C3D (it has no BatchNorm to fold): use the module's own forward")
         elif dtype == torch.float32:
             engine = Fp32Engine(own)
-        elif dtype == FP8 and is_c3d:
-            raise RuntimeError("C3D has no fp8 (float8_e4m3fn) engine: use bf16 or the module's own forward")
         elif dtype == FP8:
-            engine = Fp8Engine(own)
+            engine = Fp8EngineC3D(own) if is_c3d else Fp8Engine(own)
         else:
             raise RuntimeError(f"no inference engine for {dtype} (fp32 or bf16)")
         cached = (key, engine)

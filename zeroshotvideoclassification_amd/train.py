@@ -282,7 +282,8 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], 
     ``dtype=torch.bfloat16`` runs the forward on the bf16 engine (``inference.Bf16Engine``, the
     reduced-precision eval of BASELINE config 5 / the reference's autocast, main.py:172), ``torch.float32``
     on the folded fp32 engine (``inference.Fp32Engine``), ``torch.float8_e4m3fn`` on the e4m3 engine
-    (``inference.Fp8Engine``, VideoResNet trunks only); default (None): the module's own fp32 forward.
+    (``inference.Fp8Engine``; for a ``network.C3D`` ``inference.Fp8EngineC3D``, which needs the activation scales of
+    ``inference.calibrate_fp8(model, clips)`` stored on the model first); default (None): the module's own fp32 forward.
 
     With ``torch.distributed`` initialised (one process per GPU; ``sharded`` defaults to that) every rank
     iterates the SAME ``batches`` and runs the forward for every ``world``-th one (batch ``i`` belongs to
