@@ -14,7 +14,8 @@ choice depends on the size (``bf16_fwd_impl``'s "small" test, ``wgrad_cl_plan``'
    * forward (``conv_bf16_stats``; C3D: ``conv_bf16`` with bias + ReLU): 2^-8 relative + 1e-3 absolute per element; pad channels
      zero; the statistics partials add up to the fp64 sums of the stored z within 1e-5;
    * input gradient (``Bf16TrainPath._dgrad``): 2^-7 of the range; the positions no tap reaches are exactly zero;
-   * weight gradient (``Bf16TrainPath._wgrad``): 1e-3 of the range;
+   * weight gradient (``Bf16TrainPath._wgrad``): 1e-3 of the range; and, one geometry per kernel mode, EXACT on integer operands
+     (a lost border voxel is four times under that bar at this size);
    * BatchNorm (``bn_cl_fwd_train`` with and without ``conv_stats``, ``bn_cl_bwd`` with and without residual / ReLU / ``fwd_coef``):
      y 2^-7 of the range, mean 1e-5, invstd / running statistics 1e-5 relative, dz 2^-6 of the range, dgamma / dbeta 2e-3 of the range;
    * C3D's max-pools and ``relu_bias_bwd_cl``: exact, bias gradient 1e-5.
@@ -336,6 +337,46 @@ def test_weight_gradient_at_size(name):
     ops.join_wgrad_streams()
     torch.cuda.synchronize()
     assert torch.equal(dw, dw2)
+
+
+# one geometry per ``wgrad_cl_kernel`` mode (0: S1, 1: T1, 2: S2, 3: T2, 4: P1) on exactly representable operands
+GRID_WGRAD = ("S1", "T1", "S2", "T2", "P1")
+
+
+def _grid(shape, seed):
+    """Integers in {-2..2} drawn on the device (fp32 NCDHW); a zero on one of the six faces of a clip's (T, H, W) box becomes +-1,
+    so a lost border voxel cannot hide behind a zero product."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    x = torch.randint(-2, 3, shape, generator=g, device=DEV).float()
+    sign = torch.randint(0, 2, shape, generator=g, device=DEV).float() * 2 - 1
+    face = torch.zeros(tuple(shape[2:]), dtype=torch.bool, device=DEV)
+    face[[0, -1]] = True
+    face[:, [0, -1]] = True
+    face[:, :, [0, -1]] = True
+    return torch.where(face & (x == 0), sign, x)
+
+
+@pytest.mark.parametrize("name", GRID_WGRAD)
+def test_weight_gradient_at_size_is_exact_on_grid_operands(name):
+    """The lost voxel at size.  With N(0,1) operands one dropped or doubled voxel of the 1.1 M moves a weight gradient by 2.4e-4 of
+    its range, under the 1e-3 bar of ``test_weight_gradient_at_size``.  With x, dz in {-2..2} the sum of |terms| of an output is at
+    most 4 x 1 103 872 < 2^24: every partial sum of every slice, in every order, is an fp32 integer, so the fp32 result must EQUAL the
+    float64 one (``tests/bf16_exact_cases.py`` has the argument) -- same channel sample, all 22 clips."""
+    pb = _Problem(name)
+    seed = sum(map(ord, name))
+    pb.x = _grid(tuple(pb.x.shape), seed + 10)
+    pb.xb = amp.ncdhw_to_cl_bf16(pb.x)
+    dz = _grid((N, pb.cout) + pb.out, seed + 11)
+    assert 4 * N * pb.out[0] * pb.out[1] * pb.out[2] < 2 ** 24
+    dw = amp.Bf16TrainPath._wgrad(pb.record(), amp.ncdhw_to_cl_bf16(dz))
+    ops.join_wgrad_streams()
+    torch.cuda.synchronize()
+    ci = _channels(pb.cin, 16, len(pb.name) + 2)
+    co = _channels(pb.cout, 16, len(pb.name) + 3)
+    ref = torch.nn.grad.conv3d_weight(pb.x[:, ci].double().cpu(), (len(co), len(ci)) + pb.k, dz[:, co].double().cpu(), pb.s, pb.p)
+    got = dw[co][:, ci].double().cpu()
+    bad = got != ref
+    assert not bool(bad.any()), (name, int(bad.sum()), bad.nonzero()[:4].tolist(), got[bad][:4].tolist(), ref[bad][:4].tolist())
 
 
 def _kernels_run(fn):
