@@ -403,10 +403,33 @@ int zsv_meanpool_bf16_bwd(const float* dpooled, int32_t N, int32_t S, int32_t C,
  * crop x crop window at (top, left) of the resized frame (:80-97,132-158) and an optional horizontal
  * flip (:188-195), fused into one pass.  frames_u8: (N, T, Hin, Win, 3) uint8;
  * crop_flip_params_device: N x {top, left, flip} int32 on the device; out: (N, 3, T, crop, crop)
- * fp32.  Hres/Wres = floor(Hin*scale), floor(Win*scale); inv_scale = (float)(1/scale). */
+ * fp32.  Hres/Wres = floor(Hin*scale), floor(Win*scale); inv_scale = (float)(1/scale).
+ * Rounding: the source coordinate is fma(inv_scale, dst + 0.5, -0.5) and each of the three blends is
+ * fma(l, b, (1 - l) * a), nothing else fused.  Builds before zsv_clip_transform_batch existed left the fusing to the
+ * compiler, and which product of a blend was fused depended on the loop version a pixel went through: against those
+ * builds an output can differ in its last bit (within the 2e-6 of the reference's chain either way). */
 int zsv_clip_transform(const uint8_t* frames_u8, int32_t N, int32_t T, int32_t Hin, int32_t Win,
                        int32_t Hres, int32_t Wres, float inv_scale, int32_t crop,
                        const int32_t* crop_flip_params_device, float* out, void* stream);
+/* The same chain for a batch of B videos of different frame sizes in one launch: what the reference's loader
+ * (auxiliary/auxiliary_dataset.py:158-208,498-510) does per video on a CPU worker -- native-size decode, ONE crop / flip
+ * draw shared by the n_clips clips of the video, then the (nc*T) -> (nc, 3, T) reshuffle of :506-510 -- before it
+ * collates.  video_table_device: B rows of ZSV_CLIP_ROW int64 on the device, row b =
+ *   [0] device pointer of the video's (n_clips*T, Hin, Win, 3) uint8 frames, contiguous
+ *   [1] Hin  [2] Win  [3] Hres  [4] Wres      (Hres/Wres = floor(Hin*scale), floor(Win*scale), as above)
+ *   [5] top  [6] left                         (0 <= top <= Hres - crop, 0 <= left <= Wres - crop)
+ *   [7] low 32 bits: flip (0 / 1); high 32 bits: the bits of inv_scale = (float)(1/scale)
+ * out: (B, n_clips, 3, T, crop, crop) fp32; frame f of video b lands at clip f / T, time f % T (the
+ * reshape(3, nc, T, c, c).transpose(0, 1) of :510).  Per pixel the arithmetic is zsv_clip_transform's (one device
+ * function serves both kernels): on videos of one size the two agree bit for bit.  Checked before any launch:
+ * ZSV_E_NULL, ZSV_E_BAD_SHAPE for B, n_clips, T, crop <= 0, ZSV_E_TOO_LARGE when out has >= 2^33 elements (the rule
+ * above) or n_clips*T or B exceeds 65535 (grid y / z).  The table lives on the device: the caller checks its rows
+ * (preprocess.VideoClips does).  The kernel clamps its source indices to the frame, so no top / left / flip value
+ * can make a read leave the video's own frames; a row that breaks the contract (null pointer, window outside the
+ * resized frame, inv_scale <= 0) is never read and its frames become NaN. */
+#define ZSV_CLIP_ROW 8
+int zsv_clip_transform_batch(const int64_t* video_table_device, int32_t B, int32_t n_clips, int32_t T,
+                             int32_t crop, float* out, void* stream);
 
 /* ---- camera-motion clips from still images (main.py --dataset sun2both) ---------------------- */
 /* ImageDataset.extract_camera_motion (auxiliary/auxiliary_stillimages.py:130-137) on the device: every frame is

@@ -112,6 +112,7 @@ SIGNATURES = {
     "zsv_ncs_f32_to_cl_bf16": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P]),
     "zsv_meanpool_bf16_bwd": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P]),
     "zsv_clip_transform": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, _P, _P, _P]),
+    "zsv_clip_transform_batch": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "zsv_still_image_clips": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "zsv_resample_coeffs": (c_int, [c_int32, c_int32, _P, _P, _P]),
     "zsv_cosine_topk_workspace_bytes": (c_size_t, [c_int32, c_int32]),

@@ -13,10 +13,16 @@ drawn on the host with Python's ``random`` exactly like ``RandomCrop.get_params`
 ``auxiliary/auxiliary_stillimages.py:92-138``): the uint8 images are uploaded once and one HIP launch
 crops, resamples (PIL's antialiased bilinear, bit for bit) and normalises every frame of every
 camera-motion clip of the batch.
+
+``VideoClips`` / ``get_batch_transform`` is ``ClipTransform`` for what the reference's loader really yields
+(``auxiliary/auxiliary_dataset.py:158-208,498-510``): videos decoded at their native, DIFFERENT frame sizes, one crop / flip
+draw per video shared by its ``n_clips`` clips, collated to ``(bs, nc, 3, T, 112, 112)``.  A device table describes the
+videos, one launch transforms them all; ``VideoClips.stage`` is the loader-side upload (one pinned buffer, one copy).
 """
 from __future__ import annotations
 
 import random
+import warnings
 from ctypes import c_void_p
 from typing import Optional, Sequence
 
@@ -89,6 +95,145 @@ class ClipTransform:
 
 def get_transform(is_validation, crop_size=112):
     return ClipTransform(is_validation, crop_size)
+
+
+# ---- batches of videos of different frame sizes (auxiliary/auxiliary_dataset.py:158-208,498-510) -------------------------
+CLIP_ROW = 8                # int64 words per row of the video table (ZSV_CLIP_ROW, include/zsv_hip.h)
+
+
+def video_table(pointers: Sequence[int], sizes: Sequence[Sequence[int]], params: Sequence[Sequence[int]], size: int) -> np.ndarray:
+    """The ``(B, 8)`` int64 table of ``zsv_clip_transform_batch`` (row format: include/zsv_hip.h), a pure host function:
+    ``[pointer, Hin, Win, Hres, Wres, top, left, flip | bits of float32(1 / scale) << 32]`` per video, with
+    ``Hres, Wres, 1 / scale = resized_hw(Hin, Win, size)``."""
+    table = np.empty((len(pointers), CLIP_ROW), dtype=np.int64)
+    for b, (ptr, (h, w), (top, left, flip)) in enumerate(zip(pointers, sizes, params)):
+        hres, wres, inv_scale = resized_hw(int(h), int(w), size)
+        bits = int(np.float32(inv_scale).view(np.uint32))
+        table[b] = (int(ptr), int(h), int(w), hres, wres, int(top), int(left), (bits << 32) | (1 if flip else 0))
+    return table
+
+
+class VideoClips:
+    """The reference loader's per-video transform (``auxiliary/auxiliary_dataset.py:498-510``) for a whole batch of
+    videos of DIFFERENT frame sizes in one HIP launch: every video gets one crop / flip draw shared by its ``n_clips``
+    clips, and the ``(nc*T) -> (nc, 3, T)`` reshuffle of :506-510 is done by the kernel's store."""
+
+    def __init__(self, is_validation: bool, n_clips: int = 1, clip_len: int = 16, crop_size: int = 112):
+        self.n_clips, self.clip_len = int(n_clips), int(clip_len)
+        if self.n_clips <= 0 or self.clip_len <= 0 or int(crop_size) <= 0:
+            raise ValueError("n_clips, clip_len and crop_size must be positive")
+        self._clip = ClipTransform(is_validation, crop_size)
+        self.is_validation, self.crop_size, self.size = self._clip.is_validation, self._clip.crop_size, self._clip.size
+        self._staging = [None, None]        # two pinned buffers in alternation, each [buffer, event of its last upload]
+        self._turn = 0
+
+    def draw_params(self, sizes: Sequence[Sequence[int]]):
+        """One ``(top, left, flip)`` per video, in video order; ``sizes``: the ``(H, W)`` of every video's frames.
+        Consumes Python's ``random`` exactly as ``ClipTransform.draw_params(1, hres, wres)`` per video in turn."""
+        rows = []
+        for h, w in sizes:
+            hres, wres, _ = resized_hw(int(h), int(w), self.size)
+            if hres < self.crop_size or wres < self.crop_size:
+                raise RuntimeError("clip too small for the crop")
+            rows.extend(self._clip.draw_params(1, hres, wres))
+        return rows
+
+    def _check(self, videos, params):
+        """Everything ``__call__`` refuses, before any device is touched.  Returns the ``(H, W)`` of every video."""
+        frames, crop = self.n_clips * self.clip_len, self.crop_size
+        if not videos:
+            raise RuntimeError("expected at least one video")
+        sizes = []
+        for v in videos:
+            if not isinstance(v, torch.Tensor) or v.dim() not in (4, 5) or v.shape[-1] != 3 or v.dtype != torch.uint8:
+                raise RuntimeError("expected (n_clips*clip_len, H, W, 3) or (n_clips, clip_len, H, W, 3) uint8 videos")
+            lead = tuple(int(d) for d in v.shape[:-3])
+            if lead != (frames,) and lead != (self.n_clips, self.clip_len):
+                raise RuntimeError(f"expected {self.n_clips} x {self.clip_len} = {frames} frames per video, got {lead}")
+            h, w = int(v.shape[-3]), int(v.shape[-2])
+            hres, wres, _ = resized_hw(h, w, self.size) if min(h, w) > 0 else (0, 0, 0.0)
+            if hres < crop or wres < crop:
+                raise RuntimeError("clip too small for the crop")
+            sizes.append((h, w))
+        if params is not None:
+            if len(params) != len(videos):
+                raise RuntimeError("one (top, left, flip) triple per video expected")
+            for (h, w), (i, j, _f) in zip(sizes, params):
+                hres, wres, _ = resized_hw(h, w, self.size)
+                if not (0 <= i <= hres - crop and 0 <= j <= wres - crop):
+                    raise RuntimeError("crop window outside the resized frame")
+        for v in videos:
+            if not v.is_cuda:
+                raise RuntimeError("VideoClips runs on an MI355X HIP device only (no CPU fallback; "
+                                   "the CPU restatement lives in oracle/)")
+            if v.device != videos[0].device:
+                raise RuntimeError("all videos must live on one device")
+        return sizes
+
+    def __call__(self, videos: Sequence[torch.Tensor], params: Optional[Sequence[Sequence[int]]] = None) -> torch.Tensor:
+        """``videos``: a sequence of uint8 tensors on one HIP device, each ``(n_clips*clip_len, H_i, W_i, 3)`` or
+        ``(n_clips, clip_len, H_i, W_i, 3)``; ``params``: one ``(top, left, flip)`` per video (drawn by ``draw_params`` when
+        not given).  Returns ``(B, n_clips, 3, clip_len, crop, crop)`` fp32, the input of ``Model.forward``."""
+        videos = list(videos)
+        sizes = self._check(videos, params)
+        if params is None:
+            params = self.draw_params(sizes)
+        device = videos[0].device
+        videos = [v.contiguous() for v in videos]                # (a copy made here is freed in stream order, after the launch)
+        table = video_table([v.data_ptr() for v in videos], sizes, params, self.size)
+        # pinned + non_blocking: a pageable upload would drain the stream every call (the host could no longer run ahead)
+        vtab = torch.from_numpy(table).pin_memory().to(device, non_blocking=True)
+        out = torch.empty((len(videos), self.n_clips, 3, self.clip_len, self.crop_size, self.crop_size), dtype=torch.float32,
+                          device=device)
+        with torch.cuda.device(device):
+            _lib.check(_lib.load().zsv_clip_transform_batch(vtab.data_ptr(), len(videos), self.n_clips, self.clip_len, self.crop_size,
+                                                            out.data_ptr(), c_void_p(torch.cuda.current_stream().cuda_stream)),
+                       "zsv_clip_transform_batch")
+        return out
+
+    def stage(self, arrays: Sequence, device="cuda"):
+        """The loader-side half: ``arrays`` (CPU uint8 arrays or tensors of different sizes) are copied back to back into
+        one pinned staging buffer and uploaded with ONE ``non_blocking`` copy on the current stream; returns the device
+        views, one per video, in the shapes given.  Two staging buffers alternate; each carries the event of its last
+        upload, which is waited for on the host before the buffer is overwritten, and a buffer is replaced only when a
+        batch needs more room.  The device buffer behind the views is the caller's: the launch reads it in stream order."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("VideoClips.stage uploads to an MI355X HIP device only (no CPU fallback)")
+        sources = []
+        for a in arrays:
+            if not isinstance(a, torch.Tensor):
+                a = np.asarray(a)
+                with warnings.catch_warnings():                  # a read-only array from a loader is a fine source: it is only read
+                    warnings.simplefilter("ignore", UserWarning)
+                    a = torch.from_numpy(a) if a.dtype == np.uint8 else None
+            if a is None or a.dtype != torch.uint8 or a.is_cuda:
+                raise RuntimeError("expected CPU uint8 arrays")
+            sources.append(a)
+        if not sources:
+            raise RuntimeError("expected at least one video")
+        offsets, total = [], 0
+        for a in sources:
+            offsets.append(total)
+            total += -(-a.numel() // 256) * 256                  # every video starts on a 256-byte boundary
+        slot = self._staging[self._turn]
+        if slot is not None:
+            slot[1].synchronize()                                # the upload that last read this buffer has finished
+        if slot is None or slot[0].numel() < total:
+            slot = self._staging[self._turn] = [torch.empty(total, dtype=torch.uint8, pin_memory=True), torch.cuda.Event()]
+        self._turn ^= 1
+        pinned = slot[0]
+        for a, off in zip(sources, offsets):
+            pinned[off:off + a.numel()].view(a.shape).copy_(a)   # (torch's copy uses the host's threads)
+        with torch.cuda.device(device):
+            dev = torch.empty(total, dtype=torch.uint8, device=device)
+            dev.copy_(pinned[:total], non_blocking=True)
+            slot[1].record()
+        return [dev[off:off + a.numel()].view(a.shape) for a, off in zip(sources, offsets)]
+
+
+def get_batch_transform(is_validation, n_clips=1, clip_len=16, crop_size=112):
+    return VideoClips(is_validation, n_clips, clip_len, crop_size)
 
 
 # ---- still images (auxiliary/auxiliary_stillimages.py) ---------------------------------------------------------------
