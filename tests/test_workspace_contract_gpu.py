@@ -1,0 +1,892 @@
+"""The C ABI's memory contract (include/zsv_hip.h: "kernels never allocate: workspaces are passed in (query the size first)",
+the caller owns every output), entry point by entry point, with guard bands (tests/guarded.py).
+
+Every (entry point, case) is called through ctypes two or three times.  Each run gets a workspace / blob / panel / mask table /
+partials buffer of EXACTLY the queried size and every output in a buffer of exactly its shape, each between two 1 MiB guard
+bands in an allocation of its own; the payloads are prefilled with 0x00 in the first run and 0xFF (NaN / -1 / the e4m3 NaN
+code) in the second; the convolution and weight-gradient cases run a third time with the workspace 16 bytes past a 256-byte
+boundary, the alignment the header promises to accept.  Asserted after one synchronize:
+
+(a) the call returns ZSV_OK;
+(b) no guard band changed (nothing written before or past a buffer);
+(c) the outputs of the runs are equal as raw bytes: the library has no floating-point atomics and fixed-order reductions, so a
+    result may not depend on what a workspace held before the call;
+(d) no output element of the 0xFF run still holds the prefill: the inputs are finite, a NaN / -1 is an element nobody wrote, or
+    computed from workspace bytes nobody wrote;
+(e) the outputs equal, as raw bytes, what the package's own wrapper (ops / amp / inference / train) returns for the same operands
+    under the same switches (the other suites pin those wrappers to fp64 references); where no wrapper exposes the call, the
+    comparison is the one the existing test of that entry point makes, with its tolerance.
+
+A case is left out for an entry point only where that entry point's own ``*_supported`` / size query says it cannot run the
+geometry.  The case tables are the ones of the other suites (rows with N = 22 or more than about 2 M output elements left out:
+GPU_ROW_LIMIT).  The last test of the file asserts that every entry point ran, and on every row of its table, and prints the
+counts: run the file as a whole.
+"""
+import collections
+import ctypes
+import zlib
+from ctypes import byref
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import bf16_exact_cases as X
+import guarded as G
+import test_accuracy as TA
+import test_bf16_exact_gpu as BX
+import test_fp8_gpu as F8
+import test_ops_gpu as T
+
+pytestmark = pytest.mark.gpu
+
+from zeroshotvideoclassification_amd import _lib, amp, inference, ops, train  # noqa: E402
+
+DEV = "cuda"
+F32, F64, I32, BF16, U8 = torch.float32, torch.float64, torch.int32, torch.bfloat16, torch.uint8
+GPU_ROW_LIMIT = 2.5e6            # "about 2 M output elements"
+# rows above the limit that stay, because no smaller row of their table reaches their kernel (the F(4,3) weight-gradient form)
+KEPT_LARGE_ROWS = {"two_144_row_tiles", "m200_ragged_second_tile"}
+
+COUNTS = collections.Counter()                 # entry point -> (case, switch) combinations run
+ROWS_RUN = collections.defaultdict(set)        # (table, plain call) -> row names run
+
+
+@pytest.fixture(autouse=True)
+def _plain_wrappers(monkeypatch):
+    """The wrappers the results are compared with run the same entry points as the test: no cached weight panel, no side stream."""
+    monkeypatch.setenv("ZSV_NO_PANEL_CACHE", "1")
+    monkeypatch.setenv("ZSV_WGRAD_STREAM", "0")
+
+
+def lib():
+    return _lib.load()
+
+
+def numel(shape):
+    return int(np.prod(shape)) if len(shape) else 1
+
+
+def contract(entry, launch, outs, works=None, shifted=False, defined=None, count=True):
+    """Run ``launch`` once per payload fill (and once more with the buffers named in ``shifted`` 16 bytes past a 256-byte
+    boundary) on fresh guarded buffers and assert (a) - (d).
+
+    outs:  name -> (dtype, shape) or (dtype, shape, initial tensor) -- the latter for in / out arguments (running statistics);
+    works: name -> bytes: workspaces, blobs, panels, mask tables (prefilled, guarded, not compared);
+    launch(p): p[name] = device address; returns the status, or a list of them;
+    defined(name, tensor) -> the part of an output the operation defines (default: all of it).
+    Returns name -> the first run's output (a copy)."""
+    works = works or {}
+    runs = [(0x00, 0), (0xFF, 0)] + ([(0xFF, 16)] if shifted else [])
+    results = []
+    for fill, shift in runs:
+        bufs, views = {}, {}
+        for name, spec in outs.items():
+            b = G.guarded_like(spec[0], spec[1], DEV, fill)
+            views[name] = b.view(spec[0], spec[1])
+            if len(spec) > 2:
+                views[name].copy_(spec[2])
+            bufs[name] = b
+        for name, nbytes in works.items():
+            bufs[name] = G.guarded(nbytes, DEV, fill, 256, shift if (shifted is True or (shifted and name in shifted)) else 0)
+        status = launch({name: b.ptr for name, b in bufs.items()})
+        torch.cuda.synchronize()
+        what = f"{entry}, prefill 0x{fill:02X}" + (", workspace at 256 k + 16" if shift else "")
+        for s in (status if isinstance(status, (list, tuple)) else [status]):
+            assert s == 0, f"{what}: {lib().zsv_status_string(int(s)).decode()} (status {s})"                    # (a)
+        for name, b in bufs.items():
+            b.check(f"{what}: {name}")                                                                         # (b)
+        got = {}
+        for name, v in views.items():
+            part = defined(name, v) if defined else v
+            if fill == 0xFF:
+                G.assert_all_written(part, f"{what}: {name}")                                                  # (d)
+            got[name] = part.clone()
+        results.append(got)
+    for (fill, shift), got in zip(runs[1:], results[1:]):
+        for name, v in got.items():
+            assert v.shape == results[0][name].shape and torch.equal(v.contiguous().view(U8), results[0][name].contiguous().view(U8)), \
+                f"{entry}: {name} depends on what the buffers held before the call (prefill 0x00 vs 0x{fill:02X}, shift {shift})"   # (c)
+    if count:
+        COUNTS[entry] += 1
+    return results[0]
+
+
+def same_bytes(got, want, what):
+    """(e): equal as raw bytes."""
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {tuple(got.shape)} vs {want.dtype} {tuple(want.shape)}"
+    if not torch.equal(got.contiguous().view(U8), want.contiguous().view(U8)):
+        bad = int((got != want).sum())
+        raise AssertionError(f"{what}: {bad} of {got.numel()} elements differ from the wrapper's result")
+
+
+def params_of(test_function):
+    return [m for m in test_function.pytestmark if m.name == "parametrize"][0].args[1]
+
+
+# =========================================================================================================================
+# fp32 convolution
+# =========================================================================================================================
+ConvRow = collections.namedtuple("ConvRow", "table name xs ws stride pad knobs base")
+
+
+def _conv_rows():
+    rows = []
+
+    def add(table, name, xs, ws, stride, pad, knobs, base=()):
+        stride = ops._triple(stride)
+        d = ops.conv_desc(xs, ws, stride, pad)
+        if xs[0] == 22:
+            return
+        if d.N * d.Cout * d.To * d.Ho * d.Wo > GPU_ROW_LIMIT and name not in KEPT_LARGE_ROWS:
+            return
+        rows.append(ConvRow(table, str(name), tuple(xs), tuple(ws), stride, tuple(pad), [()] + list(knobs), tuple(base)))
+
+    for name, n, cin, t, h, w, cout, k, s, p, _bias in T.CONV_CASES:
+        add("CONV_CASES", name, (n, cin, t, h, w), (cout, cin) + k, s, p, [])
+    for name, n, cin, thw, cout, k, p in T.WGRAD_DMA_CASES:
+        add("WGRAD_DMA_CASES", name, (n, cin) + thw, (cout, cin) + k, 1, p, [(("ZSV_NO_WGRAD_DMA", "1"),)])
+    for name, n, cin, thw, cout, kt in T.WGRAD_WINO_CASES:
+        add("WGRAD_WINO_CASES", name, (n, cin) + thw, (cout, cin, kt, 3, 3), 1, (kt // 2, 1, 1),
+            [(("ZSV_NO_WGRAD_WINO4", "1"),), (("ZSV_NO_WGRAD_WINO", "1"),)])
+    for name, n, cin, thw, cout in T.WGRAD_TRING_CASES:
+        add("WGRAD_TRING_CASES", name, (n, cin) + thw, (cout, cin, 3, 1, 1), 1, (1, 0, 0),
+            [(("ZSV_NO_WGRAD_TRING", "1"),), (("ZSV_WGRAD_TRING_SLICES", "7"),)])
+    for name, n, cin, cout, thw, kind in T.S2_DGRAD_CASES:
+        k, s, p = ((1, 3, 3), (1, 2, 2), (0, 1, 1)) if kind == "hw" else ((3, 1, 1), (2, 1, 1), (1, 0, 0))
+        add("S2_DGRAD_CASES", name, (n, cin) + thw, (cout, cin) + k, s, p,
+            [(("ZSV_NO_DGRAD_S2", "1"),), (("ZSV_DGRAD_S2_NO_X4", "1"),)] +
+            [(("ZSV_DGRAD_S2_BN", bn), ("ZSV_DGRAD_S2_KS", ks)) for bn in ("64", "128") for ks in ("1", "2", "3")])   # tile width x K parts
+    for name, n, cin, cout, kt, thw in T.VW_CASES:
+        add("VW_CASES", name, (n, cin) + thw, (cout, cin, kt, 3, 3), 1, (kt // 2, 1, 1), [(("ZSV_WINO_NO_VW", "1"),)],
+            base=(("ZSV_WINO_VW_MIN_WGS", "1"),))
+    for n, t, h, w, cout in params_of(T.test_stem_weight_gradient_row_kernel):
+        add("stem_rows", f"n{n}_t{t}_{h}x{w}_c{cout}", (n, 3, t, h, w), (cout, 3, 1, 7, 7), (1, 2, 2), (0, 3, 3), [(("ZSV_NO_STEM_WGRAD", "1"),)])
+    for n, cin, cout, hw in params_of(T.test_two_frame_temporal_conv_in_dense_form):
+        add("two_frame_dense", f"n{n}_{cin}_{cout}", (n, cin, 2) + tuple(hw), (cout, cin, 3, 1, 1), 1, (1, 0, 0), [(("ZSV_NO_T2_DENSE", "1"),)])
+    # the geometries of test_conv3d_split_k_small_grid (K parts: partial slabs in the workspace + an ordered reduce)
+    for cin, cout, k, s, p, t, h, w in [(256, 320, (1, 3, 3), (1, 1, 1), (0, 1, 1), 2, 7, 7), (320, 128, (3, 1, 1), (1, 1, 1), (1, 0, 0), 2, 7, 7),
+                                        (128, 200, (1, 3, 3), (1, 2, 2), (0, 1, 1), 2, 14, 14)]:
+        add("split_k", f"{cin}_{cout}_k{k[0]}{k[1]}{k[2]}", (2, cin, t, h, w), (cout, cin) + k, s, p,
+            [(("ZSV_SPLITK_REDUCE_SCALAR", "1"),), (("ZSV_NO_SPLITK", "1"),)])
+    # test_weight_gradient_slab_sum_rows_equals_the_generic_sum, test_tiled_weight_pack_equals_the_elementwise_pack
+    add("slab_sum_rows", "6x96_200", (6, 96, 2, 7, 7), (200, 96, 1, 3, 3), 1, (0, 1, 1), [(("ZSV_NO_SLAB_SUM_ROWS", "1"),)])
+    for xs, ws, stride, pad in [((4, 128, 4, 14, 14), (300, 128, 1, 3, 3), (1, 2, 2), (0, 1, 1)), ((3, 200, 4, 7, 7), (120, 200, 3, 1, 1), (2, 1, 1), (1, 0, 0)),
+                                ((3, 96, 2, 7, 7), (130, 96, 1, 3, 3), 1, (0, 1, 1)), ((2, 40, 3, 6, 6), (50, 40, 3, 3, 3), (2, 2, 2), (1, 1, 1))]:
+        add("pack_tiled", f"{ws[1]}_{ws[0]}", xs, ws, stride, pad, [(("ZSV_NO_PACK_TILED", "1"),), (("ZSV_NO_WINO", "1"),)])
+    return rows
+
+
+CONV_ROWS = _conv_rows()
+CONV_TABLES = ["CONV_CASES", "WGRAD_DMA_CASES", "WGRAD_WINO_CASES", "WGRAD_TRING_CASES", "S2_DGRAD_CASES", "VW_CASES", "stem_rows",
+               "two_frame_dense", "split_k", "slab_sum_rows", "pack_tiled"]
+
+
+def _conv_operands(row):
+    g = torch.Generator().manual_seed(zlib.crc32((row.table + row.name).encode()))
+    d = ops.conv_desc(row.xs, row.ws, row.stride, row.pad)
+    ys = (d.N, d.Cout, d.To, d.Ho, d.Wo)
+    k = numel(row.ws[1:])
+    o = dict(x=torch.randn(row.xs, generator=g), w=torch.randn(row.ws, generator=g) / np.sqrt(k), bias=torch.randn(row.ws[0], generator=g),
+             res=torch.randn(ys, generator=g), dy=torch.randn(ys, generator=g), add=torch.randn(row.xs, generator=g))
+    pitch = (d.Cin + 15) // 16 * 16
+    coef = torch.zeros(2, pitch)
+    coef[0, :d.Cin] = torch.rand(d.Cin, generator=g) + 0.5
+    coef[1, :d.Cin] = torch.randn(d.Cin, generator=g) * 0.2
+    o["coef"] = coef
+    return d, ys, {k_: v.to(DEV) for k_, v in o.items()}, g
+
+
+def _conv_entry_points(row, tag):
+    """Every fp32 convolution entry point on one row under the switches in force."""
+    L = lib()
+    d, ys, o, g = _conv_operands(row)
+    x, w, bias, res, dy, add = (o[k].data_ptr() for k in ("x", "w", "bias", "res", "dy", "add"))
+    dp = byref(d)
+    nf, nd, nw = int(L.zsv_conv3d_fwd_workspace_bytes(dp)), int(L.zsv_conv3d_dgrad_workspace_bytes(dp)), int(L.zsv_conv3d_wgrad_workspace_bytes(dp))
+    what = f"{row.table}/{row.name}{tag}"
+
+    # ---- the wrapper's results (e) ----
+    xg, wg = o["x"].clone().requires_grad_(), o["w"].clone().requires_grad_()
+    yw = ops.conv3d(xg, wg, None, row.stride, row.pad)
+    yw.backward(o["dy"])
+    ops.join_wgrad_streams()
+    with torch.no_grad():
+        yw_relu = ops.conv3d(o["x"], o["w"], o["bias"], row.stride, row.pad, relu=True)
+        yw_stats, stats_w = ops.conv3d(o["x"], o["w"], None, row.stride, row.pad, want_stats=True)
+    torch.cuda.synchronize()
+
+    # ---- forward ----
+    def fwd(b, r, relu, stats, tiles):
+        return lambda p: L.zsv_conv3d_fwd_full(dp, x, w, b, r, p["y"], relu, p.get(stats), tiles, p["ws"], nf, None)
+
+    y = contract("zsv_conv3d_fwd_full", fwd(None, None, 0, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True)["y"]
+    same_bytes(y, yw.detach(), f"{what}: forward")
+    ROWS_RUN[(row.table, "fwd")].add(row.name)
+    yb = contract("zsv_conv3d_fwd_full (bias + ReLU)", fwd(bias, None, 1, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True)["y"]
+    same_bytes(yb, yw_relu, f"{what}: forward + bias + ReLU")
+    if L.zsv_conv3d_fwd_add_supported(dp):
+        yr = contract("zsv_conv3d_fwd_full (residual)", fwd(bias, res, 1, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True)["y"]
+        conv = torch.nn.Conv3d(d.Cin, d.Cout, row.ws[2:], row.stride, row.pad, bias=True).to(DEV)
+        with torch.no_grad():
+            conv.weight.copy_(o["w"])
+            conv.bias.copy_(o["bias"])
+            same_bytes(yr, inference._ConvOpF32(conv, None, True)(o["x"], o["res"]), f"{what}: forward + bias + residual + ReLU")
+    probe = G.guarded_like(F32, ys, DEV, 0)
+    tiles = int(L.zsv_conv3d_fwd_stat_tiles(dp, probe.ptr))
+    assert (tiles > 0) == (stats_w is not None), f"{what}: the statistics query disagrees with the wrapper's"
+    if tiles > 0:
+        out = contract("zsv_conv3d_fwd_full (statistics)", fwd(None, None, 0, "bn_partials", tiles),
+                       {"y": (F32, ys), "bn_partials": (F32, (2, d.Cout, tiles))}, {"ws": nf}, shifted=True)
+        same_bytes(out["y"], yw_stats, f"{what}: forward with the statistics epilogue")
+        same_bytes(out["bn_partials"], stats_w, f"{what}: statistics")
+
+    # ---- input gradient ----
+    dx = contract("zsv_conv3d_dgrad", lambda p: L.zsv_conv3d_dgrad(dp, dy, w, p["dx"], p["ws"], nd, None),
+                  {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True)["dx"]
+    same_bytes(dx, xg.grad, f"{what}: dgrad")
+    ROWS_RUN[(row.table, "dgrad")].add(row.name)
+    if L.zsv_conv3d_dgrad_add_supported(dp):
+        dxa = contract("zsv_conv3d_dgrad_add", lambda p: L.zsv_conv3d_dgrad_add(dp, dy, w, add, p["dx"], p["ws"], nd, None),
+                       {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True)["dx"]
+        T.close(dxa, dx.double() + o["add"].double(), rtol=1e-6, what=f"{what}: dgrad + shortcut gradient")
+    for st in (1, 2):
+        if L.zsv_conv3d_dgrad_add_strided_supported(dp, st, 2, 2):
+            sub = torch.randn((d.N, d.Cin, -(-d.Ti // st), d.Hi // 2, d.Wi // 2), generator=g).to(DEV)
+            dxs = contract("zsv_conv3d_dgrad_add_strided",
+                           lambda p: L.zsv_conv3d_dgrad_add_strided(dp, dy, w, sub.data_ptr(), st, 2, 2, p["dx"], p["ws"], nd, None),
+                           {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True)["dx"]
+            ref = dx.double()
+            ref[:, :, ::st, :2 * (d.Hi // 2):2, :2 * (d.Wi // 2):2] += sub.double()
+            T.close(dxs, ref, rtol=1e-6, what=f"{what}: dgrad + strided shortcut gradient (st = {st})")
+
+    # ---- weight gradient ----
+    x_, dy_ = o["x"].data_ptr(), dy
+    dw = contract("zsv_conv3d_wgrad", lambda p: L.zsv_conv3d_wgrad(dp, x_, dy_, p["dw"], p["ws"], nw, None),
+                  {"dw": (F32, row.ws)}, {"ws": nw}, shifted=True)["dw"]
+    same_bytes(dw, wg.grad, f"{what}: wgrad")
+    ROWS_RUN[(row.table, "wgrad")].add(row.name)
+    nm = int(L.zsv_conv3d_wgrad_mask_bytes(dp))
+    dwm = contract("zsv_conv3d_wgrad_masked",
+                   lambda p: [L.zsv_conv3d_wgrad_mask(dp, p["mask"], None) if nm else 0,
+                              L.zsv_conv3d_wgrad_masked(dp, x_, dy_, p["dw"], p["ws"], nw, p["mask"] if nm else None, None)],
+                   {"dw": (F32, row.ws)}, {"ws": nw, "mask": nm}, shifted={"ws"})["dw"]
+    same_bytes(dwm, dw, f"{what}: wgrad with a kept tap-validity table")
+
+    # ---- the BatchNorm + ReLU folded into the convolution ----
+    if L.zsv_conv3d_pre_supported(dp):
+        coef, pitch = o["coef"].data_ptr(), int(o["coef"].shape[1])
+        wp = o["w"].clone().requires_grad_()
+        yp, sp = ops.conv3d_pre(o["x"], o["coef"], wp, row.stride, row.pad, want_stats=True)
+        yp.backward(o["dy"])
+        ops.join_wgrad_streams()
+        torch.cuda.synchronize()
+        outs = {"y": (F32, ys)}
+        if tiles > 0:
+            outs["bn_partials"] = (F32, (2, d.Cout, tiles))
+        out = contract("zsv_conv3d_fwd_pre",
+                       lambda p: L.zsv_conv3d_fwd_pre(dp, x_, coef, pitch, w, p["y"], p.get("bn_partials"), tiles, p["ws"], nf, None),
+                       outs, {"ws": nf}, shifted=True)
+        same_bytes(out["y"], yp.detach(), f"{what}: forward through BatchNorm + ReLU")
+        if tiles > 0:
+            same_bytes(out["bn_partials"], sp, f"{what}: statistics of the forward through BatchNorm + ReLU")
+        dwp = contract("zsv_conv3d_wgrad_pre", lambda p: L.zsv_conv3d_wgrad_pre(dp, x_, coef, pitch, dy_, p["dw"], p["ws"], nw, None),
+                       {"dw": (F32, row.ws)}, {"ws": nw}, shifted=True)["dw"]
+        same_bytes(dwp, wp.grad, f"{what}: wgrad through BatchNorm + ReLU")
+
+
+@pytest.mark.parametrize("row", CONV_ROWS, ids=[f"{r.table}-{r.name}" for r in CONV_ROWS])
+def test_fp32_convolution_entry_points(row, monkeypatch):
+    for k, v in row.base:
+        monkeypatch.setenv(k, v)
+    for knobs in row.knobs:
+        for k, v in knobs:
+            monkeypatch.setenv(k, v)                      # (tests/conftest.py: the library re-reads its switches; sizes are re-queried)
+        _conv_entry_points(row, "".join(f" {k}={v}" for k, v in knobs))
+        for k, _ in knobs:
+            monkeypatch.delenv(k)
+
+
+# =========================================================================================================================
+# weight panels packed ahead of the call
+# =========================================================================================================================
+# PANEL_CASES, and one row more: none of them has the forward that reads its input through BatchNorm + ReLU
+# (zsv_conv3d_fwd_pre_panel); the first row of WGRAD_TRING_CASES does
+_name, _n, _cin, _thw, _cout = T.WGRAD_TRING_CASES[0]
+PANEL_ROWS = list(T.PANEL_CASES) + [("bn_folded_" + _name, (_n, _cin) + _thw, (_cout, _cin, 3, 1, 1), 1, (1, 0, 0))]
+
+
+@pytest.mark.parametrize("case", PANEL_ROWS, ids=[c[0] for c in PANEL_ROWS])
+def test_weight_panels(case):
+    name, xs, ws, stride, pad = case
+    L = lib()
+    row = ConvRow("PANEL_CASES", name, xs, ws, ops._triple(stride), pad, [()], ())
+    d, ys, o, g = _conv_operands(row)
+    dp = byref(d)
+    x, w, bias, dy = (o[k].data_ptr() for k in ("x", "w", "bias", "dy"))
+    nf, nd = int(L.zsv_conv3d_fwd_workspace_bytes(dp)), int(L.zsv_conv3d_dgrad_workspace_bytes(dp))
+
+    def panel_bytes(direction, extras):
+        nb = ctypes.c_size_t(0)
+        _lib.check(L.zsv_conv3d_panel_query(dp, direction, extras, byref(nb)), "zsv_conv3d_panel_query")
+        assert nb.value > 0, (name, direction, extras)
+        return int(nb.value)
+
+    def pack(p, direction, extras, nb):
+        job = _lib.PackJob()
+        s = L.zsv_conv3d_panel_job(dp, direction, extras, w, p["panel"], nb, byref(job))
+        if s:
+            return s
+        job.first_block = 0
+        table = torch.frombuffer(bytearray(bytes(job)), dtype=U8).to(DEV)
+        s = L.zsv_pack_multi(table.data_ptr(), 1, (int(job.total) + 1023) // 1024, None)
+        torch.cuda.synchronize()                          # (the job table is a temporary)
+        return s
+
+    for extras in (0, 1):
+        nb = panel_bytes(0, extras)
+        b = bias if extras else None
+        y = contract("zsv_pack_multi + zsv_conv3d_fwd_full_panel",
+                     lambda p: [pack(p, 0, extras, nb),
+                                L.zsv_conv3d_fwd_full_panel(dp, x, w, b, None, p["y"], extras, None, 0, p["ws"], nf, None, p["panel"], nb)],
+                     {"y": (F32, ys)}, {"ws": nf, "panel": nb}, shifted={"ws"})["y"]
+        with torch.no_grad():
+            same_bytes(y, ops.conv3d(o["x"], o["w"], o["bias"] if extras else None, stride, pad, relu=bool(extras)), f"{name}: forward, extras {extras}")
+    nb = panel_bytes(1, 0)
+    dx = contract("zsv_pack_multi + zsv_conv3d_dgrad_add_panel",
+                  lambda p: [pack(p, 1, 0, nb), L.zsv_conv3d_dgrad_add_panel(dp, dy, w, None, p["dx"], p["ws"], nd, None, p["panel"], nb)],
+                  {"dx": (F32, xs)}, {"ws": nd, "panel": nb}, shifted={"ws"})["dx"]
+    xg = o["x"].clone().requires_grad_()
+    ops.conv3d(xg, o["w"], None, stride, pad).backward(o["dy"])
+    same_bytes(dx, xg.grad, f"{name}: dgrad")
+    if L.zsv_conv3d_pre_supported(dp):
+        coef, pitch = o["coef"].data_ptr(), int(o["coef"].shape[1])
+        y = contract("zsv_pack_multi + zsv_conv3d_fwd_pre_panel",
+                     lambda p: [pack(p, 0, 0, panel_bytes(0, 0)),
+                                L.zsv_conv3d_fwd_pre_panel(dp, x, coef, pitch, w, p["y"], None, 0, p["ws"], nf, None, p["panel"], panel_bytes(0, 0))],
+                     {"y": (F32, ys)}, {"ws": nf, "panel": panel_bytes(0, 0)}, shifted={"ws"})["y"]
+        with torch.no_grad():
+            same_bytes(y, ops.conv3d_pre(o["x"], o["coef"], o["w"], stride, pad), f"{name}: forward through BatchNorm + ReLU")
+    for st in (1, 2):
+        if L.zsv_conv3d_dgrad_add_strided_supported(dp, st, 2, 2):
+            sub = torch.randn((d.N, d.Cin, -(-d.Ti // st), d.Hi // 2, d.Wi // 2), generator=g).to(DEV)
+            dxs = contract("zsv_pack_multi + zsv_conv3d_dgrad_add_strided_panel",
+                           lambda p: [pack(p, 1, 0, nb), L.zsv_conv3d_dgrad_add_strided_panel(dp, dy, w, sub.data_ptr(), st, 2, 2, p["dx"], p["ws"], nd,
+                                                                                              None, p["panel"], nb)],
+                           {"dx": (F32, xs)}, {"ws": nd, "panel": nb}, shifted={"ws"})["dx"]
+            ref = dx.double()
+            ref[:, :, ::st, :2 * (d.Hi // 2):2, :2 * (d.Wi // 2):2] += sub.double()
+            T.close(dxs, ref, rtol=1e-6, what=f"{name}: dgrad + strided shortcut gradient (panel)")
+    ROWS_RUN[("PANEL_CASES", "panel")].add(name)
+
+
+# =========================================================================================================================
+# reductions and BatchNorm
+# =========================================================================================================================
+BN_SHAPES = [(n, c) + tuple(s) for n, c, s in T.BN_CASES] + [(1, 1, 1, 1, 2), (2, 3, 1, 1, 1), (1, 260, 1, 3, 3), (5, 2, 3, 5, 7)]   # + the edge shapes
+
+
+def _bn_operands(shape):
+    n, c = shape[:2]
+    g = torch.Generator().manual_seed(n * 1000 + c)
+    o = dict(x=torch.randn(shape, generator=g) * 2 + 0.5, res=torch.randn(shape, generator=g), gamma=torch.rand(c, generator=g) + 0.5,
+             beta=torch.randn(c, generator=g) * 0.1, rm=torch.randn(c, generator=g) * 0.1, rv=torch.rand(c, generator=g) + 0.5,
+             dy=torch.randn(shape, generator=g))
+    return {k: v.to(DEV) for k, v in o.items()}
+
+
+@pytest.mark.parametrize("shape", BN_SHAPES, ids=["x".join(map(str, s)) for s in BN_SHAPES])
+def test_channel_sum_and_relu_bwd_bias(shape):
+    L = lib()
+    o = _bn_operands(shape)
+    n, c = shape[:2]
+    s = numel(shape[2:])
+    nb = int(L.zsv_channel_sum_workspace_bytes(n, c, s))
+    dy, y = o["dy"].data_ptr(), o["x"].data_ptr()
+    db = contract("zsv_channel_sum", lambda p: L.zsv_channel_sum(dy, n, c, s, p["db"], p["ws"], nb, None), {"db": (F32, (c,))}, {"ws": nb})["db"]
+    same_bytes(db, ops.channel_sum(o["dy"]), "channel_sum")
+    out = contract("zsv_relu_bwd_bias", lambda p: L.zsv_relu_bwd_bias(dy, y, p["dx"], n, c, s, p["db"], p["ws"], nb, None),
+                   {"dx": (F32, shape), "db": (F32, (c,))}, {"ws": nb})
+    ref = torch.where(o["x"] > 0, o["dy"], torch.zeros_like(o["dy"]))
+    assert torch.equal(out["dx"], ref)
+    T.close(out["db"], ref.double().sum(dim=(0, 2, 3, 4)), what="bias gradient")        # (test_relu_bwd_bias_on_misaligned_views)
+    ROWS_RUN[("BN_CASES", "channel_sum")].add(shape)
+
+
+@pytest.mark.parametrize("relu", [False, True], ids=["plain", "relu"])
+@pytest.mark.parametrize("use_res", [False, True], ids=["no_res", "res"])
+@pytest.mark.parametrize("shape", BN_SHAPES, ids=["x".join(map(str, s)) for s in BN_SHAPES])
+def test_batchnorm_entry_points(shape, use_res, relu):
+    L = lib()
+    o = _bn_operands(shape)
+    n, c = shape[:2]
+    s = numel(shape[2:])
+    nb = int(L.zsv_bn_workspace_bytes(n, c, s))
+    x, gamma, beta, dy = (o[k].data_ptr() for k in ("x", "gamma", "beta", "dy"))
+    res = o["res"].data_ptr() if use_res else None
+    r = 1 if relu else 0
+    stat_outs = {"save_mean": (F32, (c,)), "save_invstd": (F32, (c,)), "running_mean": (F32, (c,), o["rm"]), "running_var": (F32, (c,), o["rv"])}
+
+    # ---- the wrapper (e): forward and backward, training and frozen ----
+    def wrapper(training, stats=None):
+        t = {k: o[k].clone().requires_grad_() for k in ("x", "gamma", "beta")}
+        rg = o["res"].clone().requires_grad_() if use_res else None
+        rm, rv = o["rm"].clone(), o["rv"].clone()
+        y = ops.batch_norm_act(t["x"], t["gamma"], t["beta"], rm, rv, rg, training, 0.1, 1e-5, relu, stats=stats)
+        y.backward(o["dy"])
+        torch.cuda.synchronize()
+        return dict(y=y.detach(), rm=rm, rv=rv, dx=t["x"].grad, dgamma=t["gamma"].grad, dbeta=t["beta"].grad, dres=rg.grad if use_res else None)
+
+    # ---- training forward ----
+    wt = wrapper(True)
+    out = contract("zsv_bn_fwd_train",
+                   lambda p: L.zsv_bn_fwd_train(x, n, c, s, gamma, beta, res, r, p["y"], p["save_mean"], p["save_invstd"], p["running_mean"],
+                                                p["running_var"], 0.1, 1e-5, p["ws"], nb, None),
+                   dict(stat_outs, y=(F32, shape)), {"ws": nb})
+    same_bytes(out["y"], wt["y"], "bn_fwd_train: y")
+    same_bytes(out["running_mean"], wt["rm"], "bn_fwd_train: running_mean")
+    same_bytes(out["running_var"], wt["rv"], "bn_fwd_train: running_var")
+    xd = o["x"].double()
+    mean, var = xd.mean(dim=(0, 2, 3, 4)), xd.var(dim=(0, 2, 3, 4), unbiased=False)
+    T.close(out["save_mean"], mean, rtol=1e-4, what="save_mean")
+    T.close(out["save_invstd"], torch.rsqrt(var + 1e-5), rtol=1e-4, what="save_invstd")
+    save_mean, save_invstd, y_fwd = out["save_mean"], out["save_invstd"], out["y"]
+    # the same from epilogue partials: three column tiles over the voxel axis (as many as the voxels allow)
+    tiles = min(3, s)
+    cuts = [s * i // tiles for i in range(tiles + 1)]
+    xs_ = o["x"].reshape(n, c, s)
+    partials = torch.stack([torch.stack([xs_[:, :, a:b].sum(dim=(0, 2)) for a, b in zip(cuts, cuts[1:])], 1),
+                            torch.stack([(xs_[:, :, a:b] ** 2).sum(dim=(0, 2)) for a, b in zip(cuts, cuts[1:])], 1)]).contiguous()
+    ws_ = wrapper(True, partials)
+    out = contract("zsv_bn_fwd_train_stats",
+                   lambda p: L.zsv_bn_fwd_train_stats(x, n, c, s, gamma, beta, res, r, p["y"], p["save_mean"], p["save_invstd"], p["running_mean"],
+                                                      p["running_var"], 0.1, 1e-5, partials.data_ptr(), tiles, p["ws"], nb, None),
+                   dict(stat_outs, y=(F32, shape)), {"ws": nb})
+    same_bytes(out["y"], ws_["y"], "bn_fwd_train_stats: y")
+    same_bytes(out["running_mean"], ws_["rm"], "bn_fwd_train_stats: running_mean")
+    same_bytes(out["running_var"], ws_["rv"], "bn_fwd_train_stats: running_var")
+    if not use_res and not relu:
+        pitch = (c + 15) // 16 * 16
+        out = contract("zsv_bn_fwd_train_coeffs",
+                       lambda p: L.zsv_bn_fwd_train_coeffs(x, n, c, s, gamma, beta, p["save_mean"], p["save_invstd"], p["running_mean"], p["running_var"],
+                                                           0.1, 1e-5, None, 0, p["coef"], pitch, p["ws"], nb, None),
+                       dict(stat_outs, coef=(F32, (2, pitch))), {"ws": nb})
+        assert int(torch.count_nonzero(out["coef"][:, c:])) == 0, "coef entries C .. coef_pitch-1 must be zero"
+        rm, rv = o["rm"].clone(), o["rv"].clone()
+        _, coef_w = ops._BatchNormDeferred.apply(o["x"], o["gamma"], o["beta"], rm, rv, 0.1, 1e-5, None)
+        same_bytes(out["coef"], coef_w, "bn_fwd_train_coeffs: coef")
+        same_bytes(out["running_var"], rv, "bn_fwd_train_coeffs: running_var")
+        same_bytes(out["save_mean"], save_mean, "bn_fwd_train_coeffs: save_mean")
+
+    # ---- training backward: every ReLU mode this forward allows, with and without the residual gradient ----
+    # (e): the combination the wrapper itself calls is held to the wrapper's bytes, the others to the fp64 reference with the
+    # tolerance of test_batchnorm_train_fwd_bwd
+    modes = [0] if not relu else ([1] if use_res else [1, 2])
+    wrapper_calls = (0, False) if not relu else ((1, True) if use_res else (2, False))
+
+    def reference(training):
+        t = {k: o[k].double().cpu().requires_grad_() for k in ("x", "gamma", "beta")}
+        y = F.batch_norm(t["x"], o["rm"].double().cpu(), o["rv"].double().cpu(), t["gamma"], t["beta"], training=training, momentum=0.1, eps=1e-5)
+        if use_res:
+            y = y + o["res"].double().cpu()
+        if relu:
+            y = F.relu(y)
+        y.backward(o["dy"].double().cpu())
+        return dict(dx=t["x"].grad, dgamma=t["gamma"].grad, dbeta=t["beta"].grad)
+
+    def check_grads(got, mode, with_dres, wrap, ref, y_saved, name):
+        for k in ("dx", "dgamma", "dbeta"):
+            if (mode, with_dres) == wrapper_calls:
+                same_bytes(got[k], wrap[k], f"{name} mode {mode}: {k}")
+            elif k == "dx" and name == "bn_bwd" and n * s <= 2:
+                # one or two samples per channel (the edge shapes): dx = a * (g - mean(g) - xhat * mean(g * xhat)) cancels to (almost)
+                # nothing, so the fp32 error is relative to the terms of that sum, a * max |dy|, not to the result
+                terms = float((o["gamma"].abs() * save_invstd.abs()).max() * o["dy"].abs().max())
+                err = float((got[k].double().cpu() - ref[k]).abs().max())
+                assert err <= 1e-4 * terms, f"{name} mode {mode}: dx: max err {err:.3e} vs the terms' scale {terms:.3e}"
+            else:
+                T.close(got[k], ref[k], rtol=1e-4, what=f"{name} mode {mode}{', d_residual' if with_dres else ''}: {k}")
+        if with_dres:
+            masked = o["dy"] if not relu else torch.where(y_saved > 0, o["dy"], torch.zeros_like(o["dy"]))
+            assert torch.equal(got["d_residual"], masked), f"{name}: d_residual is the masked dy"
+            if use_res and relu:
+                same_bytes(got["d_residual"], wrap["dres"], f"{name}: d_residual")
+
+    ref_t = reference(True)
+    for mode in modes:
+        for with_dres in (False, True):
+            outs = {"dx": (F32, shape), "dgamma": (F32, (c,)), "dbeta": (F32, (c,))}
+            if with_dres:
+                outs["d_residual"] = (F32, shape)
+            got = contract(f"zsv_bn_bwd (relu mode {mode}{', d_residual' if with_dres else ''})",
+                           lambda p: L.zsv_bn_bwd(dy, x, y_fwd.data_ptr() if mode == 1 else None, n, c, s, gamma, beta, save_mean.data_ptr(),
+                                                  save_invstd.data_ptr(), mode, p["dx"], p.get("d_residual"), p["dgamma"], p["dbeta"],
+                                                  p["ws"], nb, None), outs, {"ws": nb})
+            check_grads(got, mode, with_dres, wt, ref_t, y_fwd, "bn_bwd")
+
+    # ---- frozen statistics: forward and backward ----
+    we = wrapper(False)
+    rm_, rv_ = o["rm"].data_ptr(), o["rv"].data_ptr()
+    ye = contract("zsv_bn_fwd_eval", lambda p: L.zsv_bn_fwd_eval(x, n, c, s, gamma, beta, rm_, rv_, res, r, 1e-5, p["y"], p["ws"], nb, None),
+                  {"y": (F32, shape)}, {"ws": nb})["y"]
+    same_bytes(ye, we["y"], "bn_fwd_eval: y")
+    ref_e = reference(False)
+    for mode in modes:
+        for with_dres in (False, True):
+            outs = {"dx": (F32, shape), "dgamma": (F32, (c,)), "dbeta": (F32, (c,))}
+            if with_dres:
+                outs["d_residual"] = (F32, shape)
+            got = contract(f"zsv_bn_bwd_eval (relu mode {mode}{', d_residual' if with_dres else ''})",
+                           lambda p: L.zsv_bn_bwd_eval(dy, x, ye.data_ptr() if mode == 1 else None, n, c, s, gamma, beta, rm_, rv_, 1e-5, mode,
+                                                       p["dx"], p.get("d_residual"), p["dgamma"], p["dbeta"], p["ws"], nb, None), outs, {"ws": nb})
+            check_grads(got, mode, with_dres, we, ref_e, ye, "bn_bwd_eval")
+    ROWS_RUN[("BN_CASES", "bn")].add(shape)
+
+
+# =========================================================================================================================
+# dense head and nearest class
+# =========================================================================================================================
+@pytest.mark.parametrize("rows,fin,fout,relu", params_of(T.test_linear))
+def test_linear_entry_points(rows, fin, fout, relu):
+    L = lib()
+    g = torch.Generator().manual_seed(rows + fin)
+    x, w, b, dy = (t.to(DEV) for t in (torch.randn(rows, fin, generator=g), torch.randn(fout, fin, generator=g) / np.sqrt(fin),
+                                       torch.randn(fout, generator=g), torch.randn(rows, fout, generator=g)))
+    with torch.no_grad():
+        yw = ops.linear(x, w, b, relu=relu)
+    xg2, wg2 = x.clone().requires_grad_(), w.clone().requires_grad_()
+    ops.linear(xg2, wg2, None).backward(dy)                               # plain: dy reaches dgrad / wgrad unmasked
+    torch.cuda.synchronize()
+    nf, nd, nw = (int(f(rows, fin, fout)) for f in (L.zsv_linear_fwd_workspace_bytes, L.zsv_linear_dgrad_workspace_bytes, L.zsv_linear_wgrad_workspace_bytes))
+    y = contract("zsv_linear_fwd", lambda p: L.zsv_linear_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), p["y"], rows, fin, fout, 1 if relu else 0,
+                                                              p["ws"], nf, None), {"y": (F32, (rows, fout))}, {"ws": nf}, shifted=True)["y"]
+    same_bytes(y, yw.detach(), "linear_fwd")
+    dx = contract("zsv_linear_dgrad", lambda p: L.zsv_linear_dgrad(dy.data_ptr(), w.data_ptr(), p["dx"], rows, fin, fout, p["ws"], nd, None),
+                  {"dx": (F32, (rows, fin))}, {"ws": nd}, shifted=True)["dx"]
+    same_bytes(dx, xg2.grad, "linear_dgrad")
+    dw = contract("zsv_linear_wgrad", lambda p: L.zsv_linear_wgrad(x.data_ptr(), dy.data_ptr(), p["dw"], rows, fin, fout, p["ws"], nw, None),
+                  {"dw": (F32, (fout, fin))}, {"ws": nw}, shifted=True)["dw"]
+    same_bytes(dw, wg2.grad, "linear_wgrad")
+    ROWS_RUN[("test_linear", "linear")].add((rows, fin, fout))
+
+
+@pytest.mark.parametrize("rows,n_classes,dim,k", params_of(TA.test_cosine_topk_c_abi_against_scipy))
+def test_cosine_topk(rows, n_classes, dim, k):
+    """The workspace is the (rows, n_classes rounded up to 16) double distance matrix: the top-k must not look at its pad columns."""
+    L = lib()
+    g = torch.Generator().manual_seed(rows * 1000 + n_classes)
+    e, c = torch.randn(rows, dim, generator=g) * 3.0, torch.randn(n_classes, dim, generator=g)
+    if n_classes > 8:
+        c[7] = c[2]
+    e, c = e.to(DEV), c.to(DEV)
+    nb = int(L.zsv_cosine_topk_workspace_bytes(rows, n_classes))
+    out = contract("zsv_cosine_topk", lambda p: L.zsv_cosine_topk(e.data_ptr(), c.data_ptr(), rows, dim, n_classes, k, p["out_index"], p["out_dist"],
+                                                                  p["ws"], nb, None),
+                   {"out_index": (I32, (rows, k)), "out_dist": (F64, (rows, k))}, {"ws": nb})
+    assert torch.equal(out["out_index"].long(), train.nearest_classes(e, c, k))
+    out2 = contract("zsv_cosine_topk (no distances)", lambda p: L.zsv_cosine_topk(e.data_ptr(), c.data_ptr(), rows, dim, n_classes, k, p["out_index"], None,
+                                                                                 p["ws"], nb, None), {"out_index": (I32, (rows, k))}, {"ws": nb})
+    same_bytes(out2["out_index"], out["out_index"], "cosine_topk without distances")
+    ec, cc = e.double().cpu(), c.double().cpu()
+    full = 1 - (ec @ cc.t()) / (ec.norm(dim=1, keepdim=True) * cc.norm(dim=1).view(1, -1))
+    assert float((out["out_dist"].cpu() - full.gather(1, out["out_index"].long().cpu())).abs().max()) < 1e-13
+    ROWS_RUN[("test_cosine_topk", "topk")].add((rows, n_classes, dim, k))
+
+
+# =========================================================================================================================
+# bf16 / fp8 path
+# =========================================================================================================================
+def _cl_random(shape5, channels, g, scale=1.0):
+    """[N][T][H][W][Cp] fp32 values on the host, pad channels zero."""
+    t = torch.randn(shape5, generator=g) * scale
+    t[..., channels:] = 0
+    return t
+
+
+def _bf16_forward_operands(case):
+    g = torch.Generator().manual_seed(zlib.crc32(("contract" + case.name).encode()))
+    geo = BX._geometry(case.cin, case.cout, case.kernel, case.stride, case.padding)
+    t, h, w = case.thw
+    if geo.folded:
+        xb, wo = geo.clip_input(torch.randn((case.n, case.cin) + case.thw, generator=g).to(DEV))
+        d = geo.desc(case.n, t, xb.shape[2], xb.shape[3], wo)
+    else:
+        d = geo.desc(case.n, t, h, w)
+        cp = inference.channel_pitch(case.cin)
+        xb = _cl_random((case.n, t, h, w, cp), case.cin, g).to(DEV).to(BF16)
+    k = case.cin * numel(case.kernel)
+    wgt = (torch.randn((case.cout, case.cin) + case.kernel, generator=g) / np.sqrt(k)).to(DEV)
+    scale, shift = (torch.rand(case.cout, generator=g) + 0.5).to(DEV), torch.randn(case.cout, generator=g).to(DEV)
+    ys = (d.N, d.To, d.Ho, d.Wo, inference.channel_pitch(case.cout))
+    return d, xb, wgt, scale, shift, ys, g
+
+
+@pytest.mark.parametrize("case", X.FORWARD_CASES, ids=[c.name for c in X.FORWARD_CASES])
+def test_bf16_blob_and_forward(case, monkeypatch):
+    L = lib()
+    d, xb, wgt, scale, shift, ys, g = _bf16_forward_operands(case)
+    rb = _cl_random(ys, case.cout, g).to(DEV).to(BF16) if case.residual else None
+    nb = int(L.zsv_conv3d_bf16_blob_bytes(byref(d)))
+    assert nb > 0
+    for knob in BX._routes(case):
+        if knob:
+            monkeypatch.setenv(knob, "1")
+        y = contract("zsv_conv3d_bf16_pack + zsv_conv3d_bf16_fwd",
+                     lambda p: [L.zsv_conv3d_bf16_pack(byref(d), wgt.data_ptr(), scale.data_ptr(), shift.data_ptr(), p["blob"], None),
+                                L.zsv_conv3d_bf16_fwd(byref(d), xb.data_ptr(), p["blob"], ops._ptr(rb), 1 if case.relu else 0, p["y"], None)],
+                     {"y": (BF16, ys)}, {"blob": nb})["y"]
+        same_bytes(y, inference.conv_bf16(d, xb, inference.pack_conv(d, wgt, scale, shift), rb, case.relu), f"{case.name} {knob or ''}: y")
+        assert int(torch.count_nonzero(y[..., case.cout:].float())) == 0, "pad channels must be written as zero"
+        if knob:
+            monkeypatch.delenv(knob)
+    ROWS_RUN[("FORWARD_CASES", "bf16_fwd")].add(case.name)
+
+
+@pytest.mark.parametrize("case", X.STATS_CASES, ids=[c.name for c in X.STATS_CASES])
+def test_bf16_statistics_epilogue(case):
+    L = lib()
+    fc = X.FwdCase(case.name, case.n, case.cin, case.cout, case.thw, case.kernel, case.stride, case.padding, False, False)
+    d, xb, wgt, _, _, ys, g = _bf16_forward_operands(fc)
+    nb = int(L.zsv_conv3d_bf16_blob_bytes(byref(d)))
+    cap = int(L.zsv_conv3d_bf16_stat_rows(byref(d)))
+    assert nb > 0 and cap > 0
+    cp = ys[-1]
+    rows = ctypes.c_int32(0)
+
+    def launch(p):
+        rows.value = 0
+        return [L.zsv_conv3d_bf16_pack(byref(d), wgt.data_ptr(), None, None, p["blob"], None),
+                L.zsv_conv3d_bf16_fwd_stats(byref(d), xb.data_ptr(), p["blob"], p["y"], p["bn_partials"], cap, byref(rows), None)]
+
+    out = contract("zsv_conv3d_bf16_fwd_stats", launch, {"y": (BF16, ys), "bn_partials": (F32, (cap, 2, cp))}, {"blob": nb},
+                   defined=lambda name, v: v[:rows.value] if name == "bn_partials" else v)
+    assert 0 < rows.value <= cap
+    z, partials, rows_w = amp.conv_bf16_stats(d, xb, amp.pack_conv(d, wgt, None, None))
+    assert rows_w == rows.value
+    same_bytes(out["y"], z, f"{case.name}: z")
+    same_bytes(out["bn_partials"], partials[:rows_w], f"{case.name}: partials")
+    ROWS_RUN[("STATS_CASES", "bf16_fwd_stats")].add(case.name)
+
+
+@pytest.mark.parametrize("case", X.DGRAD_CASES, ids=[c.name for c in X.DGRAD_CASES])
+def test_bf16_dgrad_blob_and_forward(case):
+    """The input-gradient problems of a convolution exactly as amp.Bf16TrainPath._dgrad forms them (one per residue class of a
+    strided convolution), each packed into a guarded blob of exactly its size."""
+    L = lib()
+    g = torch.Generator().manual_seed(zlib.crc32(("contract" + case.name).encode()))
+    n, cin, t, h, w_ = case.xs
+    _, u = BX._unit(case)
+    d = u.desc(n, t, h, w_)
+    cp = inference.channel_pitch(case.cout)
+    dz = _cl_random((n, d.To, d.Ho, d.Wo, cp), case.cout, g).to(DEV).to(BF16)
+    w = u.conv.weight.detach()
+    axes = [amp.Bf16TrainPath._axis_classes(k, p, s, n_in, n_out) for k, p, s, n_in, n_out in
+            zip(u.kernel, u.padding, u.stride, (d.Ti, d.Hi, d.Wi), (d.To, d.Ho, d.Wo))]
+    st, sh, sw = u.stride
+    problems = 0
+    for ct in axes[0]:
+        for ch in axes[1]:
+            for cw in axes[2]:
+                if ct[2] == 0 or ch[2] == 0 or cw[2] == 0:
+                    continue
+                sub = w[:, :, ct[1]::st, ch[1]::sh, cw[1]::sw].contiguous()
+                kernel, pads = (ct[2], ch[2], cw[2]), (ct[3], ch[3], cw[3])
+                if all(len(a) == 1 for a in axes):
+                    dims = (d.Ti, d.Hi, d.Wi)
+                else:
+                    dims = tuple(n_out + 2 * c[3] - c[2] + 1 for c, n_out in zip((ct, ch, cw), (d.To, d.Ho, d.Wo)))
+                d2 = _lib.ConvDesc(n, u.cout, d.To, d.Ho, d.Wo, u.cin, dims[0], dims[1], dims[2], kernel[0], kernel[1], kernel[2], 1, 1, 1, *pads)
+                nb = int(L.zsv_conv3d_bf16_blob_bytes(byref(d2)))
+                assert nb > 0
+                ys = (n,) + dims + (inference.channel_pitch(u.cin),)
+                y = contract("zsv_conv3d_bf16_pack_dgrad + zsv_conv3d_bf16_fwd",
+                             lambda p: [L.zsv_conv3d_bf16_pack_dgrad(byref(d2), sub.data_ptr(), p["blob"], None),
+                                        L.zsv_conv3d_bf16_fwd(byref(d2), dz.data_ptr(), p["blob"], None, 0, p["y"], None)],
+                             {"y": (BF16, ys)}, {"blob": nb}, count=problems == 0)["y"]
+                same_bytes(y, amp.Bf16TrainPath._dgrad_problem(u, dz, sub, kernel, pads, dims), f"{case.name}: class problem {kernel}")
+                problems += 1
+    assert problems > 0
+    ROWS_RUN[("DGRAD_CASES", "bf16_pack_dgrad")].add(case.name)
+
+
+@pytest.mark.parametrize("case", X.WGRAD_CASES, ids=[c.name for c in X.WGRAD_CASES])
+def test_bf16_weight_gradient(case):
+    L = lib()
+    g = torch.Generator().manual_seed(zlib.crc32(("contract" + case.name).encode()))
+    n, cin, t, h, w_ = case.xs
+    _, u = BX._unit(case)
+    d = u.desc(n, t, h, w_)
+    x = _cl_random((n, t, h, w_, inference.channel_pitch(cin)), cin, g).to(DEV).to(BF16)
+    dz = _cl_random((n, d.To, d.Ho, d.Wo, inference.channel_pitch(case.cout)), case.cout, g).to(DEV).to(BF16)
+    nb = int(L.zsv_conv3d_bf16_wgrad_workspace_bytes(byref(d)))
+    assert nb > 0, "the native kernel must take this geometry"
+    ws = (case.cout, cin) + tuple(case.kernel)
+    dw = contract("zsv_conv3d_bf16_wgrad", lambda p: L.zsv_conv3d_bf16_wgrad(byref(d), x.data_ptr(), dz.data_ptr(), p["dw"], p["ws"], nb, None),
+                  {"dw": (F32, ws)}, {"ws": nb}, shifted=True)["dw"]
+    rec = amp._Record()
+    rec.unit, rec.desc, rec.x, rec.clips = u, d, x, None
+    want = amp.Bf16TrainPath._wgrad(rec, dz)
+    ops.join_wgrad_streams()
+    torch.cuda.synchronize()
+    same_bytes(dw, want, f"{case.name}: dW")
+    ROWS_RUN[("WGRAD_CASES", "bf16_wgrad")].add(case.name)
+
+
+BN_CL_CASES = params_of(BX.test_batchnorm_forward_is_the_arithmetic_its_header_states)
+
+
+@pytest.mark.parametrize("shape,relu,res", BN_CL_CASES, ids=[f"{'x'.join(map(str, s))}{'_relu' if r else ''}{'_res' if q else ''}" for s, r, q in BN_CL_CASES])
+def test_channels_last_batchnorm_entry_points(shape, relu, res):
+    L = lib()
+    n, c = shape[:2]
+    g = torch.Generator().manual_seed(c * 11 + shape[2])
+    cp = inference.channel_pitch(c)
+    cl = (n,) + tuple(shape[2:]) + (cp,)
+    z = (_cl_random(cl, c, g, 1.5) + 0.3 * (torch.arange(cp) < c)).to(DEV).to(BF16)
+    rb = _cl_random(cl, c, g).to(DEV).to(BF16) if res else None
+    dy = _cl_random(cl, c, g).to(DEV).to(BF16)
+    bn = BX._bn(c, g)
+    rows = numel(cl[:-1])
+    nb = int(L.zsv_bn_cl_workspace_bytes(rows, c))
+    assert nb > 0
+    r = 1 if relu else 0
+    gamma, beta = bn.weight.data_ptr(), bn.bias.data_ptr()
+    rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
+
+    def fresh_bn():
+        with torch.no_grad():
+            bn.running_mean.copy_(rm0)
+            bn.running_var.copy_(rv0)
+        return bn
+
+    outs = {"y": (BF16, cl), "save_mean": (F32, (c,)), "save_invstd": (F32, (c,)), "save_coef": (F32, (2, cp)),
+            "running_mean": (F32, (c,), rm0), "running_var": (F32, (c,), rv0)}
+    out = contract("zsv_bn_cl_fwd_train",
+                   lambda p: L.zsv_bn_cl_fwd_train(z.data_ptr(), ops._ptr(rb), rows, c, gamma, beta, p["running_mean"], p["running_var"], 0.1, bn.eps, r,
+                                                   p["y"], p["save_mean"], p["save_invstd"], p["save_coef"], p["ws"], nb, None), outs, {"ws": nb})
+    yw, mean, invstd, coef = amp.bn_cl_fwd_train(z, fresh_bn(), rb, relu, want_coef=True)
+    torch.cuda.synchronize()
+    for name, want in (("y", yw), ("save_mean", mean), ("save_invstd", invstd), ("save_coef", coef), ("running_mean", bn.running_mean),
+                       ("running_var", bn.running_var)):
+        same_bytes(out[name], want.detach(), f"bn_cl_fwd_train: {name}")
+    # the same from a convolution's epilogue partials: [rows][2][Cp], three row blocks over the voxels
+    blocks = min(3, rows)
+    cuts = [rows * i // blocks for i in range(blocks + 1)]
+    zf = z.reshape(rows, cp).float()
+    partials = torch.stack([torch.stack([zf[a:b].sum(0), (zf[a:b] ** 2).sum(0)]) for a, b in zip(cuts, cuts[1:])]).contiguous()
+    out2 = contract("zsv_bn_cl_fwd_train_stats",
+                    lambda p: L.zsv_bn_cl_fwd_train_stats(z.data_ptr(), ops._ptr(rb), rows, c, gamma, beta, p["running_mean"], p["running_var"], 0.1, bn.eps,
+                                                          r, p["y"], p["save_mean"], p["save_invstd"], p["save_coef"], partials.data_ptr(), blocks,
+                                                          p["ws"], nb, None), outs, {"ws": nb})
+    yw2, mean2, invstd2, coef2 = amp.bn_cl_fwd_train(z, fresh_bn(), rb, relu, want_coef=True, conv_stats=(partials, blocks))
+    torch.cuda.synchronize()
+    for name, want in (("y", yw2), ("save_mean", mean2), ("save_invstd", invstd2), ("save_coef", coef2), ("running_var", bn.running_var)):
+        same_bytes(out2[name], want.detach(), f"bn_cl_fwd_train_stats: {name}")
+
+    # ---- backward: the mask from the saved output, and (no residual) recomputed from z ----
+    grads = {"dz": (BF16, cl), "g_out": (BF16, cl), "dgamma": (F32, (c,)), "dbeta": (F32, (c,))}
+    y_saved = out["y"]
+    forms = [False] + ([True] if (relu and not res) else [])
+    for recompute in forms:
+        o = contract("zsv_bn_cl_bwd" + (" (mask recomputed from z)" if recompute else ""),
+                     lambda p: L.zsv_bn_cl_bwd(dy.data_ptr(), y_saved.data_ptr() if (relu and not recompute) else None, z.data_ptr(), rows, c, gamma,
+                                               mean.data_ptr(), invstd.data_ptr(), coef.data_ptr() if recompute else None, r, p["dz"], p["g_out"],
+                                               p["dgamma"], p["dbeta"], p["ws"], nb, None), grads, {"ws": nb})
+        dzw, gw, dgw, dbw = amp.bn_cl_bwd(dy, yw, z, bn, mean, invstd, relu, want_g=True, fwd_coef=coef if recompute else None)
+        torch.cuda.synchronize()
+        for name, want in (("dz", dzw), ("g_out", gw), ("dgamma", dgw), ("dbeta", dbw)):
+            same_bytes(o[name], want, f"bn_cl_bwd: {name}")
+    # ---- frozen statistics ----
+    ye, coef4 = amp.bn_cl_fwd_eval(z, bn.eval(), rb, relu)
+    for use_y in ([True, False] if relu else [False]):
+        if relu and not use_y and res:
+            continue                                       # (the recomputed mask is the forward's only without a residual)
+        o = contract("zsv_bn_cl_bwd_eval" + ("" if use_y or not relu else " (mask recomputed from z)"),
+                     lambda p: L.zsv_bn_cl_bwd_eval(dy.data_ptr(), ye.data_ptr() if use_y else None, z.data_ptr(), rows, c, coef4.data_ptr(), r, p["dz"],
+                                                    p["g_out"], p["dgamma"], p["dbeta"], p["ws"], nb, None), grads, {"ws": nb})
+        dzw, gw, dgw, dbw = amp.bn_cl_bwd_eval(dy, ye if use_y else None, z, bn, coef4, relu, want_g=True)
+        torch.cuda.synchronize()
+        for name, want in (("dz", dzw), ("g_out", gw), ("dgamma", dgw), ("dbeta", dbw)):
+            same_bytes(o[name], want, f"bn_cl_bwd_eval: {name}")
+    bn.train()
+    # ---- C3D's relu(conv + bias) backward on the same tensors ----
+    o = contract("zsv_relu_bias_bwd_cl", lambda p: L.zsv_relu_bias_bwd_cl(dy.data_ptr(), y_saved.data_ptr(), rows, c, p["g_out"], p["dbias"], p["ws"], nb, None),
+                 {"g_out": (BF16, cl), "dbias": (F32, (c,))}, {"ws": nb})
+    gw, dbw = amp.relu_bias_bwd_cl(dy, y_saved, c)
+    torch.cuda.synchronize()
+    same_bytes(o["g_out"], gw, "relu_bias_bwd_cl: g")
+    same_bytes(o["dbias"], dbw, "relu_bias_bwd_cl: dbias")
+    ROWS_RUN[("bn_cl", "bn_cl")].add((tuple(shape), relu, res))
+
+
+@pytest.mark.parametrize("case", F8.CASES, ids=[f"c{i}" for i in range(len(F8.CASES))])
+def test_fp8_blob_and_forward(case):
+    L = lib()
+    n, cin, cout, thw, k, s, p, use_res, relu = case
+    t, h, w = thw
+    g = torch.Generator().manual_seed(zlib.crc32(str(case).encode()))
+    wgt = (torch.randn((cout, cin) + k, generator=g) / np.sqrt(cin * numel(k))).to(DEV)
+    shift = (torch.randn(cout, generator=g) * 8.0).to(DEV)
+    d = ops.conv_desc((n, cin, t, h, w), wgt.shape, s, p)
+    ys = (d.N, d.To, d.Ho, d.Wo, inference.fp8_channel_pitch(cout))
+
+    def e4m3_cl(shape5, channels, scale):
+        v = _cl_random(shape5, channels, g, scale).clamp(-448.0, 448.0).to(F8.FP8)
+        return v.view(U8).to(DEV).view(F8.FP8)
+
+    xb = e4m3_cl((n, t, h, w, inference.fp8_channel_pitch(cin)), cin, 4.0)
+    rb = e4m3_cl(ys, cout, 8.0) if use_res else None
+    nb = int(L.zsv_conv3d_fp8_blob_bytes(byref(d)))
+    assert nb > 0
+    y = contract("zsv_conv3d_fp8_pack + zsv_conv3d_fp8_fwd",
+                 lambda q: [L.zsv_conv3d_fp8_pack(byref(d), wgt.data_ptr(), None, shift.data_ptr(), q["blob"], None),
+                            L.zsv_conv3d_fp8_fwd(byref(d), xb.data_ptr(), q["blob"], ops._ptr(rb), 1 if relu else 0, q["y"], None)],
+                 {"y": (U8, ys)}, {"blob": nb})["y"]
+    want = inference.conv_fp8(d, xb, inference.pack_conv_fp8(d, wgt, None, shift), rb, relu)
+    same_bytes(y, want.view(U8), "conv_fp8: y")
+    assert int(torch.count_nonzero(y[..., cout:])) == 0, "pad channels must be written as zero"
+    ROWS_RUN[("fp8 CASES", "fp8_fwd")].add(case)
+
+
+# =========================================================================================================================
+# nothing was skipped
+# =========================================================================================================================
+ENTRY_POINTS = [
+    "zsv_conv3d_fwd_full", "zsv_conv3d_fwd_full (bias + ReLU)", "zsv_conv3d_fwd_full (residual)", "zsv_conv3d_fwd_full (statistics)",
+    "zsv_conv3d_fwd_pre", "zsv_conv3d_dgrad", "zsv_conv3d_dgrad_add", "zsv_conv3d_dgrad_add_strided", "zsv_conv3d_wgrad", "zsv_conv3d_wgrad_masked",
+    "zsv_conv3d_wgrad_pre", "zsv_pack_multi + zsv_conv3d_fwd_full_panel", "zsv_pack_multi + zsv_conv3d_dgrad_add_panel",
+    "zsv_pack_multi + zsv_conv3d_fwd_pre_panel", "zsv_pack_multi + zsv_conv3d_dgrad_add_strided_panel",
+    "zsv_channel_sum", "zsv_relu_bwd_bias", "zsv_bn_fwd_train", "zsv_bn_fwd_train_stats", "zsv_bn_fwd_train_coeffs", "zsv_bn_fwd_eval",
+    "zsv_bn_bwd (relu mode 0)", "zsv_bn_bwd (relu mode 0, d_residual)", "zsv_bn_bwd (relu mode 1)", "zsv_bn_bwd (relu mode 1, d_residual)",
+    "zsv_bn_bwd (relu mode 2)", "zsv_bn_bwd (relu mode 2, d_residual)", "zsv_bn_bwd_eval (relu mode 0)", "zsv_bn_bwd_eval (relu mode 0, d_residual)",
+    "zsv_bn_bwd_eval (relu mode 1)", "zsv_bn_bwd_eval (relu mode 1, d_residual)", "zsv_bn_bwd_eval (relu mode 2)",
+    "zsv_bn_bwd_eval (relu mode 2, d_residual)", "zsv_linear_fwd", "zsv_linear_dgrad", "zsv_linear_wgrad", "zsv_cosine_topk", "zsv_cosine_topk (no distances)",
+    "zsv_conv3d_bf16_pack + zsv_conv3d_bf16_fwd", "zsv_conv3d_bf16_pack_dgrad + zsv_conv3d_bf16_fwd", "zsv_conv3d_fp8_pack + zsv_conv3d_fp8_fwd",
+    "zsv_conv3d_bf16_fwd_stats", "zsv_bn_cl_fwd_train", "zsv_bn_cl_fwd_train_stats", "zsv_bn_cl_bwd", "zsv_bn_cl_bwd (mask recomputed from z)",
+    "zsv_bn_cl_bwd_eval", "zsv_bn_cl_bwd_eval (mask recomputed from z)", "zsv_relu_bias_bwd_cl", "zsv_conv3d_bf16_wgrad",
+]
+
+
+def test_every_entry_point_ran_and_on_every_row(capsys):
+    """Run the file as a whole: this test reads what the tests above recorded."""
+    with capsys.disabled():
+        print("\nworkspace / output contract: (entry point, case x switch combinations run)")
+        for name in sorted(COUNTS):
+            print(f"  {name:68s} {COUNTS[name]:5d}")
+    assert COUNTS, "nothing was recorded: this test reads what the other tests of the file record -- run the file as a whole, in order"
+    missing = [e for e in ENTRY_POINTS if COUNTS[e] == 0]
+    assert not missing, f"entry points that ran on no case (was the whole file run?): {missing}"
+    for table in CONV_TABLES:
+        names = {r.name for r in CONV_ROWS if r.table == table}
+        assert len(names) >= (1 if table == "slab_sum_rows" else 2), f"{table}: GPU_ROW_LIMIT left {len(names)} row(s)"
+        for call in ("fwd", "dgrad", "wgrad"):
+            assert ROWS_RUN[(table, call)] == names, f"{table}: the plain {call} call missed {sorted(names - ROWS_RUN[(table, call)])}"
+    expected = {("PANEL_CASES", "panel"): len(PANEL_ROWS), ("BN_CASES", "bn"): len(BN_SHAPES), ("BN_CASES", "channel_sum"): len(BN_SHAPES),
+                ("test_linear", "linear"): len(params_of(T.test_linear)),
+                ("test_cosine_topk", "topk"): len(params_of(TA.test_cosine_topk_c_abi_against_scipy)),
+                ("FORWARD_CASES", "bf16_fwd"): len(X.FORWARD_CASES), ("STATS_CASES", "bf16_fwd_stats"): len(X.STATS_CASES),
+                ("DGRAD_CASES", "bf16_pack_dgrad"): len(X.DGRAD_CASES), ("WGRAD_CASES", "bf16_wgrad"): len(X.WGRAD_CASES),
+                ("bn_cl", "bn_cl"): len(BN_CL_CASES), ("fp8 CASES", "fp8_fwd"): len(F8.CASES)}
+    for key, count in expected.items():
+        assert len(ROWS_RUN[key]) == count, f"{key}: {len(ROWS_RUN[key])} of {count} rows ran"

@@ -297,6 +297,12 @@ __device__ __forceinline__ void epilogue(const Bf16Params& prm, f32x4 (&acc)[TM]
             const int col = voxel(c);
             if (col < prm.P) *(u32x2*)(Y + (size_t)col * prm.CoutP + covered + 4 * k) = u32x2{0u, 0u};
         }
+        // ... and so do their statistics (the sums of those zeros): bn_cl_fwd_finalize_kernel reads whole [2][CoutP] rows
+        if (stats && tid < prm.CoutP - covered) {
+            float* out = prm.stat + (size_t)tn * 2 * prm.CoutP + covered + tid;
+            out[0] = 0.f;
+            out[prm.CoutP] = 0.f;
+        }
     }
 }
 
