@@ -10,6 +10,7 @@
  *   - all tensors are contiguous fp32, channel-major "NCS": (N, C, T, H, W) with
  *     S = T*H*W; pointers are device pointers owned by the caller;
  *   - kernels never allocate: workspaces are passed in (query the size first);
+ *   - no byte outside the stated extent of an input may influence a result, and no input (const pointer) is written;
  *   - `stream` is a hipStream_t passed as void*; launches are asynchronous on it;
  *   - return value: 0 = OK, otherwise a ZSV_E_* code (zsv_status_string() names it);
  *     nothing throws across this boundary;

@@ -90,3 +90,120 @@ def test_one_unwritten_element_fails_the_every_element_written_check(dtype):
 def _prefill_scalar(dtype):
     size = torch.empty((), dtype=dtype).element_size()
     return torch.full((size,), 0xFF, dtype=torch.uint8).view(dtype)[0]
+
+
+# ---- the guard byte is the instance's own ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("guard_byte", [G.GUARD_BYTE] + list(G.BAND_BYTES))
+def test_check_passes_and_fails_against_the_instance_s_own_guard_byte(guard_byte):
+    b = G.guarded(52, "cpu", 0x00, guard_byte=guard_byte)
+    assert b.guard_byte == guard_byte
+    assert bool((b.buf[:b.start] == guard_byte).all()) and bool((b.buf[b.end:] == guard_byte).all())
+    b.check()
+    b.payload.fill_(0x3C)
+    b.check()
+    other = G.GUARD_BYTE if guard_byte != G.GUARD_BYTE else 0xFF     # the default byte is a change in a poisoned band, and the reverse
+    b.buf[b.end + 5] = other
+    b.buf[b.start - 3] = other
+    with pytest.raises(AssertionError) as e:
+        b.check("x")
+    assert "first at payload_end+5, last at payload_end+5" in str(e.value)              # the offsets mean what they meant
+    assert "first at payload_start-3, last at payload_start-3" in str(e.value)
+    assert "x (52 bytes" in str(e.value)
+    assert (f"guard byte 0x{guard_byte:02X}" in str(e.value)) == (guard_byte != G.GUARD_BYTE)
+    with pytest.raises(ValueError):
+        G.guarded(4, "cpu", 0, guard_byte=256)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.bfloat16, torch.int32, torch.uint8, torch.float8_e4m3fn])
+@pytest.mark.parametrize("guard_byte", G.BAND_BYTES)
+def test_guarded_copy_round_trips_the_bytes_in_an_exact_extent(dtype, guard_byte):
+    shape = (3, 5, 7)
+    src = (torch.arange(105).view(shape) - 50).to(torch.float32).to(dtype)
+    view = src.transpose(0, 2)                                       # a non-contiguous operand: placed in contiguous order
+    for t in (src, view, src[:0], src[0, 0, 0]):
+        b = G.guarded_copy(t, "cpu", guard_byte)
+        assert b.nbytes == t.numel() * t.element_size() and b.end - b.start == b.nbytes
+        assert b.ptr % 256 == 0 and b.guard_byte == guard_byte
+        assert torch.equal(b.bytes(), t.contiguous().reshape(-1).view(torch.uint8))
+        assert bool((b.buf[b.start - G.GUARD_BYTES:b.start] == guard_byte).all())
+        assert bool((b.buf[b.end:b.end + G.GUARD_BYTES] == guard_byte).all())
+        b.check()
+    for shift in (2, 14):
+        b = G.guarded_copy(src, "cpu", guard_byte, align=16, shift=shift)
+        assert b.ptr % 16 == shift and torch.equal(b.bytes(), src.reshape(-1).view(torch.uint8))
+    assert bool((G.guarded_copy(src, "cpu").buf[:G.GUARD_BYTES] == G.GUARD_BYTE).all())
+
+
+def test_what_the_band_bytes_read_as():
+    """The values the comment at guarded.BAND_BYTES promises."""
+    ff, sf = (torch.full((8,), b, dtype=torch.uint8) for b in G.BAND_BYTES)
+    for dtype in (torch.float32, torch.float64, torch.bfloat16):
+        assert bool(torch.isnan(ff.view(dtype)).all())
+    assert bool(torch.isnan(ff.view(torch.float8_e4m3fn).float()).all())
+    assert bool((ff.view(torch.int32) == -1).all()) and bool((ff == 255).all())
+    assert 3.38e38 < float(sf.view(torch.float32)[0]) < 3.4e38 and 3.38e38 < float(sf.view(torch.bfloat16)[0].float()) < 3.4e38
+    assert bool(torch.isfinite(sf.view(torch.float32)).all())
+    # e4m3: 0x7F is the positive NaN code, the largest positive pattern when the codes are compared as sign-magnitude integers
+    assert int(sf[0]) == max(range(0x80))
+
+
+# ---- the checker catches what it is for: three "kernels" that read one element past a guarded input ---------------------------
+def _input_and_one_past(values, band):
+    """The input as the kernel is given it (exactly its extent) and as a kernel with an off-by-one bound sees it."""
+    import numpy as np
+    b = G.guarded_copy(torch.from_numpy(values), "cpu", band)
+    n = values.size
+    return b, b.buf[b.start:b.end + 4].numpy().view(np.float32), n
+
+
+def _k_sum(x, n, over):
+    import numpy as np
+    return np.asarray([x[:n + over].sum(dtype=np.float32)])
+
+
+def _k_window_max(x, n, over):
+    """fmaxf over windows of 4; the last window runs ``over`` elements long."""
+    import numpy as np
+    out = np.fmax.reduce(x[:n].reshape(-1, 4), axis=1)
+    if over:
+        out[-1] = np.fmax(out[-1], x[n])
+    return out
+
+
+def _k_relu_mask(y, n, over, dy):
+    """dx[i] = y[i] > 0 ? dy[i] : 0, with the mask of the last element taken one element late."""
+    import numpy as np
+    idx = np.arange(n)
+    if over:
+        idx[-1] += 1
+    with np.errstate(invalid="ignore"):
+        return np.where(y[idx] > 0, dy, np.float32(0))
+
+
+def _run_kernel(kind, band, over):
+    import numpy as np
+    rng = np.random.default_rng(7)
+    x = rng.standard_normal(16).astype(np.float32)
+    x[-1] = -abs(x[-1]) - 0.5                           # the mask kernel's last y is negative: the late read decides
+    dy = rng.standard_normal(16).astype(np.float32) + 3.0
+    b, seen, n = _input_and_one_past(x, band)
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = {"sum": lambda: _k_sum(seen, n, over), "max": lambda: _k_window_max(seen, n, over),
+               "mask": lambda: _k_relu_mask(seen, n, over, dy)}[kind]()
+    b.check()                                           # an over-READ changes no band: only the results can tell
+    assert torch.equal(b.bytes(), torch.from_numpy(x).view(torch.uint8))
+    return out.tobytes()
+
+
+@pytest.mark.parametrize("kind,caught_by", [("sum", {0xFF: True, 0x7F: True}), ("max", {0xFF: False, 0x7F: True}),
+                                            ("mask", {0xFF: False, 0x7F: True})])
+def test_two_band_bytes_because_a_nan_band_alone_misses_a_max_type_over_read(kind, caught_by):
+    """The recorded reason for BAND_BYTES: the contract compares a poisoned run's outputs with the ordinary run's, byte for byte.
+    A sum that reads one element too many differs under the NaN band; an fmax or a ``> 0`` mask that does so gives the RIGHT
+    bytes next to a NaN and is only seen next to 3.39e38.  With correct bounds every kernel passes under both."""
+    first = _run_kernel(kind, G.GUARD_BYTE, over=0)
+    for band in G.BAND_BYTES:
+        assert _run_kernel(kind, band, over=0) == first, f"{kind}: correct bounds, band 0x{band:02X}"
+        differs = _run_kernel(kind, band, over=1) != first
+        assert differs == caught_by[band], f"{kind} reading one element past its input, band 0x{band:02X}: caught = {differs}"
+    assert any(caught_by.values())

@@ -1,11 +1,17 @@
 """The C ABI's memory contract (include/zsv_hip.h: "kernels never allocate: workspaces are passed in (query the size first)",
 the caller owns every output), entry point by entry point, with guard bands (tests/guarded.py).
 
-Every (entry point, case) is called through ctypes two or three times.  Each run gets a workspace / blob / panel / mask table /
+Every (entry point, case) is called through ctypes four or five times.  Each run gets a workspace / blob / panel / mask table /
 partials buffer of EXACTLY the queried size and every output in a buffer of exactly its shape, each between two 1 MiB guard
 bands in an allocation of its own; the payloads are prefilled with 0x00 in the first run and 0xFF (NaN / -1 / the e4m3 NaN
 code) in the second; the convolution and weight-gradient cases run a third time with the workspace 16 bytes past a 256-byte
-boundary, the alignment the header promises to accept.  Asserted after one synchronize:
+boundary, the alignment the header promises to accept.  Every INPUT (x, w, dy, residuals, BatchNorm vectors, coefficient rows,
+partials that are consumed) is handed over the same way: its bytes are the payload of a guarded buffer of exactly the extent the
+header states, so the launch sees no tensor of the caching allocator.  Two more runs (prefill 0x00) poison the bands of EVERY
+buffer of the run -- inputs, workspaces, blobs, panels, mask tables, outputs -- with 0xFF and then 0x7F (guarded.BAND_BYTES: a
+NaN that survives every sum and product, then a huge finite value that wins every max and passes every ``> 0``).  Many kernels
+fetch past the logical data on purpose (16-byte pieces, halo voxels, clamped loads) and rely on a mask, a clamp or a buffer
+descriptor's range to keep the value out of the result: these runs pin that.  Asserted after one synchronize:
 
 (a) the call returns ZSV_OK;
 (b) no guard band changed (nothing written before or past a buffer);
@@ -15,7 +21,10 @@ boundary, the alignment the header promises to accept.  Asserted after one synch
     computed from workspace bytes nobody wrote;
 (e) the outputs equal, as raw bytes, what the package's own wrapper (ops / amp / inference / train) returns for the same operands
     under the same switches (the other suites pin those wrappers to fp64 references); where no wrapper exposes the call, the
-    comparison is the one the existing test of that entry point makes, with its tolerance.
+    comparison is the one the existing test of that entry point makes, with its tolerance;
+(f) the outputs of the two poisoned runs equal the first run's as raw bytes: no byte outside the stated extent of an input (or
+    of a workspace) may influence a result;
+(g) no input's band changed and every input's payload holds the bytes it held before the call: inputs are const.
 
 A case is left out for an entry point only where that entry point's own ``*_supported`` / size query says it cannot run the
 geometry.  The case tables are the ones of the other suites (rows with N = 22 or more than about 2 M output elements left out:
@@ -35,13 +44,15 @@ import torch.nn.functional as F
 import bf16_exact_cases as X
 import guarded as G
 import test_accuracy as TA
+import test_amp_gpu as TAMP
 import test_bf16_exact_gpu as BX
+import test_bf16_gpu as TB
 import test_fp8_gpu as F8
 import test_ops_gpu as T
 
 pytestmark = pytest.mark.gpu
 
-from zeroshotvideoclassification_amd import _lib, amp, inference, ops, train  # noqa: E402
+from zeroshotvideoclassification_amd import _lib, amp, inference, ops, preprocess, train  # noqa: E402
 
 DEV = "cuda"
 F32, F64, I32, BF16, U8 = torch.float32, torch.float64, torch.int32, torch.bfloat16, torch.uint8
@@ -68,35 +79,61 @@ def numel(shape):
     return int(np.prod(shape)) if len(shape) else 1
 
 
-def contract(entry, launch, outs, works=None, shifted=False, defined=None, count=True):
+def contract(entry, launch, outs, works=None, shifted=False, defined=None, count=True, ins=None):
     """Run ``launch`` once per payload fill (and once more with the buffers named in ``shifted`` 16 bytes past a 256-byte
-    boundary) on fresh guarded buffers and assert (a) - (d).
+    boundary), then once per poisoned band byte, on fresh guarded buffers and assert (a) - (d), (f), (g).
 
     outs:  name -> (dtype, shape) or (dtype, shape, initial tensor) -- the latter for in / out arguments (running statistics);
     works: name -> bytes: workspaces, blobs, panels, mask tables (prefilled, guarded, not compared);
-    launch(p): p[name] = device address; returns the status, or a list of them;
+    ins:   name -> device tensor of EXACTLY the extent the header states for that argument (None: an operand left out, the
+           launch gets None), or (tensor, shift): the copy starts ``shift`` bytes past a 256-byte boundary;
+    launch(p): p[name] = device address, p["table"](tensor) = the address of a guarded copy of a table the launch itself builds
+           (job and pointer tables hold addresses of this run's buffers); returns the status, or a list of them;
     defined(name, tensor) -> the part of an output the operation defines (default: all of it).
     Returns name -> the first run's output (a copy)."""
-    works = works or {}
-    runs = [(0x00, 0), (0xFF, 0)] + ([(0xFF, 16)] if shifted else [])
+    works, ins = works or {}, ins or {}
+    for name in ins:
+        assert name not in outs and name not in works, f"{entry}: {name} is named twice"
+    runs = [(0x00, 0, G.GUARD_BYTE), (0xFF, 0, G.GUARD_BYTE)] + ([(0xFF, 16, G.GUARD_BYTE)] if shifted else []) + \
+        [(0x00, 0, band) for band in G.BAND_BYTES]
     results = []
-    for fill, shift in runs:
-        bufs, views = {}, {}
+    for fill, shift, band in runs:
+        bufs, views, sources = {}, {}, {}
         for name, spec in outs.items():
-            b = G.guarded_like(spec[0], spec[1], DEV, fill)
+            b = G.guarded_like(spec[0], spec[1], DEV, fill, guard_byte=band)
             views[name] = b.view(spec[0], spec[1])
             if len(spec) > 2:
                 views[name].copy_(spec[2])
             bufs[name] = b
         for name, nbytes in works.items():
-            bufs[name] = G.guarded(nbytes, DEV, fill, 256, shift if (shifted is True or (shifted and name in shifted)) else 0)
-        status = launch({name: b.ptr for name, b in bufs.items()})
+            bufs[name] = G.guarded(nbytes, DEV, fill, 256, shift if (shifted is True or (shifted and name in shifted)) else 0, guard_byte=band)
+        for name, t in ins.items():
+            if t is None:
+                continue
+            t, in_shift = t if isinstance(t, tuple) else (t, 0)
+            bufs[name] = sources[name] = G.guarded_copy(t, DEV, band, 256, in_shift)
+        before = {name: b.bytes() for name, b in sources.items()}
+        p = {name: b.ptr for name, b in bufs.items()}
+        p.update({name: None for name, t in ins.items() if t is None})
+
+        def table(tensor, name="table"):
+            """For a launch that builds a device table of addresses of this run's buffers: the table as one more guarded input."""
+            name = f"{name} #{len(bufs)}"
+            bufs[name] = sources[name] = G.guarded_copy(tensor, DEV, band)
+            before[name] = sources[name].bytes()
+            return sources[name].ptr
+
+        p["table"] = table
+        status = launch(p)
         torch.cuda.synchronize()
-        what = f"{entry}, prefill 0x{fill:02X}" + (", workspace at 256 k + 16" if shift else "")
+        what = f"{entry}, prefill 0x{fill:02X}" + (", workspace at 256 k + 16" if shift else "") + \
+            (f", bands 0x{band:02X}" if band != G.GUARD_BYTE else "")
         for s in (status if isinstance(status, (list, tuple)) else [status]):
             assert s == 0, f"{what}: {lib().zsv_status_string(int(s)).decode()} (status {s})"                    # (a)
         for name, b in bufs.items():
-            b.check(f"{what}: {name}")                                                                         # (b)
+            b.check(f"{what}: {name}")                                                                         # (b), (g)
+        for name, b in sources.items():
+            assert torch.equal(b.payload, before[name]), f"{what}: the input {name} was written (inputs are const)"   # (g)
         got = {}
         for name, v in views.items():
             part = defined(name, v) if defined else v
@@ -104,13 +141,30 @@ def contract(entry, launch, outs, works=None, shifted=False, defined=None, count
                 G.assert_all_written(part, f"{what}: {name}")                                                  # (d)
             got[name] = part.clone()
         results.append(got)
-    for (fill, shift), got in zip(runs[1:], results[1:]):
+    for (fill, shift, band), got in zip(runs[1:], results[1:]):
         for name, v in got.items():
-            assert v.shape == results[0][name].shape and torch.equal(v.contiguous().view(U8), results[0][name].contiguous().view(U8)), \
-                f"{entry}: {name} depends on what the buffers held before the call (prefill 0x00 vs 0x{fill:02X}, shift {shift})"   # (c)
+            first = results[0][name]
+            assert v.shape == first.shape, f"{entry}: {name}: {tuple(v.shape)} vs {tuple(first.shape)}"
+            a, b = v.contiguous().view(-1).view(U8), first.contiguous().view(-1).view(U8)
+            if torch.equal(a, b):
+                continue
+            if band == G.GUARD_BYTE:
+                raise AssertionError(f"{entry}: {name} depends on what the buffers held before the call (prefill 0x00 vs 0x{fill:02X}, "
+                                     f"shift {shift})")                                                        # (c)
+            index = int(torch.nonzero(a != b).flatten()[0]) // v.element_size()
+            raise AssertionError(f"{entry}: {name} depends on bytes OUTSIDE the inputs or the workspace: with bands of 0x{band:02X} "
+                                 f"around every buffer {int((a != b).sum())} byte(s) differ from the ordinary run, first at flat index "
+                                 f"{index} of {v.numel()}")                                                     # (f)
     if count:
         COUNTS[entry] += 1
     return results[0]
+
+
+def pick(o, *names, **renamed):
+    """The operands of one call out of a test's operand dict: ``pick(o, "x", "w", y="x")`` = {x: o[x], w: o[w], y: o[x]}."""
+    d = {k: o[k] for k in names}
+    d.update({k: o[v] for k, v in renamed.items()})
+    return d
 
 
 def same_bytes(got, want, what):
@@ -202,7 +256,6 @@ def _conv_entry_points(row, tag):
     """Every fp32 convolution entry point on one row under the switches in force."""
     L = lib()
     d, ys, o, g = _conv_operands(row)
-    x, w, bias, res, dy, add = (o[k].data_ptr() for k in ("x", "w", "bias", "res", "dy", "add"))
     dp = byref(d)
     nf, nd, nw = int(L.zsv_conv3d_fwd_workspace_bytes(dp)), int(L.zsv_conv3d_dgrad_workspace_bytes(dp)), int(L.zsv_conv3d_wgrad_workspace_bytes(dp))
     what = f"{row.table}/{row.name}{tag}"
@@ -219,15 +272,17 @@ def _conv_entry_points(row, tag):
 
     # ---- forward ----
     def fwd(b, r, relu, stats, tiles):
-        return lambda p: L.zsv_conv3d_fwd_full(dp, x, w, b, r, p["y"], relu, p.get(stats), tiles, p["ws"], nf, None)
+        return lambda p: L.zsv_conv3d_fwd_full(dp, p["x"], p["w"], p.get(b), p.get(r), p["y"], relu, p.get(stats), tiles, p["ws"], nf, None)
 
-    y = contract("zsv_conv3d_fwd_full", fwd(None, None, 0, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True)["y"]
+    y = contract("zsv_conv3d_fwd_full", fwd(None, None, 0, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True, ins=pick(o, "x", "w"))["y"]
     same_bytes(y, yw.detach(), f"{what}: forward")
     ROWS_RUN[(row.table, "fwd")].add(row.name)
-    yb = contract("zsv_conv3d_fwd_full (bias + ReLU)", fwd(bias, None, 1, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True)["y"]
+    yb = contract("zsv_conv3d_fwd_full (bias + ReLU)", fwd("bias", None, 1, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True,
+                  ins=pick(o, "x", "w", "bias"))["y"]
     same_bytes(yb, yw_relu, f"{what}: forward + bias + ReLU")
     if L.zsv_conv3d_fwd_add_supported(dp):
-        yr = contract("zsv_conv3d_fwd_full (residual)", fwd(bias, res, 1, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True)["y"]
+        yr = contract("zsv_conv3d_fwd_full (residual)", fwd("bias", "res", 1, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True,
+                      ins=pick(o, "x", "w", "bias", "res"))["y"]
         conv = torch.nn.Conv3d(d.Cin, d.Cout, row.ws[2:], row.stride, row.pad, bias=True).to(DEV)
         with torch.no_grad():
             conv.weight.copy_(o["w"])
@@ -238,45 +293,44 @@ def _conv_entry_points(row, tag):
     assert (tiles > 0) == (stats_w is not None), f"{what}: the statistics query disagrees with the wrapper's"
     if tiles > 0:
         out = contract("zsv_conv3d_fwd_full (statistics)", fwd(None, None, 0, "bn_partials", tiles),
-                       {"y": (F32, ys), "bn_partials": (F32, (2, d.Cout, tiles))}, {"ws": nf}, shifted=True)
+                       {"y": (F32, ys), "bn_partials": (F32, (2, d.Cout, tiles))}, {"ws": nf}, shifted=True, ins=pick(o, "x", "w"))
         same_bytes(out["y"], yw_stats, f"{what}: forward with the statistics epilogue")
         same_bytes(out["bn_partials"], stats_w, f"{what}: statistics")
 
     # ---- input gradient ----
-    dx = contract("zsv_conv3d_dgrad", lambda p: L.zsv_conv3d_dgrad(dp, dy, w, p["dx"], p["ws"], nd, None),
-                  {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True)["dx"]
+    dx = contract("zsv_conv3d_dgrad", lambda p: L.zsv_conv3d_dgrad(dp, p["dy"], p["w"], p["dx"], p["ws"], nd, None),
+                  {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True, ins=pick(o, "dy", "w"))["dx"]
     same_bytes(dx, xg.grad, f"{what}: dgrad")
     ROWS_RUN[(row.table, "dgrad")].add(row.name)
     if L.zsv_conv3d_dgrad_add_supported(dp):
-        dxa = contract("zsv_conv3d_dgrad_add", lambda p: L.zsv_conv3d_dgrad_add(dp, dy, w, add, p["dx"], p["ws"], nd, None),
-                       {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True)["dx"]
+        dxa = contract("zsv_conv3d_dgrad_add", lambda p: L.zsv_conv3d_dgrad_add(dp, p["dy"], p["w"], p["add"], p["dx"], p["ws"], nd, None),
+                       {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True, ins=pick(o, "dy", "w", "add"))["dx"]
         T.close(dxa, dx.double() + o["add"].double(), rtol=1e-6, what=f"{what}: dgrad + shortcut gradient")
     for st in (1, 2):
         if L.zsv_conv3d_dgrad_add_strided_supported(dp, st, 2, 2):
             sub = torch.randn((d.N, d.Cin, -(-d.Ti // st), d.Hi // 2, d.Wi // 2), generator=g).to(DEV)
             dxs = contract("zsv_conv3d_dgrad_add_strided",
-                           lambda p: L.zsv_conv3d_dgrad_add_strided(dp, dy, w, sub.data_ptr(), st, 2, 2, p["dx"], p["ws"], nd, None),
-                           {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True)["dx"]
+                           lambda p: L.zsv_conv3d_dgrad_add_strided(dp, p["dy"], p["w"], p["sub"], st, 2, 2, p["dx"], p["ws"], nd, None),
+                           {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True, ins=dict(pick(o, "dy", "w"), sub=sub))["dx"]
             ref = dx.double()
             ref[:, :, ::st, :2 * (d.Hi // 2):2, :2 * (d.Wi // 2):2] += sub.double()
             T.close(dxs, ref, rtol=1e-6, what=f"{what}: dgrad + strided shortcut gradient (st = {st})")
 
     # ---- weight gradient ----
-    x_, dy_ = o["x"].data_ptr(), dy
-    dw = contract("zsv_conv3d_wgrad", lambda p: L.zsv_conv3d_wgrad(dp, x_, dy_, p["dw"], p["ws"], nw, None),
-                  {"dw": (F32, row.ws)}, {"ws": nw}, shifted=True)["dw"]
+    dw = contract("zsv_conv3d_wgrad", lambda p: L.zsv_conv3d_wgrad(dp, p["x"], p["dy"], p["dw"], p["ws"], nw, None),
+                  {"dw": (F32, row.ws)}, {"ws": nw}, shifted=True, ins=pick(o, "x", "dy"))["dw"]
     same_bytes(dw, wg.grad, f"{what}: wgrad")
     ROWS_RUN[(row.table, "wgrad")].add(row.name)
     nm = int(L.zsv_conv3d_wgrad_mask_bytes(dp))
     dwm = contract("zsv_conv3d_wgrad_masked",
                    lambda p: [L.zsv_conv3d_wgrad_mask(dp, p["mask"], None) if nm else 0,
-                              L.zsv_conv3d_wgrad_masked(dp, x_, dy_, p["dw"], p["ws"], nw, p["mask"] if nm else None, None)],
-                   {"dw": (F32, row.ws)}, {"ws": nw, "mask": nm}, shifted={"ws"})["dw"]
+                              L.zsv_conv3d_wgrad_masked(dp, p["x"], p["dy"], p["dw"], p["ws"], nw, p["mask"] if nm else None, None)],
+                   {"dw": (F32, row.ws)}, {"ws": nw, "mask": nm}, shifted={"ws"}, ins=pick(o, "x", "dy"))["dw"]
     same_bytes(dwm, dw, f"{what}: wgrad with a kept tap-validity table")
 
     # ---- the BatchNorm + ReLU folded into the convolution ----
     if L.zsv_conv3d_pre_supported(dp):
-        coef, pitch = o["coef"].data_ptr(), int(o["coef"].shape[1])
+        pitch = int(o["coef"].shape[1])
         wp = o["w"].clone().requires_grad_()
         yp, sp = ops.conv3d_pre(o["x"], o["coef"], wp, row.stride, row.pad, want_stats=True)
         yp.backward(o["dy"])
@@ -286,13 +340,13 @@ def _conv_entry_points(row, tag):
         if tiles > 0:
             outs["bn_partials"] = (F32, (2, d.Cout, tiles))
         out = contract("zsv_conv3d_fwd_pre",
-                       lambda p: L.zsv_conv3d_fwd_pre(dp, x_, coef, pitch, w, p["y"], p.get("bn_partials"), tiles, p["ws"], nf, None),
-                       outs, {"ws": nf}, shifted=True)
+                       lambda p: L.zsv_conv3d_fwd_pre(dp, p["x"], p["coef"], pitch, p["w"], p["y"], p.get("bn_partials"), tiles, p["ws"], nf, None),
+                       outs, {"ws": nf}, shifted=True, ins=pick(o, "x", "coef", "w"))
         same_bytes(out["y"], yp.detach(), f"{what}: forward through BatchNorm + ReLU")
         if tiles > 0:
             same_bytes(out["bn_partials"], sp, f"{what}: statistics of the forward through BatchNorm + ReLU")
-        dwp = contract("zsv_conv3d_wgrad_pre", lambda p: L.zsv_conv3d_wgrad_pre(dp, x_, coef, pitch, dy_, p["dw"], p["ws"], nw, None),
-                       {"dw": (F32, row.ws)}, {"ws": nw}, shifted=True)["dw"]
+        dwp = contract("zsv_conv3d_wgrad_pre", lambda p: L.zsv_conv3d_wgrad_pre(dp, p["x"], p["coef"], pitch, p["dy"], p["dw"], p["ws"], nw, None),
+                       {"dw": (F32, row.ws)}, {"ws": nw}, shifted=True, ins=pick(o, "x", "coef", "dy"))["dw"]
         same_bytes(dwp, wp.grad, f"{what}: wgrad through BatchNorm + ReLU")
 
 
@@ -324,7 +378,6 @@ def test_weight_panels(case):
     row = ConvRow("PANEL_CASES", name, xs, ws, ops._triple(stride), pad, [()], ())
     d, ys, o, g = _conv_operands(row)
     dp = byref(d)
-    x, w, bias, dy = (o[k].data_ptr() for k in ("x", "w", "bias", "dy"))
     nf, nd = int(L.zsv_conv3d_fwd_workspace_bytes(dp)), int(L.zsv_conv3d_dgrad_workspace_bytes(dp))
 
     def panel_bytes(direction, extras):
@@ -335,46 +388,43 @@ def test_weight_panels(case):
 
     def pack(p, direction, extras, nb):
         job = _lib.PackJob()
-        s = L.zsv_conv3d_panel_job(dp, direction, extras, w, p["panel"], nb, byref(job))
+        s = L.zsv_conv3d_panel_job(dp, direction, extras, p["w"], p["panel"], nb, byref(job))
         if s:
             return s
         job.first_block = 0
-        table = torch.frombuffer(bytearray(bytes(job)), dtype=U8).to(DEV)
-        s = L.zsv_pack_multi(table.data_ptr(), 1, (int(job.total) + 1023) // 1024, None)
-        torch.cuda.synchronize()                          # (the job table is a temporary)
-        return s
+        return L.zsv_pack_multi(p["table"](torch.frombuffer(bytearray(bytes(job)), dtype=U8), "jobs"), 1, (int(job.total) + 1023) // 1024, None)
 
     for extras in (0, 1):
         nb = panel_bytes(0, extras)
-        b = bias if extras else None
         y = contract("zsv_pack_multi + zsv_conv3d_fwd_full_panel",
                      lambda p: [pack(p, 0, extras, nb),
-                                L.zsv_conv3d_fwd_full_panel(dp, x, w, b, None, p["y"], extras, None, 0, p["ws"], nf, None, p["panel"], nb)],
-                     {"y": (F32, ys)}, {"ws": nf, "panel": nb}, shifted={"ws"})["y"]
+                                L.zsv_conv3d_fwd_full_panel(dp, p["x"], p["w"], p["bias"], None, p["y"], extras, None, 0, p["ws"], nf, None, p["panel"], nb)],
+                     {"y": (F32, ys)}, {"ws": nf, "panel": nb}, shifted={"ws"}, ins=dict(pick(o, "x", "w"), bias=o["bias"] if extras else None))["y"]
         with torch.no_grad():
             same_bytes(y, ops.conv3d(o["x"], o["w"], o["bias"] if extras else None, stride, pad, relu=bool(extras)), f"{name}: forward, extras {extras}")
     nb = panel_bytes(1, 0)
     dx = contract("zsv_pack_multi + zsv_conv3d_dgrad_add_panel",
-                  lambda p: [pack(p, 1, 0, nb), L.zsv_conv3d_dgrad_add_panel(dp, dy, w, None, p["dx"], p["ws"], nd, None, p["panel"], nb)],
-                  {"dx": (F32, xs)}, {"ws": nd, "panel": nb}, shifted={"ws"})["dx"]
+                  lambda p: [pack(p, 1, 0, nb), L.zsv_conv3d_dgrad_add_panel(dp, p["dy"], p["w"], None, p["dx"], p["ws"], nd, None, p["panel"], nb)],
+                  {"dx": (F32, xs)}, {"ws": nd, "panel": nb}, shifted={"ws"}, ins=pick(o, "dy", "w"))["dx"]
     xg = o["x"].clone().requires_grad_()
     ops.conv3d(xg, o["w"], None, stride, pad).backward(o["dy"])
     same_bytes(dx, xg.grad, f"{name}: dgrad")
     if L.zsv_conv3d_pre_supported(dp):
-        coef, pitch = o["coef"].data_ptr(), int(o["coef"].shape[1])
+        pitch = int(o["coef"].shape[1])
         y = contract("zsv_pack_multi + zsv_conv3d_fwd_pre_panel",
                      lambda p: [pack(p, 0, 0, panel_bytes(0, 0)),
-                                L.zsv_conv3d_fwd_pre_panel(dp, x, coef, pitch, w, p["y"], None, 0, p["ws"], nf, None, p["panel"], panel_bytes(0, 0))],
-                     {"y": (F32, ys)}, {"ws": nf, "panel": panel_bytes(0, 0)}, shifted={"ws"})["y"]
+                                L.zsv_conv3d_fwd_pre_panel(dp, p["x"], p["coef"], pitch, p["w"], p["y"], None, 0, p["ws"], nf, None, p["panel"],
+                                                           panel_bytes(0, 0))],
+                     {"y": (F32, ys)}, {"ws": nf, "panel": panel_bytes(0, 0)}, shifted={"ws"}, ins=pick(o, "x", "coef", "w"))["y"]
         with torch.no_grad():
             same_bytes(y, ops.conv3d_pre(o["x"], o["coef"], o["w"], stride, pad), f"{name}: forward through BatchNorm + ReLU")
     for st in (1, 2):
         if L.zsv_conv3d_dgrad_add_strided_supported(dp, st, 2, 2):
             sub = torch.randn((d.N, d.Cin, -(-d.Ti // st), d.Hi // 2, d.Wi // 2), generator=g).to(DEV)
             dxs = contract("zsv_pack_multi + zsv_conv3d_dgrad_add_strided_panel",
-                           lambda p: [pack(p, 1, 0, nb), L.zsv_conv3d_dgrad_add_strided_panel(dp, dy, w, sub.data_ptr(), st, 2, 2, p["dx"], p["ws"], nd,
+                           lambda p: [pack(p, 1, 0, nb), L.zsv_conv3d_dgrad_add_strided_panel(dp, p["dy"], p["w"], p["sub"], st, 2, 2, p["dx"], p["ws"], nd,
                                                                                               None, p["panel"], nb)],
-                           {"dx": (F32, xs)}, {"ws": nd, "panel": nb}, shifted={"ws"})["dx"]
+                           {"dx": (F32, xs)}, {"ws": nd, "panel": nb}, shifted={"ws"}, ins=dict(pick(o, "dy", "w"), sub=sub))["dx"]
             ref = dx.double()
             ref[:, :, ::st, :2 * (d.Hi // 2):2, :2 * (d.Wi // 2):2] += sub.double()
             T.close(dxs, ref, rtol=1e-6, what=f"{name}: dgrad + strided shortcut gradient (panel)")
@@ -403,11 +453,11 @@ def test_channel_sum_and_relu_bwd_bias(shape):
     n, c = shape[:2]
     s = numel(shape[2:])
     nb = int(L.zsv_channel_sum_workspace_bytes(n, c, s))
-    dy, y = o["dy"].data_ptr(), o["x"].data_ptr()
-    db = contract("zsv_channel_sum", lambda p: L.zsv_channel_sum(dy, n, c, s, p["db"], p["ws"], nb, None), {"db": (F32, (c,))}, {"ws": nb})["db"]
+    db = contract("zsv_channel_sum", lambda p: L.zsv_channel_sum(p["dy"], n, c, s, p["db"], p["ws"], nb, None), {"db": (F32, (c,))}, {"ws": nb},
+                  ins=pick(o, "dy"))["db"]
     same_bytes(db, ops.channel_sum(o["dy"]), "channel_sum")
-    out = contract("zsv_relu_bwd_bias", lambda p: L.zsv_relu_bwd_bias(dy, y, p["dx"], n, c, s, p["db"], p["ws"], nb, None),
-                   {"dx": (F32, shape), "db": (F32, (c,))}, {"ws": nb})
+    out = contract("zsv_relu_bwd_bias", lambda p: L.zsv_relu_bwd_bias(p["dy"], p["y"], p["dx"], n, c, s, p["db"], p["ws"], nb, None),
+                   {"dx": (F32, shape), "db": (F32, (c,))}, {"ws": nb}, ins=pick(o, "dy", y="x"))
     ref = torch.where(o["x"] > 0, o["dy"], torch.zeros_like(o["dy"]))
     assert torch.equal(out["dx"], ref)
     T.close(out["db"], ref.double().sum(dim=(0, 2, 3, 4)), what="bias gradient")        # (test_relu_bwd_bias_on_misaligned_views)
@@ -423,8 +473,7 @@ def test_batchnorm_entry_points(shape, use_res, relu):
     n, c = shape[:2]
     s = numel(shape[2:])
     nb = int(L.zsv_bn_workspace_bytes(n, c, s))
-    x, gamma, beta, dy = (o[k].data_ptr() for k in ("x", "gamma", "beta", "dy"))
-    res = o["res"].data_ptr() if use_res else None
+    fwd_ins = dict(pick(o, "x", "gamma", "beta"), res=o["res"] if use_res else None)
     r = 1 if relu else 0
     stat_outs = {"save_mean": (F32, (c,)), "save_invstd": (F32, (c,)), "running_mean": (F32, (c,), o["rm"]), "running_var": (F32, (c,), o["rv"])}
 
@@ -441,9 +490,9 @@ def test_batchnorm_entry_points(shape, use_res, relu):
     # ---- training forward ----
     wt = wrapper(True)
     out = contract("zsv_bn_fwd_train",
-                   lambda p: L.zsv_bn_fwd_train(x, n, c, s, gamma, beta, res, r, p["y"], p["save_mean"], p["save_invstd"], p["running_mean"],
-                                                p["running_var"], 0.1, 1e-5, p["ws"], nb, None),
-                   dict(stat_outs, y=(F32, shape)), {"ws": nb})
+                   lambda p: L.zsv_bn_fwd_train(p["x"], n, c, s, p["gamma"], p["beta"], p["res"], r, p["y"], p["save_mean"], p["save_invstd"],
+                                                p["running_mean"], p["running_var"], 0.1, 1e-5, p["ws"], nb, None),
+                   dict(stat_outs, y=(F32, shape)), {"ws": nb}, ins=fwd_ins)
     same_bytes(out["y"], wt["y"], "bn_fwd_train: y")
     same_bytes(out["running_mean"], wt["rm"], "bn_fwd_train: running_mean")
     same_bytes(out["running_var"], wt["rv"], "bn_fwd_train: running_var")
@@ -460,18 +509,18 @@ def test_batchnorm_entry_points(shape, use_res, relu):
                             torch.stack([(xs_[:, :, a:b] ** 2).sum(dim=(0, 2)) for a, b in zip(cuts, cuts[1:])], 1)]).contiguous()
     ws_ = wrapper(True, partials)
     out = contract("zsv_bn_fwd_train_stats",
-                   lambda p: L.zsv_bn_fwd_train_stats(x, n, c, s, gamma, beta, res, r, p["y"], p["save_mean"], p["save_invstd"], p["running_mean"],
-                                                      p["running_var"], 0.1, 1e-5, partials.data_ptr(), tiles, p["ws"], nb, None),
-                   dict(stat_outs, y=(F32, shape)), {"ws": nb})
+                   lambda p: L.zsv_bn_fwd_train_stats(p["x"], n, c, s, p["gamma"], p["beta"], p["res"], r, p["y"], p["save_mean"], p["save_invstd"],
+                                                      p["running_mean"], p["running_var"], 0.1, 1e-5, p["conv_partials"], tiles, p["ws"], nb, None),
+                   dict(stat_outs, y=(F32, shape)), {"ws": nb}, ins=dict(fwd_ins, conv_partials=partials))
     same_bytes(out["y"], ws_["y"], "bn_fwd_train_stats: y")
     same_bytes(out["running_mean"], ws_["rm"], "bn_fwd_train_stats: running_mean")
     same_bytes(out["running_var"], ws_["rv"], "bn_fwd_train_stats: running_var")
     if not use_res and not relu:
         pitch = (c + 15) // 16 * 16
         out = contract("zsv_bn_fwd_train_coeffs",
-                       lambda p: L.zsv_bn_fwd_train_coeffs(x, n, c, s, gamma, beta, p["save_mean"], p["save_invstd"], p["running_mean"], p["running_var"],
-                                                           0.1, 1e-5, None, 0, p["coef"], pitch, p["ws"], nb, None),
-                       dict(stat_outs, coef=(F32, (2, pitch))), {"ws": nb})
+                       lambda p: L.zsv_bn_fwd_train_coeffs(p["x"], n, c, s, p["gamma"], p["beta"], p["save_mean"], p["save_invstd"], p["running_mean"],
+                                                           p["running_var"], 0.1, 1e-5, None, 0, p["coef"], pitch, p["ws"], nb, None),
+                       dict(stat_outs, coef=(F32, (2, pitch))), {"ws": nb}, ins=pick(o, "x", "gamma", "beta"))
         assert int(torch.count_nonzero(out["coef"][:, c:])) == 0, "coef entries C .. coef_pitch-1 must be zero"
         rm, rv = o["rm"].clone(), o["rv"].clone()
         _, coef_w = ops._BatchNormDeferred.apply(o["x"], o["gamma"], o["beta"], rm, rv, 0.1, 1e-5, None)
@@ -520,16 +569,16 @@ def test_batchnorm_entry_points(shape, use_res, relu):
             if with_dres:
                 outs["d_residual"] = (F32, shape)
             got = contract(f"zsv_bn_bwd (relu mode {mode}{', d_residual' if with_dres else ''})",
-                           lambda p: L.zsv_bn_bwd(dy, x, y_fwd.data_ptr() if mode == 1 else None, n, c, s, gamma, beta, save_mean.data_ptr(),
-                                                  save_invstd.data_ptr(), mode, p["dx"], p.get("d_residual"), p["dgamma"], p["dbeta"],
-                                                  p["ws"], nb, None), outs, {"ws": nb})
+                           lambda p: L.zsv_bn_bwd(p["dy"], p["x"], p["y"], n, c, s, p["gamma"], p["beta"], p["save_mean"], p["save_invstd"], mode,
+                                                  p["dx"], p.get("d_residual"), p["dgamma"], p["dbeta"], p["ws"], nb, None), outs, {"ws": nb},
+                           ins=dict(pick(o, "dy", "x", "gamma", "beta"), y=y_fwd if mode == 1 else None, save_mean=save_mean, save_invstd=save_invstd))
             check_grads(got, mode, with_dres, wt, ref_t, y_fwd, "bn_bwd")
 
     # ---- frozen statistics: forward and backward ----
     we = wrapper(False)
-    rm_, rv_ = o["rm"].data_ptr(), o["rv"].data_ptr()
-    ye = contract("zsv_bn_fwd_eval", lambda p: L.zsv_bn_fwd_eval(x, n, c, s, gamma, beta, rm_, rv_, res, r, 1e-5, p["y"], p["ws"], nb, None),
-                  {"y": (F32, shape)}, {"ws": nb})["y"]
+    ye = contract("zsv_bn_fwd_eval", lambda p: L.zsv_bn_fwd_eval(p["x"], n, c, s, p["gamma"], p["beta"], p["rm"], p["rv"], p["res"], r, 1e-5, p["y"],
+                                                                 p["ws"], nb, None),
+                  {"y": (F32, shape)}, {"ws": nb}, ins=dict(fwd_ins, **pick(o, "rm", "rv")))["y"]
     same_bytes(ye, we["y"], "bn_fwd_eval: y")
     ref_e = reference(False)
     for mode in modes:
@@ -538,8 +587,9 @@ def test_batchnorm_entry_points(shape, use_res, relu):
             if with_dres:
                 outs["d_residual"] = (F32, shape)
             got = contract(f"zsv_bn_bwd_eval (relu mode {mode}{', d_residual' if with_dres else ''})",
-                           lambda p: L.zsv_bn_bwd_eval(dy, x, ye.data_ptr() if mode == 1 else None, n, c, s, gamma, beta, rm_, rv_, 1e-5, mode,
-                                                       p["dx"], p.get("d_residual"), p["dgamma"], p["dbeta"], p["ws"], nb, None), outs, {"ws": nb})
+                           lambda p: L.zsv_bn_bwd_eval(p["dy"], p["x"], p["y"], n, c, s, p["gamma"], p["beta"], p["rm"], p["rv"], 1e-5, mode,
+                                                       p["dx"], p.get("d_residual"), p["dgamma"], p["dbeta"], p["ws"], nb, None), outs, {"ws": nb},
+                           ins=dict(pick(o, "dy", "x", "gamma", "beta", "rm", "rv"), y=ye if mode == 1 else None))
             check_grads(got, mode, with_dres, we, ref_e, ye, "bn_bwd_eval")
     ROWS_RUN[("BN_CASES", "bn")].add(shape)
 
@@ -559,14 +609,15 @@ def test_linear_entry_points(rows, fin, fout, relu):
     ops.linear(xg2, wg2, None).backward(dy)                               # plain: dy reaches dgrad / wgrad unmasked
     torch.cuda.synchronize()
     nf, nd, nw = (int(f(rows, fin, fout)) for f in (L.zsv_linear_fwd_workspace_bytes, L.zsv_linear_dgrad_workspace_bytes, L.zsv_linear_wgrad_workspace_bytes))
-    y = contract("zsv_linear_fwd", lambda p: L.zsv_linear_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), p["y"], rows, fin, fout, 1 if relu else 0,
-                                                              p["ws"], nf, None), {"y": (F32, (rows, fout))}, {"ws": nf}, shifted=True)["y"]
+    y = contract("zsv_linear_fwd", lambda p: L.zsv_linear_fwd(p["x"], p["w"], p["bias"], p["y"], rows, fin, fout, 1 if relu else 0,
+                                                              p["ws"], nf, None), {"y": (F32, (rows, fout))}, {"ws": nf}, shifted=True,
+                 ins=dict(x=x, w=w, bias=b))["y"]
     same_bytes(y, yw.detach(), "linear_fwd")
-    dx = contract("zsv_linear_dgrad", lambda p: L.zsv_linear_dgrad(dy.data_ptr(), w.data_ptr(), p["dx"], rows, fin, fout, p["ws"], nd, None),
-                  {"dx": (F32, (rows, fin))}, {"ws": nd}, shifted=True)["dx"]
+    dx = contract("zsv_linear_dgrad", lambda p: L.zsv_linear_dgrad(p["dy"], p["w"], p["dx"], rows, fin, fout, p["ws"], nd, None),
+                  {"dx": (F32, (rows, fin))}, {"ws": nd}, shifted=True, ins=dict(dy=dy, w=w))["dx"]
     same_bytes(dx, xg2.grad, "linear_dgrad")
-    dw = contract("zsv_linear_wgrad", lambda p: L.zsv_linear_wgrad(x.data_ptr(), dy.data_ptr(), p["dw"], rows, fin, fout, p["ws"], nw, None),
-                  {"dw": (F32, (fout, fin))}, {"ws": nw}, shifted=True)["dw"]
+    dw = contract("zsv_linear_wgrad", lambda p: L.zsv_linear_wgrad(p["x"], p["dy"], p["dw"], rows, fin, fout, p["ws"], nw, None),
+                  {"dw": (F32, (fout, fin))}, {"ws": nw}, shifted=True, ins=dict(x=x, dy=dy))["dw"]
     same_bytes(dw, wg2.grad, "linear_wgrad")
     ROWS_RUN[("test_linear", "linear")].add((rows, fin, fout))
 
@@ -581,12 +632,13 @@ def test_cosine_topk(rows, n_classes, dim, k):
         c[7] = c[2]
     e, c = e.to(DEV), c.to(DEV)
     nb = int(L.zsv_cosine_topk_workspace_bytes(rows, n_classes))
-    out = contract("zsv_cosine_topk", lambda p: L.zsv_cosine_topk(e.data_ptr(), c.data_ptr(), rows, dim, n_classes, k, p["out_index"], p["out_dist"],
+    out = contract("zsv_cosine_topk", lambda p: L.zsv_cosine_topk(p["embed"], p["class_embed"], rows, dim, n_classes, k, p["out_index"], p["out_dist"],
                                                                   p["ws"], nb, None),
-                   {"out_index": (I32, (rows, k)), "out_dist": (F64, (rows, k))}, {"ws": nb})
+                   {"out_index": (I32, (rows, k)), "out_dist": (F64, (rows, k))}, {"ws": nb}, ins=dict(embed=e, class_embed=c))
     assert torch.equal(out["out_index"].long(), train.nearest_classes(e, c, k))
-    out2 = contract("zsv_cosine_topk (no distances)", lambda p: L.zsv_cosine_topk(e.data_ptr(), c.data_ptr(), rows, dim, n_classes, k, p["out_index"], None,
-                                                                                 p["ws"], nb, None), {"out_index": (I32, (rows, k))}, {"ws": nb})
+    out2 = contract("zsv_cosine_topk (no distances)", lambda p: L.zsv_cosine_topk(p["embed"], p["class_embed"], rows, dim, n_classes, k, p["out_index"], None,
+                                                                                 p["ws"], nb, None), {"out_index": (I32, (rows, k))}, {"ws": nb},
+                    ins=dict(embed=e, class_embed=c))
     same_bytes(out2["out_index"], out["out_index"], "cosine_topk without distances")
     ec, cc = e.double().cpu(), c.double().cpu()
     full = 1 - (ec @ cc.t()) / (ec.norm(dim=1, keepdim=True) * cc.norm(dim=1).view(1, -1))
@@ -633,9 +685,9 @@ def test_bf16_blob_and_forward(case, monkeypatch):
         if knob:
             monkeypatch.setenv(knob, "1")
         y = contract("zsv_conv3d_bf16_pack + zsv_conv3d_bf16_fwd",
-                     lambda p: [L.zsv_conv3d_bf16_pack(byref(d), wgt.data_ptr(), scale.data_ptr(), shift.data_ptr(), p["blob"], None),
-                                L.zsv_conv3d_bf16_fwd(byref(d), xb.data_ptr(), p["blob"], ops._ptr(rb), 1 if case.relu else 0, p["y"], None)],
-                     {"y": (BF16, ys)}, {"blob": nb})["y"]
+                     lambda p: [L.zsv_conv3d_bf16_pack(byref(d), p["w"], p["scale"], p["shift"], p["blob"], None),
+                                L.zsv_conv3d_bf16_fwd(byref(d), p["x"], p["blob"], p["residual"], 1 if case.relu else 0, p["y"], None)],
+                     {"y": (BF16, ys)}, {"blob": nb}, ins=dict(w=wgt, scale=scale, shift=shift, x=xb, residual=rb))["y"]
         same_bytes(y, inference.conv_bf16(d, xb, inference.pack_conv(d, wgt, scale, shift), rb, case.relu), f"{case.name} {knob or ''}: y")
         assert int(torch.count_nonzero(y[..., case.cout:].float())) == 0, "pad channels must be written as zero"
         if knob:
@@ -656,10 +708,10 @@ def test_bf16_statistics_epilogue(case):
 
     def launch(p):
         rows.value = 0
-        return [L.zsv_conv3d_bf16_pack(byref(d), wgt.data_ptr(), None, None, p["blob"], None),
-                L.zsv_conv3d_bf16_fwd_stats(byref(d), xb.data_ptr(), p["blob"], p["y"], p["bn_partials"], cap, byref(rows), None)]
+        return [L.zsv_conv3d_bf16_pack(byref(d), p["w"], None, None, p["blob"], None),
+                L.zsv_conv3d_bf16_fwd_stats(byref(d), p["x"], p["blob"], p["y"], p["bn_partials"], cap, byref(rows), None)]
 
-    out = contract("zsv_conv3d_bf16_fwd_stats", launch, {"y": (BF16, ys), "bn_partials": (F32, (cap, 2, cp))}, {"blob": nb},
+    out = contract("zsv_conv3d_bf16_fwd_stats", launch, {"y": (BF16, ys), "bn_partials": (F32, (cap, 2, cp))}, {"blob": nb}, ins=dict(w=wgt, x=xb),
                    defined=lambda name, v: v[:rows.value] if name == "bn_partials" else v)
     assert 0 < rows.value <= cap
     z, partials, rows_w = amp.conv_bf16_stats(d, xb, amp.pack_conv(d, wgt, None, None))
@@ -701,9 +753,9 @@ def test_bf16_dgrad_blob_and_forward(case):
                 assert nb > 0
                 ys = (n,) + dims + (inference.channel_pitch(u.cin),)
                 y = contract("zsv_conv3d_bf16_pack_dgrad + zsv_conv3d_bf16_fwd",
-                             lambda p: [L.zsv_conv3d_bf16_pack_dgrad(byref(d2), sub.data_ptr(), p["blob"], None),
-                                        L.zsv_conv3d_bf16_fwd(byref(d2), dz.data_ptr(), p["blob"], None, 0, p["y"], None)],
-                             {"y": (BF16, ys)}, {"blob": nb}, count=problems == 0)["y"]
+                             lambda p: [L.zsv_conv3d_bf16_pack_dgrad(byref(d2), p["w_fwd"], p["blob"], None),
+                                        L.zsv_conv3d_bf16_fwd(byref(d2), p["dz"], p["blob"], None, 0, p["y"], None)],
+                             {"y": (BF16, ys)}, {"blob": nb}, count=problems == 0, ins=dict(w_fwd=sub, dz=dz))["y"]
                 same_bytes(y, amp.Bf16TrainPath._dgrad_problem(u, dz, sub, kernel, pads, dims), f"{case.name}: class problem {kernel}")
                 problems += 1
     assert problems > 0
@@ -722,8 +774,8 @@ def test_bf16_weight_gradient(case):
     nb = int(L.zsv_conv3d_bf16_wgrad_workspace_bytes(byref(d)))
     assert nb > 0, "the native kernel must take this geometry"
     ws = (case.cout, cin) + tuple(case.kernel)
-    dw = contract("zsv_conv3d_bf16_wgrad", lambda p: L.zsv_conv3d_bf16_wgrad(byref(d), x.data_ptr(), dz.data_ptr(), p["dw"], p["ws"], nb, None),
-                  {"dw": (F32, ws)}, {"ws": nb}, shifted=True)["dw"]
+    dw = contract("zsv_conv3d_bf16_wgrad", lambda p: L.zsv_conv3d_bf16_wgrad(byref(d), p["x"], p["dz"], p["dw"], p["ws"], nb, None),
+                  {"dw": (F32, ws)}, {"ws": nb}, shifted=True, ins=dict(x=x, dz=dz))["dw"]
     rec = amp._Record()
     rec.unit, rec.desc, rec.x, rec.clips = u, d, x, None
     want = amp.Bf16TrainPath._wgrad(rec, dz)
@@ -751,7 +803,7 @@ def test_channels_last_batchnorm_entry_points(shape, relu, res):
     nb = int(L.zsv_bn_cl_workspace_bytes(rows, c))
     assert nb > 0
     r = 1 if relu else 0
-    gamma, beta = bn.weight.data_ptr(), bn.bias.data_ptr()
+    fwd_ins = dict(z=z, residual=rb, gamma=bn.weight.detach(), beta=bn.bias.detach())
     rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
 
     def fresh_bn():
@@ -763,8 +815,9 @@ def test_channels_last_batchnorm_entry_points(shape, relu, res):
     outs = {"y": (BF16, cl), "save_mean": (F32, (c,)), "save_invstd": (F32, (c,)), "save_coef": (F32, (2, cp)),
             "running_mean": (F32, (c,), rm0), "running_var": (F32, (c,), rv0)}
     out = contract("zsv_bn_cl_fwd_train",
-                   lambda p: L.zsv_bn_cl_fwd_train(z.data_ptr(), ops._ptr(rb), rows, c, gamma, beta, p["running_mean"], p["running_var"], 0.1, bn.eps, r,
-                                                   p["y"], p["save_mean"], p["save_invstd"], p["save_coef"], p["ws"], nb, None), outs, {"ws": nb})
+                   lambda p: L.zsv_bn_cl_fwd_train(p["z"], p["residual"], rows, c, p["gamma"], p["beta"], p["running_mean"], p["running_var"], 0.1, bn.eps,
+                                                   r, p["y"], p["save_mean"], p["save_invstd"], p["save_coef"], p["ws"], nb, None), outs, {"ws": nb},
+                   ins=fwd_ins)
     yw, mean, invstd, coef = amp.bn_cl_fwd_train(z, fresh_bn(), rb, relu, want_coef=True)
     torch.cuda.synchronize()
     for name, want in (("y", yw), ("save_mean", mean), ("save_invstd", invstd), ("save_coef", coef), ("running_mean", bn.running_mean),
@@ -776,9 +829,9 @@ def test_channels_last_batchnorm_entry_points(shape, relu, res):
     zf = z.reshape(rows, cp).float()
     partials = torch.stack([torch.stack([zf[a:b].sum(0), (zf[a:b] ** 2).sum(0)]) for a, b in zip(cuts, cuts[1:])]).contiguous()
     out2 = contract("zsv_bn_cl_fwd_train_stats",
-                    lambda p: L.zsv_bn_cl_fwd_train_stats(z.data_ptr(), ops._ptr(rb), rows, c, gamma, beta, p["running_mean"], p["running_var"], 0.1, bn.eps,
-                                                          r, p["y"], p["save_mean"], p["save_invstd"], p["save_coef"], partials.data_ptr(), blocks,
-                                                          p["ws"], nb, None), outs, {"ws": nb})
+                    lambda p: L.zsv_bn_cl_fwd_train_stats(p["z"], p["residual"], rows, c, p["gamma"], p["beta"], p["running_mean"], p["running_var"], 0.1,
+                                                          bn.eps, r, p["y"], p["save_mean"], p["save_invstd"], p["save_coef"], p["conv_partials"], blocks,
+                                                          p["ws"], nb, None), outs, {"ws": nb}, ins=dict(fwd_ins, conv_partials=partials))
     yw2, mean2, invstd2, coef2 = amp.bn_cl_fwd_train(z, fresh_bn(), rb, relu, want_coef=True, conv_stats=(partials, blocks))
     torch.cuda.synchronize()
     for name, want in (("y", yw2), ("save_mean", mean2), ("save_invstd", invstd2), ("save_coef", coef2), ("running_var", bn.running_var)):
@@ -790,9 +843,10 @@ def test_channels_last_batchnorm_entry_points(shape, relu, res):
     forms = [False] + ([True] if (relu and not res) else [])
     for recompute in forms:
         o = contract("zsv_bn_cl_bwd" + (" (mask recomputed from z)" if recompute else ""),
-                     lambda p: L.zsv_bn_cl_bwd(dy.data_ptr(), y_saved.data_ptr() if (relu and not recompute) else None, z.data_ptr(), rows, c, gamma,
-                                               mean.data_ptr(), invstd.data_ptr(), coef.data_ptr() if recompute else None, r, p["dz"], p["g_out"],
-                                               p["dgamma"], p["dbeta"], p["ws"], nb, None), grads, {"ws": nb})
+                     lambda p: L.zsv_bn_cl_bwd(p["dy"], p["y"], p["z"], rows, c, p["gamma"], p["save_mean"], p["save_invstd"], p["fwd_coef"], r, p["dz"],
+                                               p["g_out"], p["dgamma"], p["dbeta"], p["ws"], nb, None), grads, {"ws": nb},
+                     ins=dict(dy=dy, y=y_saved if (relu and not recompute) else None, z=z, gamma=bn.weight.detach(), save_mean=mean, save_invstd=invstd,
+                              fwd_coef=coef if recompute else None))
         dzw, gw, dgw, dbw = amp.bn_cl_bwd(dy, yw, z, bn, mean, invstd, relu, want_g=True, fwd_coef=coef if recompute else None)
         torch.cuda.synchronize()
         for name, want in (("dz", dzw), ("g_out", gw), ("dgamma", dgw), ("dbeta", dbw)):
@@ -803,16 +857,16 @@ def test_channels_last_batchnorm_entry_points(shape, relu, res):
         if relu and not use_y and res:
             continue                                       # (the recomputed mask is the forward's only without a residual)
         o = contract("zsv_bn_cl_bwd_eval" + ("" if use_y or not relu else " (mask recomputed from z)"),
-                     lambda p: L.zsv_bn_cl_bwd_eval(dy.data_ptr(), ye.data_ptr() if use_y else None, z.data_ptr(), rows, c, coef4.data_ptr(), r, p["dz"],
-                                                    p["g_out"], p["dgamma"], p["dbeta"], p["ws"], nb, None), grads, {"ws": nb})
+                     lambda p: L.zsv_bn_cl_bwd_eval(p["dy"], p["y"], p["z"], rows, c, p["coef"], r, p["dz"], p["g_out"], p["dgamma"], p["dbeta"],
+                                                    p["ws"], nb, None), grads, {"ws": nb}, ins=dict(dy=dy, y=ye if use_y else None, z=z, coef=coef4))
         dzw, gw, dgw, dbw = amp.bn_cl_bwd_eval(dy, ye if use_y else None, z, bn, coef4, relu, want_g=True)
         torch.cuda.synchronize()
         for name, want in (("dz", dzw), ("g_out", gw), ("dgamma", dgw), ("dbeta", dbw)):
             same_bytes(o[name], want, f"bn_cl_bwd_eval: {name}")
     bn.train()
     # ---- C3D's relu(conv + bias) backward on the same tensors ----
-    o = contract("zsv_relu_bias_bwd_cl", lambda p: L.zsv_relu_bias_bwd_cl(dy.data_ptr(), y_saved.data_ptr(), rows, c, p["g_out"], p["dbias"], p["ws"], nb, None),
-                 {"g_out": (BF16, cl), "dbias": (F32, (c,))}, {"ws": nb})
+    o = contract("zsv_relu_bias_bwd_cl", lambda p: L.zsv_relu_bias_bwd_cl(p["dy"], p["y"], rows, c, p["g_out"], p["dbias"], p["ws"], nb, None),
+                 {"g_out": (BF16, cl), "dbias": (F32, (c,))}, {"ws": nb}, ins=dict(dy=dy, y=y_saved))
     gw, dbw = amp.relu_bias_bwd_cl(dy, y_saved, c)
     torch.cuda.synchronize()
     same_bytes(o["g_out"], gw, "relu_bias_bwd_cl: g")
@@ -840,13 +894,276 @@ def test_fp8_blob_and_forward(case):
     nb = int(L.zsv_conv3d_fp8_blob_bytes(byref(d)))
     assert nb > 0
     y = contract("zsv_conv3d_fp8_pack + zsv_conv3d_fp8_fwd",
-                 lambda q: [L.zsv_conv3d_fp8_pack(byref(d), wgt.data_ptr(), None, shift.data_ptr(), q["blob"], None),
-                            L.zsv_conv3d_fp8_fwd(byref(d), xb.data_ptr(), q["blob"], ops._ptr(rb), 1 if relu else 0, q["y"], None)],
-                 {"y": (U8, ys)}, {"blob": nb})["y"]
+                 lambda q: [L.zsv_conv3d_fp8_pack(byref(d), q["w"], None, q["shift"], q["blob"], None),
+                            L.zsv_conv3d_fp8_fwd(byref(d), q["x"], q["blob"], q["residual"], 1 if relu else 0, q["y"], None)],
+                 {"y": (U8, ys)}, {"blob": nb}, ins=dict(w=wgt, shift=shift, x=xb, residual=rb))["y"]
     want = inference.conv_fp8(d, xb, inference.pack_conv_fp8(d, wgt, None, shift), rb, relu)
     same_bytes(y, want.view(U8), "conv_fp8: y")
     assert int(torch.count_nonzero(y[..., cout:])) == 0, "pad channels must be written as zero"
     ROWS_RUN[("fp8 CASES", "fp8_fwd")].add(case)
+
+
+# =========================================================================================================================
+# entry points without a workspace: element-wise passes, pools, layout converters, the optimiser, clip pre-processing
+# =========================================================================================================================
+ELEMENTWISE_SHAPES = [(3, 5, 2, 7, 7), (1, 1, 1, 1, 3), (2, 4, 4, 8, 8)]            # test_relu_add_relu_meanpool
+
+
+@pytest.mark.parametrize("shape", ELEMENTWISE_SHAPES, ids=["x".join(map(str, s)) for s in ELEMENTWISE_SHAPES])
+def test_elementwise_and_mean_pool(shape):
+    L = lib()
+    g = torch.Generator().manual_seed(2 + sum(shape))
+    a, b, dy = (torch.randn(shape, generator=g).to(DEV) for _ in range(3))
+    n, c = shape[:2]
+    s = numel(shape[2:])
+    count = numel(shape)
+    ag = a.clone().requires_grad_()
+    yw = ops.relu(ag)
+    yw.backward(dy)
+    y = contract("zsv_relu_fwd", lambda p: L.zsv_relu_fwd(p["x"], p["y"], count, None), {"y": (F32, shape)}, ins=dict(x=a))["y"]
+    same_bytes(y, yw.detach(), "relu_fwd")
+    dx = contract("zsv_relu_bwd", lambda p: L.zsv_relu_bwd(p["dy"], p["y"], p["dx"], count, None), {"dx": (F32, shape)}, ins=dict(dy=dy, y=y))["dx"]
+    same_bytes(dx, ag.grad, "relu_bwd")
+    with torch.no_grad():
+        sw = ops.add_relu(a, b)
+    out = contract("zsv_add_relu_fwd", lambda p: L.zsv_add_relu_fwd(p["a"], p["b"], p["y"], count, None), {"y": (F32, shape)}, ins=dict(a=a, b=b))["y"]
+    same_bytes(out, sw, "add_relu_fwd")
+    dm = torch.randn((n, c), generator=g).to(DEV)
+    ag = a.clone().requires_grad_()
+    mw = ops.mean_pool(ag)
+    mw.backward(dm)
+    m = contract("zsv_meanpool_fwd", lambda p: L.zsv_meanpool_fwd(p["x"], n, c, s, p["y"], None), {"y": (F32, (n, c))}, ins=dict(x=a))["y"]
+    same_bytes(m, mw.detach(), "meanpool_fwd")
+    dxm = contract("zsv_meanpool_bwd", lambda p: L.zsv_meanpool_bwd(p["dy"], n, c, s, p["dx"], None), {"dx": (F32, shape)}, ins=dict(dy=dm))["dx"]
+    same_bytes(dxm, ag.grad, "meanpool_bwd")
+    ROWS_RUN[("elementwise", "elementwise")].add(shape)
+
+
+def _pool_geometry(shape, k, p):
+    n, c, ti, hi, wi = shape
+    to, ho, wo = ((v + 2 * q - w) // w + 1 for v, q, w in zip((ti, hi, wi), p, k))
+    return (n, c, ti, hi, wi) + tuple(k) + tuple(p) + (to, ho, wo), (to, ho, wo)
+
+
+@pytest.mark.parametrize("k,p,shape", T.POOL_CASES, ids=[f"k{k[0]}{k[1]}{k[2]}_p{p[0]}{p[1]}{p[2]}_{'x'.join(map(str, s))}" for k, p, s in T.POOL_CASES])
+def test_max_pool_fp32(k, p, shape):
+    L = lib()
+    g = torch.Generator().manual_seed(sum(shape))
+    x = F.relu(torch.randn(*shape, generator=g)).to(DEV)            # ties at 0 like post-ReLU activations
+    geom, (to, ho, wo) = _pool_geometry(shape, k, p)
+    ys = shape[:2] + (to, ho, wo)
+    dy = torch.randn(ys, generator=g).to(DEV)
+    xg = x.clone().requires_grad_()
+    yw = ops.max_pool3d(xg, k, k, p)
+    yw.backward(dy)
+    out = contract("zsv_maxpool3d_fwd", lambda q: L.zsv_maxpool3d_fwd(q["x"], *geom, q["y"], q["argmax"], None),
+                   {"y": (F32, ys), "argmax": (I32, ys)}, ins=dict(x=x))
+    same_bytes(out["y"], yw.detach(), "maxpool3d_fwd")
+    arg = out["argmax"].long()
+    assert int(arg.min()) >= 0 and int(arg.max()) < numel(shape[2:])
+    assert torch.equal(x.flatten(2).gather(2, arg.flatten(2)).view(ys), out["y"]), "argmax names the element the maximum was taken from"
+    dx = contract("zsv_maxpool3d_bwd", lambda q: L.zsv_maxpool3d_bwd(q["dy"], q["argmax"], *geom, q["dx"], None), {"dx": (F32, shape)},
+                  ins=dict(dy=dy, argmax=out["argmax"]))["dx"]
+    same_bytes(dx, xg.grad, "maxpool3d_bwd")
+    ROWS_RUN[("POOL_CASES", "maxpool")].add((k, p, shape))
+
+
+CL_POOL_CASES = params_of(TB.test_maxpool3d_channels_last_bf16)
+
+
+@pytest.mark.parametrize("shape,kernel,pad", CL_POOL_CASES, ids=["x".join(map(str, s)) for s, _, _ in CL_POOL_CASES])
+def test_channels_last_pools(shape, kernel, pad):
+    L = lib()
+    g = torch.Generator().manual_seed(sum(shape))
+    n, c, t, h, w = shape
+    geom, (to, ho, wo) = _pool_geometry(shape, kernel, pad)
+    s = t * h * w
+    # ---- bf16 ----
+    cp = inference.channel_pitch(c)
+    x = _cl_random((n, t, h, w, cp), c, g).to(DEV).to(BF16)
+    dy = _cl_random((n, to, ho, wo, cp), c, g).to(DEV).to(BF16)
+    y = contract("zsv_maxpool3d_bf16", lambda q: L.zsv_maxpool3d_bf16(q["x"], *geom, q["y"], None), {"y": (BF16, (n, to, ho, wo, cp))}, ins=dict(x=x))["y"]
+    same_bytes(y, inference.maxpool3d_bf16(x, c, kernel, pad), "maxpool3d_bf16")
+    dx = contract("zsv_maxpool3d_bf16_bwd", lambda q: L.zsv_maxpool3d_bf16_bwd(q["dy"], q["x"], *geom, q["dx"], None), {"dx": (BF16, tuple(x.shape))},
+                  ins=dict(dy=dy, x=x))["dx"]
+    same_bytes(dx, amp.maxpool3d_bf16_bwd(dy, x, c, kernel, pad), "maxpool3d_bf16_bwd")
+    m = contract("zsv_meanpool_bf16", lambda q: L.zsv_meanpool_bf16(q["x"], n, s, c, q["out"], None), {"out": (F32, (n, c))}, ins=dict(x=x))["out"]
+    same_bytes(m, inference.meanpool_bf16(x, c), "meanpool_bf16")
+    dp = torch.randn((n, c), generator=g).to(DEV)
+    dxm = contract("zsv_meanpool_bf16_bwd", lambda q: L.zsv_meanpool_bf16_bwd(q["dpooled"], n, s, c, q["dx"], None), {"dx": (BF16, tuple(x.shape))},
+                   ins=dict(dpooled=dp))["dx"]
+    same_bytes(dxm, amp.meanpool_bf16_bwd(dp, x, c), "meanpool_bf16_bwd")
+    # ---- e4m3: finite codes of both signs; the input's pad channels hold a non-zero code (test_maxpool3d_channels_last_fp8) ----
+    cp8 = inference.fp8_channel_pitch(c)
+    codes = torch.full((n, t, h, w, cp8), 0x55, dtype=U8)
+    codes[..., :c] = (torch.randn((n, t, h, w, c), generator=g) * 40.0).clamp(-448.0, 448.0).to(F8.FP8).view(U8)
+    x8 = codes.to(DEV).view(F8.FP8)
+    y8 = contract("zsv_maxpool3d_fp8", lambda q: L.zsv_maxpool3d_fp8(q["x"], *geom, q["y"], None), {"y": (U8, (n, to, ho, wo, cp8))}, ins=dict(x=x8))["y"]
+    same_bytes(y8, inference.maxpool3d_fp8(x8, c, kernel, pad).view(U8), "maxpool3d_fp8")
+    m8 = contract("zsv_meanpool_fp8", lambda q: L.zsv_meanpool_fp8(q["x"], n, s, c, q["out"], None), {"out": (F32, (n, c))}, ins=dict(x=x8))["out"]
+    same_bytes(m8, inference.meanpool_fp8(x8, c), "meanpool_fp8")
+    ROWS_RUN[("CL_POOL_CASES", "cl_pools")].add(shape)
+
+
+CONVERTER_SHAPES = list(params_of(TAMP.test_layout_converters_round_trip))
+
+
+@pytest.mark.parametrize("shape", CONVERTER_SHAPES, ids=["x".join(map(str, s)) for s in CONVERTER_SHAPES])
+def test_layout_converters(shape):
+    L = lib()
+    g = torch.Generator().manual_seed(sum(shape))
+    n, c, t, h, w = shape
+    s, cp = t * h * w, inference.channel_pitch(c)
+    x = torch.randn(shape, generator=g).to(DEV)
+    cl = contract("zsv_ncs_f32_to_cl_bf16", lambda q: L.zsv_ncs_f32_to_cl_bf16(q["x"], n, s, c, q["out"], None), {"out": (BF16, (n, t, h, w, cp))},
+                  ins=dict(x=x))["out"]
+    same_bytes(cl, amp.ncdhw_to_cl_bf16(x), "ncs_f32_to_cl_bf16")
+    back = contract("zsv_cl_bf16_to_ncs_f32", lambda q: L.zsv_cl_bf16_to_ncs_f32(q["x"], n, s, c, q["out"], None), {"out": (F32, shape)}, ins=dict(x=cl))["out"]
+    same_bytes(back, amp.cl_to_ncdhw_f32(cl, c), "cl_bf16_to_ncs_f32")
+    assert torch.equal(back, x.to(BF16).float())
+    ROWS_RUN[("converters", "converters")].add(shape)
+
+
+# (N, C, T, H, W), (padH, padW), (Hp, Wp): C = 3 and fewer, a border on every side, Hp / Wp beyond the frame + its offset
+CLIP_CASES = [((2, 3, 2, 9, 11), (3, 3), (15, 24)), ((1, 3, 1, 5, 7), (1, 2), (6, 9)), ((1, 1, 3, 4, 5), (0, 0), (4, 8)), ((3, 2, 1, 1, 1), (2, 0), (5, 1))]
+
+
+@pytest.mark.parametrize("shape,pads,padded", CLIP_CASES, ids=["x".join(map(str, c[0])) for c in CLIP_CASES])
+def test_clip_to_bf16(shape, pads, padded):
+    L = lib()
+    g = torch.Generator().manual_seed(sum(shape))
+    n, c, t, h, w = shape
+    x = torch.randn(shape, generator=g).to(DEV)
+    out = contract("zsv_clip_to_bf16", lambda q: L.zsv_clip_to_bf16(q["x"], n, c, t, h, w, pads[0], pads[1], padded[0], padded[1], q["out"], None),
+                   {"out": (BF16, (n, t) + padded + (4,))}, ins=dict(x=x))["out"]
+    same_bytes(out, inference.clip_to_bf16(x, pads[0], pads[1], padded[0], padded[1]), "clip_to_bf16")
+    want = torch.zeros((n, t) + padded + (4,), device=DEV)
+    want[:, :, pads[0]:pads[0] + h, pads[1]:pads[1] + w, :c] = x.permute(0, 2, 3, 4, 1)
+    assert torch.equal(out, want.to(BF16)), "the frame at (padH, padW) inside a zero border"
+    ROWS_RUN[("CLIP_CASES", "clip_to_bf16")].add(shape)
+
+
+@pytest.mark.parametrize("shift", [0, 2, 14])
+@pytest.mark.parametrize("count", [1, 255, 4 * 256 + 3])
+def test_absmax_bf16(count, shift):
+    """The head / 16-byte-aligned body / tail split starts at the input's address: the input begins 0, 2 and 14 bytes past a
+    16-byte boundary.  The result is a maximum, so the 0x7F band is the run that matters (|NaN| wins the integer maximum too)."""
+    L = lib()
+    g = torch.Generator().manual_seed(count)
+    x = torch.randn(count, generator=g).to(BF16).to(DEV)
+    want = x.float().abs().max().reshape(1)
+    for start in (0.0, 1e4):                            # folds into what *amax holds
+        out = contract("zsv_absmax_bf16", lambda q: L.zsv_absmax_bf16(q["x"], count, q["amax"], None),
+                       {"amax": (F32, (1,), torch.full((1,), start, device=DEV))}, ins=dict(x=(x, shift)), count=start == 0.0)["amax"]
+        same_bytes(out, torch.maximum(want, torch.full((1,), start, device=DEV)), f"absmax_bf16 from {start}")
+    amax = torch.zeros(1, device=DEV)
+    inference.absmax_bf16(x, amax)
+    assert torch.equal(amax, want)
+    ROWS_RUN[("absmax", "absmax")].add((count, shift))
+
+
+@pytest.mark.parametrize("c", [1, 3, 64, 260])
+def test_bn_eval_coeffs(c):
+    L = lib()
+    o = _bn_operands((2, c, 1, 1, 1))
+    pitch = (c + 15) // 16 * 16
+    coef = contract("zsv_bn_eval_coeffs", lambda p: L.zsv_bn_eval_coeffs(c, p["gamma"], p["beta"], p["rm"], p["rv"], 1e-5, p["coef"], pitch, None),
+                    {"coef": (F32, (2, pitch))}, ins=pick(o, "gamma", "beta", "rm", "rv"))["coef"]
+    _, coef_w = ops._BatchNormFrozenDeferred.apply(o["x"], o["gamma"], o["beta"], o["rm"], o["rv"], 1e-5)
+    same_bytes(coef, coef_w, "bn_eval_coeffs")
+    assert int(torch.count_nonzero(coef[:, c:])) == 0, "coef entries C .. coef_pitch-1 must be zero"
+    a = o["gamma"].double() / torch.sqrt(o["rv"].double() + 1e-5)
+    T.close(coef[0, :c], a, rtol=1e-6, what="scale")
+    T.close(coef[1, :c], o["beta"].double() - o["rm"].double() * a, rtol=1e-6, what="shift")
+    ROWS_RUN[("bn_eval_coeffs", "bn_eval_coeffs")].add(c)
+
+
+@pytest.mark.parametrize("n", [1, 1000, 4099])         # (1000: test_adam_step_matches_torch)
+def test_adam_step(n):
+    L = lib()
+    g = torch.Generator().manual_seed(4 + n)
+    p0, grad, m0 = (torch.randn(n, generator=g).to(DEV) for _ in range(3))
+    v0 = torch.rand(n, generator=g).to(DEV)
+    out = contract("zsv_adam_step", lambda q: L.zsv_adam_step(q["p"], q["g"], q["exp_avg"], q["exp_avg_sq"], n, 1e-3, 0.9, 0.999, 1e-8, 3, None),
+                   {"p": (F32, (n,), p0), "exp_avg": (F32, (n,), m0), "exp_avg_sq": (F32, (n,), v0)}, ins=dict(g=grad))
+    pw, mw, vw = p0.clone(), m0.clone(), v0.clone()
+    ops.adam_step_(pw, grad, mw, vw, 3, 1e-3)
+    for name, want in (("p", pw), ("exp_avg", mw), ("exp_avg_sq", vw)):
+        same_bytes(out[name], want, f"adam_step: {name}")
+    ROWS_RUN[("adam_step", "adam_step")].add(n)
+
+
+# ---- clip pre-processing: every video / image is a guarded uint8 buffer of its own, the device tables point into them ----
+# crop 16 (short side resized to 256): the smallest frames of test_clip_batch_gpu.py / test_still_image_gpu.py.  (top, left, flip)
+# per video: the four corners of the resized frame -- every frame edge, both flips, the bottom-right corner -- and the centre.
+VIDEO_SIZES = [(40, 50), (41, 53), (50, 40)]
+
+
+def _corner_params(sizes, crop, size):
+    res = [preprocess.resized_hw(h, w, size)[:2] for h, w in sizes]
+    corners = [lambda r: (0, 0, 0), lambda r: (r[0] - crop, r[1] - crop, 1), lambda r: (0, r[1] - crop, 1), lambda r: (r[0] - crop, 0, 0),
+               lambda r: ((r[0] - crop) // 2, (r[1] - crop) // 2, 1)]
+    return res, [[f(r) for r in res] for f in corners]
+
+
+def test_clip_transform_one_size():
+    L = lib()
+    crop, n, t = 16, 5, 2
+    clips = preprocess.ClipTransform(False, crop)
+    for h, w in VIDEO_SIZES[:2]:
+        frames = torch.randint(0, 256, (n, t, h, w, 3), dtype=U8, generator=torch.Generator().manual_seed(h * w)).to(DEV)
+        hres, wres, inv_scale = preprocess.resized_hw(h, w, clips.size)
+        _, rounds = _corner_params([(h, w)], crop, clips.size)
+        params = [r[0] for r in rounds]                             # one corner per clip
+        out = contract("zsv_clip_transform",
+                       lambda p: L.zsv_clip_transform(p["frames"], n, t, h, w, hres, wres, float(inv_scale), crop, p["params"], p["out"], None),
+                       {"out": (F32, (n, 3, t, crop, crop))}, ins=dict(frames=frames, params=torch.tensor(params, dtype=I32).to(DEV)))["out"]
+        same_bytes(out, clips(frames, params), f"clip_transform {h}x{w}")
+        ROWS_RUN[("clip_transform", "clip_transform")].add((h, w))
+
+
+def test_clip_transform_batch():
+    L = lib()
+    crop, nc, t = 16, 2, 2
+    clips = preprocess.VideoClips(False, n_clips=nc, clip_len=t, crop_size=crop)
+    g = torch.Generator().manual_seed(11)
+    videos = [torch.randint(0, 256, (nc * t, h, w, 3), dtype=U8, generator=g).to(DEV) for h, w in VIDEO_SIZES]
+    _, rounds = _corner_params(VIDEO_SIZES, crop, clips.size)
+    names = [f"video{b}" for b in range(len(videos))]
+    for i, params in enumerate(rounds):
+        out = contract("zsv_clip_transform_batch",
+                       lambda p: L.zsv_clip_transform_batch(p["table"](torch.from_numpy(preprocess.video_table([p[k] for k in names], VIDEO_SIZES, params,
+                                                                                                                 clips.size)), "video table"),
+                                                            len(videos), nc, t, crop, p["out"], None),
+                       {"out": (F32, (len(videos), nc, 3, t, crop, crop))}, ins=dict(zip(names, videos)), count=i == 0)["out"]
+        same_bytes(out, clips(videos, params), f"clip_transform_batch, windows {params}")
+    ROWS_RUN[("clip_transform", "clip_transform_batch")].update(VIDEO_SIZES)
+
+
+def test_still_image_clips():
+    L = lib()
+    crop, nc, t = 16, 1, 4
+    sizes = [(40, 50), (41, 53), (130, 141)]
+    clips = preprocess.StillImageClips(clip_len=t, n_clips=nc, crop_size=crop)
+    images = [torch.randint(0, 256, (h, w, 3), dtype=U8, generator=torch.Generator().manual_seed(h + w)).to(DEV) for h, w in sizes]
+    # (top, left, side) per frame: flush with the top-left and the bottom-right corner at the smallest and the largest side the
+    # image and the kernel allow (crop <= side <= 8 * crop), the other two corners in between
+    trajectories = []
+    for h, w in sizes:
+        big = min(h, w, 8 * crop)
+        mid = (crop + big) // 2
+        trajectories.append(np.array([[0, 0, big], [h - crop, w - crop, crop], [0, w - mid, mid], [h - big, w - big, big]]))
+    names = [f"image{b}" for b in range(len(images))]
+    ftab = torch.from_numpy(np.stack(trajectories).astype(np.int32)).to(DEV)
+    max_side = int(max(tr[:, 2].max() for tr in trajectories))
+    out = contract("zsv_still_image_clips",
+                   lambda p: L.zsv_still_image_clips(p["table"](torch.tensor([[p[k], im.shape[0], im.shape[1]] for k, im in zip(names, images)],
+                                                                             dtype=torch.int64), "image table"),
+                                                     p["frames"], len(images), nc, t, crop, max_side, p["out"], None),
+                   {"out": (F32, (len(images), nc, 3, t, crop, crop))}, ins=dict(zip(names, images), frames=ftab))["out"]
+    same_bytes(out, clips(images, trajectories), "still_image_clips")
+    ROWS_RUN[("still_image", "still_image_clips")].update(sizes)
+
 
 
 # =========================================================================================================================
@@ -865,6 +1182,11 @@ ENTRY_POINTS = [
     "zsv_conv3d_bf16_pack + zsv_conv3d_bf16_fwd", "zsv_conv3d_bf16_pack_dgrad + zsv_conv3d_bf16_fwd", "zsv_conv3d_fp8_pack + zsv_conv3d_fp8_fwd",
     "zsv_conv3d_bf16_fwd_stats", "zsv_bn_cl_fwd_train", "zsv_bn_cl_fwd_train_stats", "zsv_bn_cl_bwd", "zsv_bn_cl_bwd (mask recomputed from z)",
     "zsv_bn_cl_bwd_eval", "zsv_bn_cl_bwd_eval (mask recomputed from z)", "zsv_relu_bias_bwd_cl", "zsv_conv3d_bf16_wgrad",
+    # the entry points that take no workspace: their inputs and outputs are pinned all the same
+    "zsv_relu_fwd", "zsv_relu_bwd", "zsv_add_relu_fwd", "zsv_meanpool_fwd", "zsv_meanpool_bwd", "zsv_maxpool3d_fwd", "zsv_maxpool3d_bwd",
+    "zsv_maxpool3d_bf16", "zsv_maxpool3d_bf16_bwd", "zsv_maxpool3d_fp8", "zsv_meanpool_bf16", "zsv_meanpool_bf16_bwd", "zsv_meanpool_fp8",
+    "zsv_cl_bf16_to_ncs_f32", "zsv_ncs_f32_to_cl_bf16", "zsv_clip_to_bf16", "zsv_absmax_bf16", "zsv_bn_eval_coeffs", "zsv_adam_step",
+    "zsv_clip_transform", "zsv_clip_transform_batch", "zsv_still_image_clips",
 ]
 
 
@@ -887,6 +1209,11 @@ def test_every_entry_point_ran_and_on_every_row(capsys):
                 ("test_cosine_topk", "topk"): len(params_of(TA.test_cosine_topk_c_abi_against_scipy)),
                 ("FORWARD_CASES", "bf16_fwd"): len(X.FORWARD_CASES), ("STATS_CASES", "bf16_fwd_stats"): len(X.STATS_CASES),
                 ("DGRAD_CASES", "bf16_pack_dgrad"): len(X.DGRAD_CASES), ("WGRAD_CASES", "bf16_wgrad"): len(X.WGRAD_CASES),
-                ("bn_cl", "bn_cl"): len(BN_CL_CASES), ("fp8 CASES", "fp8_fwd"): len(F8.CASES)}
+                ("bn_cl", "bn_cl"): len(BN_CL_CASES), ("fp8 CASES", "fp8_fwd"): len(F8.CASES),
+                ("elementwise", "elementwise"): len(ELEMENTWISE_SHAPES), ("POOL_CASES", "maxpool"): len(T.POOL_CASES),
+                ("CL_POOL_CASES", "cl_pools"): len(CL_POOL_CASES), ("converters", "converters"): len(CONVERTER_SHAPES),
+                ("CLIP_CASES", "clip_to_bf16"): len(CLIP_CASES), ("absmax", "absmax"): 9, ("bn_eval_coeffs", "bn_eval_coeffs"): 4,
+                ("adam_step", "adam_step"): 3, ("clip_transform", "clip_transform"): 2, ("clip_transform", "clip_transform_batch"): len(VIDEO_SIZES),
+                ("still_image", "still_image_clips"): 3}
     for key, count in expected.items():
         assert len(ROWS_RUN[key]) == count, f"{key}: {len(ROWS_RUN[key])} of {count} rows ran"
