@@ -611,6 +611,40 @@ int zsv_avg_advance(zsv_avg_state* avg_state_device, const zsv_scaler_state* sca
  * addresses everything else is keyed on) and back, exactly. */
 int zsv_swap_multi(const zsv_pair_tensor* table_device, int32_t count, int64_t total_chunks, void* stream);
 
+/* ---- torch.optim.SGD (momentum, dampening, Nesterov, L2 weight decay, maximize) in one launch ---------------------------
+ * ONE entry point over the zsv_adam_tensor table: `exp_avg` is the momentum buffer (may be NULL when momentum == 0, must
+ * not be otherwise), `exp_avg_sq` is not read (may be NULL), so zsv_grad_check_multi, zsv_grad_norm_multi / _finalize and
+ * zsv_grad_unscale_multi work on the same table.  What a step does not use is a NULL pointer:
+ *   clip_device        NULL: no clipping
+ *   state_device       NULL: no loss scaler.  Otherwise found_inf != 0 skips the whole launch (decay, buffers and the average
+ *                      included) and g_mem is multiplied by (float)(1 / (double)scale) unless `grads_unscaled` != 0
+ *   shadows_device,    both NULL: no weight average.  Otherwise as for zsv_adam_multi_avg (`count` pointers parallel to the
+ *   avg_state_device   table; the state is read, zsv_avg_advance advances it)
+ * Per element, in torch's order (torch/optim/sgd.py::_single_tensor_sgd), all fp32:
+ *   g = g_mem * inv_scale; g = g * clip_coef      (two separate products)
+ *   g = maximize ? -g : g
+ *   g = fma(weight_decay, p, g)                   (weight_decay != 0)
+ *   momentum != 0:  buf = first ? g : fma(1 - dampening, g, momentum * buf);  g = nesterov ? fma(momentum, buf, g) : buf
+ *   p = fma(-lr, g, p)
+ *   shadow <- the averaging rule with the new p
+ * `first` is torch's "the momentum buffer does not exist yet" (the buffer is then written and not read).  It differs from a
+ * zero-initialised buffer only when dampening != 0.  ONE rule decides it, on the device:
+ *       first  iff  steps_done == first_step,   steps_done = state_device->steps_done, or 0 without a scaler
+ * so without a scaler the host passes 0 on the first step and -1 (never) afterwards; with a scaler it passes the value
+ * steps_done had when the optimizer had no buffers yet (-1: it has them) and the device decides: a first step the scaler skips
+ * leaves steps_done where it was, and the next step is the first one again, as under GradScaler, which never calls
+ * optimizer.step() on a skipped step.
+ * p, g, buf and the shadows need only be 4-byte aligned, each on its own: a tensor whose pointers are all 16-byte aligned is
+ * walked 16 bytes per lane, any other 4 bytes per lane, to the same bits.  No atomics.  No element outside [0, n) of any
+ * array is read or written.  ZSV_E_NULL: table NULL, or one of shadows / avg state NULL; ZSV_E_BAD_SHAPE: count <= 0,
+ * total_chunks out of range, lr / momentum / weight_decay negative or not finite, nesterov without momentum > 0 and
+ * dampening == 0, ema_weight > 1. */
+int zsv_sgd_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr, float momentum,
+                  float dampening, int32_t nesterov, double weight_decay, int32_t maximize,
+                  const zsv_clip_record* clip_device, const zsv_scaler_state* state_device, int32_t grads_unscaled,
+                  int32_t first_step, float* const* shadows_device, const zsv_avg_state* avg_state_device, float ema_weight,
+                  void* stream);
+
 /* ---- weight panels packed ahead of the call ---------------------------------------------------------------------------
  * Every forward / dgrad entry point above first re-lays its weights out (a "panel": the direct kernel's [block][tap][16][m]
  * image, the Winograd kernels' transformed weights, the stride-2 dgrad's tap-major image) in a small launch of its own: 76

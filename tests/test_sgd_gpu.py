@@ -1,0 +1,560 @@
+"""``optim.FusedSGD`` / ``zsv_sgd_multi`` on the device against ``torch.optim.SGD``.
+
+Two yardsticks.  On dyadic operands (parameters k/8 with |k| <= 32, gradients j/4 with |j| <= 32, lr 2^-3, momentum / dampening 1/2, weight decay 1/4) every
+intermediate of three steps is an fp32 number -- the test proves that by running the recurrence in fp64 and checking that
+each intermediate survives a round trip through fp32 -- so the result has to be torch's on the CPU, value for value, whatever
+the order or the contraction of the fp32 operations.  On random operands the yardstick is torch's own error: with ``ref64`` the
+recurrence in fp64 on the CPU,
+
+    max|fused - ref64|  <=  2 * max|torch_gpu - ref64|  +  2^-23 * max|ref64|        per parameter and per momentum buffer,
+
+the factor 2 covering a different contraction / order of the same fp32 operations."""
+import copy
+import itertools
+import struct
+import subprocess
+import sys
+from types import SimpleNamespace
+
+import pytest
+import torch
+from torch.optim.swa_utils import AveragedModel  # noqa: F401  (through _averaged)
+
+pytestmark = pytest.mark.gpu
+
+import guarded as G  # noqa: E402
+from bf16_exact_cases import assert_same_values  # noqa: E402
+from test_weight_average_gpu import EPS, _Holder, _averaged, _bar_ema, _close  # noqa: E402  (the shadow bars of FusedAdam's average)
+from zeroshotvideoclassification_amd import _lib, ddp, optim, train  # noqa: E402
+from zeroshotvideoclassification_amd._tables import CHUNK  # noqa: E402
+
+DEV = "cuda"
+
+
+# ---- the rule in fp64 ------------------------------------------------------------------------------------------------------
+def _fp32(x, what):
+    """An intermediate of the exact case: it must be an fp32 number."""
+    assert torch.equal(x.float().double(), x), f"{what} is not exact in fp32: the case proves nothing"
+    return x
+
+
+def ref_step(p, g, buf, hp, first, check=None, coef=1.0):
+    """torch/optim/sgd.py::_single_tensor_sgd in fp64 on one tensor: returns (p, buf).  ``buf`` is None with momentum == 0;
+    ``first``: the momentum buffer does not exist yet.  ``check`` sees every intermediate."""
+    ok = check or (lambda x, what: x)
+    g = ok(g * coef, "g * clip_coef")
+    if hp.get("maximize", False):
+        g = -g
+    if hp.get("weight_decay", 0) != 0:
+        g = ok(g + ok(hp["weight_decay"] * p, "wd * p"), "g + wd * p")
+    momentum, dampening = hp.get("momentum", 0), hp.get("dampening", 0)
+    if momentum != 0:
+        if first:
+            buf = g.clone()
+        else:
+            buf = ok(ok(momentum * buf, "momentum * buf") + ok((1 - dampening) * g, "(1 - dampening) * g"), "buf")
+        g = ok(g + ok(momentum * buf, "momentum * buf"), "g + momentum * buf") if hp.get("nesterov", False) else buf
+    return ok(p - ok(hp["lr"] * g, "lr * g"), "p - lr * g"), buf
+
+
+def _bar(got, torch_gpu, ref64, what):
+    """The bar of the module docstring."""
+    got, torch_gpu = got.detach().double().cpu(), torch_gpu.detach().double().cpu()
+    err, yard = (got - ref64).abs().max().item(), (torch_gpu - ref64).abs().max().item()
+    bound = 2 * yard + EPS * ref64.abs().max().item()
+    print(f"{what}: |fused - ref64| {err:.3e}  |torch - ref64| {yard:.3e}  bound {bound:.3e}")
+    assert err <= bound, (what, err, yard, bound)
+
+
+# ---- 1: exact ---------------------------------------------------------------------------------------------------------------
+def _exact_cases():
+    for momentum, dampening, wd, nesterov, maximize in itertools.product((0, 0.5), (0, 0.5), (0, 0.25), (False, True), (False, True)):
+        if nesterov and (momentum == 0 or dampening != 0):
+            continue                                          # torch refuses these
+        yield dict(lr=2.0 ** -3, momentum=momentum, dampening=dampening, weight_decay=wd, nesterov=nesterov, maximize=maximize)
+
+
+def _dyadic(seed=0):
+    """Every (k, j) pair once: parameters k/8, and three gradients j/4 with j permuted per step, |j| <= 32.  |k| <= 32: with
+    parameters up to 8 the two Nesterov cases with weight decay leave fp32 in their third step (lr, weight decay and momentum put
+    the result on a 2^-21 grid, and 167 of the 8385 values end in [8, 10.4), which takes 25 bits), so nothing could be demanded
+    of them; from |p| <= 4 every intermediate of every case is exact, which the test asserts before it compares anything."""
+    k = torch.arange(-32, 33, dtype=torch.float64)
+    j = torch.arange(-32, 33, dtype=torch.float64)
+    p = (k[:, None] / 8).expand(65, 65).contiguous()
+    gen = torch.Generator().manual_seed(seed)
+    grads = [(j[torch.randperm(65, generator=gen)][None, :] / 4).expand(65, 65).contiguous() for _ in range(3)]
+    return p, grads
+
+
+@pytest.mark.parametrize("hp", list(_exact_cases()), ids=lambda hp: "m{momentum}-d{dampening}-wd{weight_decay}-n{nesterov:d}-max{maximize:d}".format(**hp))
+def test_exact_case_equals_torch_on_the_cpu(hp):
+    """1: three steps on dyadic operands: value for value torch.optim.SGD on the CPU (-0 == +0)."""
+    p0, grads = _dyadic()
+    # the proof of exactness: the fp64 recurrence never rounds in fp32
+    p64, buf64 = p0, None
+    for step, g in enumerate(grads):
+        p64, buf64 = ref_step(p64, g, buf64, hp, first=step == 0, check=_fp32)
+    cpu = torch.nn.Parameter(p0.float())
+    ref = torch.optim.SGD([cpu], **hp)
+    dev = torch.nn.Parameter(p0.float().to(DEV))
+    opt = optim.FusedSGD([dev], **hp)
+    for g in grads:
+        cpu.grad, dev.grad = g.float(), g.float().to(DEV)
+        ref.step()
+        opt.step()
+    assert_same_values(cpu, p64, what="torch on the CPU against the fp64 recurrence")
+    assert_same_values(dev, cpu, exact=p64, what="parameters")
+    if hp["momentum"] != 0:
+        assert_same_values(opt.state[dev]["momentum_buffer"], ref.state[cpu]["momentum_buffer"], exact=buf64, what="momentum buffer")
+    else:
+        assert "momentum_buffer" not in opt.state[dev]
+
+
+# ---- 2: chunk and alignment edges, raw entry point ----------------------------------------------------------------------------
+SIZES = (1, 3, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 5)
+EDGE_HP = dict(lr=2.0 ** -3, momentum=0.5, dampening=0.5, weight_decay=0.25)
+# element offsets of (p, g, buf, shadow) from a 16-byte boundary.  "own": four allocations of their own; the others: four slices of
+# ONE flat buffer.  With offsets (0, 0, 0, 0) every pointer is 16-byte aligned (the 16-byte form); in the other three only some are.
+LAYOUTS = {"own": None, "slice0": (0, 0, 0, 0), "slice1": (1, 2, 3, 0), "slice2": (2, 3, 0, 1), "slice3": (3, 0, 1, 2)}
+
+
+def _edge_operands(n, seed):
+    gen = torch.Generator().manual_seed(seed)
+    p = torch.randint(-64, 65, (n,), generator=gen).double() / 8
+    g = torch.randint(-32, 33, (n,), generator=gen).double() / 4
+    buf = torch.randint(-32, 33, (n,), generator=gen).double() / 4
+    shadow = torch.randint(-64, 65, (n,), generator=gen).double() / 8
+    return p, g, buf, shadow
+
+
+class _Flat:
+    """p, g, buf and shadow of one tensor as slices of ONE guarded flat buffer whose every other element is a NaN: a read outside
+    a slice reaches the result, a write outside a slice changes a poison element or a band."""
+    GAP = 64
+
+    def __init__(self, arrays, offsets):
+        n = arrays[0].numel()
+        stride = (n + 3) // 4 * 4 + self.GAP
+        self.g = G.guarded(4 * (4 * stride + self.GAP), DEV, 0xFF)
+        self.flat = self.g.view(torch.float32, (4 * stride + self.GAP,))
+        self.starts = [self.GAP // 2 + r * stride + off for r, off in enumerate(offsets)]
+        self.n = n
+        for s, a in zip(self.starts, arrays):
+            self.flat[s:s + n] = a.float().to(DEV)
+        self.before = self.flat.view(torch.int32).clone()
+
+    def ptr(self, r):
+        return self.flat.data_ptr() + 4 * self.starts[r]
+
+    def get(self, r):
+        return self.flat[self.starts[r]:self.starts[r] + self.n]
+
+    def check(self, what):
+        self.g.check(what)
+        now = self.flat.view(torch.int32)
+        outside = torch.ones_like(now, dtype=torch.bool)
+        for s in self.starts:
+            outside[s:s + self.n] = False
+        assert torch.equal(now[outside], self.before[outside]), f"{what}: an element outside the slices was written"
+        assert torch.equal(self.get(1).view(torch.int32), self.before[self.starts[1]:self.starts[1] + self.n]), f"{what}: g was written"
+
+
+class _Own:
+    """The same four arrays, each the payload of a guarded allocation of its own (256-byte aligned, NaN bands)."""
+
+    def __init__(self, arrays):
+        self.bufs = [G.guarded_copy(a.float(), DEV, guard_byte=0xFF) for a in arrays]
+        self.n = arrays[0].numel()
+        self.g_before = self.bufs[1].bytes()
+
+    def ptr(self, r):
+        return self.bufs[r].ptr
+
+    def get(self, r):
+        return self.bufs[r].view(torch.float32, (self.n,))
+
+    def check(self, what):
+        for r, b in enumerate(self.bufs):
+            b.check(f"{what} array {r}")
+        assert torch.equal(self.bufs[1].bytes(), self.g_before), f"{what}: g was written"
+
+
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+def test_chunk_and_alignment_edges_stay_in_bounds(layout):
+    """2: tensors of 1 .. 2 * 4096 + 5 elements in ONE launch (six descriptors, first_chunk 0, 1, 2, 3, 4, 6), each array in
+    poisoned surroundings: the bands hold 0xFF (a NaN, which survives every product, sum and fma of the rule -- there is no max and
+    no comparison on data in it), so a read outside [0, n) reaches a result and a write outside [0, n) changes a band.  One step
+    that reads the buffer (not the first) with weight decay and an EMA shadow, on dyadic operands: values equal the fp64 rule."""
+    lib = _lib.load()
+    offsets = LAYOUTS[layout]
+    held, rows, first = [], [], 0
+    for i, n in enumerate(SIZES):
+        arrays = _edge_operands(n, 100 + i)
+        h = _Own(arrays) if offsets is None else _Flat(arrays, offsets)
+        if offsets is not None:
+            assert [(h.ptr(r) % 16) // 4 for r in range(4)] == list(offsets)
+        held.append((h, arrays))
+        rows.append((h.ptr(0), h.ptr(1), h.ptr(2), 0, n, first))
+        first += (n + CHUNK - 1) // CHUNK
+    table = torch.frombuffer(bytearray(b"".join(struct.pack("<QQQQqq", *r) for r in rows)), dtype=torch.uint8).to(DEV)
+    shadows = torch.tensor([h.ptr(3) for h, _ in held], dtype=torch.int64, device=DEV)
+    avg_state = torch.tensor([1], dtype=torch.int32, device=DEV)                  # one step averaged already: the shadow is read
+    hp = EDGE_HP
+    _lib.check(lib.zsv_sgd_multi(table.data_ptr(), len(rows), first, hp["lr"], hp["momentum"], hp["dampening"], 0, hp["weight_decay"],
+                                 0, None, None, 0, -1, shadows.data_ptr(), avg_state.data_ptr(), 0.5,
+                                 torch.cuda.current_stream().cuda_stream), "zsv_sgd_multi")
+    torch.cuda.synchronize()
+    for (h, (p, g, buf, shadow)), n in zip(held, SIZES):
+        what = f"{layout} n={n}"
+        h.check(what)
+        p1, buf1 = ref_step(p, g, buf, hp, first=False, check=_fp32)
+        s1 = _fp32(p1 - (p1 - shadow) * 0.5, "shadow")                             # lerp(avg, p, 0.5), torch's form for w >= 0.5
+        assert_same_values(h.get(0), p1, what=what + " p")
+        assert_same_values(h.get(2), buf1, what=what + " buf")
+        assert_same_values(h.get(3), s1, what=what + " shadow")
+    assert int(avg_state) == 1                                                     # read, not advanced
+
+
+# ---- 3: random operands, two groups -------------------------------------------------------------------------------------------
+SHAPES = [(5000,), (3, 7, 11), (1,), (CHUNK + 1,), (64, 64), (2 * CHUNK + 5,)]
+GROUPS = [dict(lr=0.05, momentum=0.9, dampening=0.0, weight_decay=1e-2, nesterov=True),
+          dict(lr=0.02, momentum=0.8, dampening=0.3, weight_decay=1e-3, nesterov=False)]
+
+
+def _random(seed, steps):
+    gen = torch.Generator().manual_seed(seed)
+    ps = [torch.randn(*s, generator=gen) for s in SHAPES]
+    grads = [[torch.randn(*s, generator=gen) for s in SHAPES] for _ in range(steps)]
+    return ps, grads
+
+
+def _split(ps, groups=GROUPS):
+    half = len(ps) // 2
+    return [dict(params=ps[:half], **groups[0]), dict(params=ps[half:], **groups[1])]
+
+
+def _hp_of(i, groups=GROUPS):
+    return groups[0] if i < len(SHAPES) // 2 else groups[1]
+
+
+def _ref_run(ps, grads, groups=GROUPS, first_step=0, coefs=None):
+    """ref64 over the steps; ``first_step``: the index of the first step that is taken (the earlier ones are skipped)."""
+    p64, b64 = [p.double() for p in ps], [None] * len(ps)
+    for step, gs in enumerate(grads):
+        if step < first_step:
+            continue
+        for i, g in enumerate(gs):
+            p64[i], b64[i] = ref_step(p64[i], g.double(), b64[i], _hp_of(i, groups), first=step == first_step,
+                                      coef=1.0 if coefs is None else coefs[step])
+    return p64, b64
+
+
+def _twins(ps, make_fused, make_torch):
+    a = [torch.nn.Parameter(p.clone().to(DEV)) for p in ps]
+    b = [torch.nn.Parameter(p.clone().to(DEV)) for p in ps]
+    return a, make_fused(a), b, make_torch(b)
+
+
+def _compare(fused_ps, fused_opt, torch_ps, torch_opt, p64, b64, what):
+    for i, (a, b) in enumerate(zip(fused_ps, torch_ps)):
+        _bar(a, b, p64[i], f"{what} p[{i}]")
+        _bar(fused_opt.state[a]["momentum_buffer"], torch_opt.state[b]["momentum_buffer"], b64[i], f"{what} buf[{i}]")
+
+
+def test_random_operands_against_torch_on_the_same_device():
+    """3: five steps, two groups with different lr / momentum / dampening / weight decay, one of them Nesterov."""
+    ps, grads = _random(11, 5)
+    a, fused, b, ref = _twins(ps, lambda q: optim.FusedSGD(_split(q)), lambda q: torch.optim.SGD(_split(q), foreach=True))
+    gen0 = _lib.raw_param_generation()
+    for gs in grads:
+        for x, y, g in zip(a, b, gs):
+            x.grad, y.grad = g.to(DEV), g.to(DEV)
+        fused.step()
+        ref.step()
+    assert _lib.raw_param_generation() == gen0 + 5                                 # note_raw_write() after every step
+    p64, b64 = _ref_run(ps, grads)
+    _compare(a, fused, b, ref, p64, b64, "random")
+    # a parameter that joins late: fine with dampening == 0 (group 0), refused with dampening != 0 (group 1)
+    late = [torch.nn.Parameter(torch.ones(5, device=DEV)) for _ in range(2)]
+    for x in a:
+        x.grad = None
+    fused.param_groups[0]["params"].append(late[0])
+    late[0].grad = torch.ones(5, device=DEV)
+    fused.step()
+    assert torch.equal(fused.state[late[0]]["momentum_buffer"], late[0].grad + 1e-2 * torch.ones(5, device=DEV))
+    late[0].grad = None
+    fused.param_groups[1]["params"].append(late[1])
+    late[1].grad = torch.ones(5, device=DEV)
+    with pytest.raises(RuntimeError, match="dampening != 0"):
+        fused.step()
+
+
+# ---- 4: scaler -------------------------------------------------------------------------------------------------------------------
+SCALED_GROUPS = [dict(GROUPS[0], nesterov=False, dampening=0.5), dict(GROUPS[1], dampening=0.5)]
+
+
+def _scaled_run(ps, grads, unscale_first):
+    a = [torch.nn.Parameter(p.clone().to(DEV)) for p in ps]
+    opt = optim.FusedSGD(_split(a, SCALED_GROUPS))
+    scaler = optim.LossScaler(init_scale=4.0)
+    start = [x.detach().clone() for x in a]
+    for step, gs in enumerate(grads):
+        scale = scaler.get_scale()
+        for x, g in zip(a, gs):
+            x.grad = (g * scale).to(DEV)
+        if unscale_first:
+            scaler.unscale_(opt)
+            if step > 0:
+                for x, g in zip(a, gs):
+                    assert torch.equal(x.grad.cpu(), g)                            # rewritten in place: scale is a power of two
+        scaler.step(opt)
+        scaler.update()
+        if step == 0:
+            # the inf sits in the LAST group: nothing of any group moved, no buffer was written, the scale is halved
+            for x, x0 in zip(a, start):
+                assert torch.equal(x.detach(), x0)
+                assert not opt.state[x]["momentum_buffer"].any()
+            st = scaler.state()
+            assert st["scale"] == 2.0 and st["steps_done"] == 0 and st["found_inf"] == 0
+            assert opt.state_dict()["state"] == {k: {} for k in range(len(a))}     # torch has no buffers yet either
+    return a, opt, scaler
+
+
+def test_scaler_skips_everything_and_the_next_step_is_the_first():
+    """4: init_scale 4, an inf in the last group's gradient on step 1, dampening 0.5 in both groups.  Step 2 is then the first
+    buffer step (buf = g, not 0.5 * g), as in GradScaler + torch.optim.SGD fed the same gradients."""
+    ps, grads = _random(12, 3)
+    grads[0][-1].view(-1)[7] = float("inf")
+    b = [torch.nn.Parameter(p.clone().to(DEV)) for p in ps]
+    ref = torch.optim.SGD(_split(b, SCALED_GROUPS), foreach=True)
+    ref_scaler = torch.amp.GradScaler("cuda", init_scale=4.0)
+    ref_scaler.scale(torch.zeros((), device=DEV))                                  # GradScaler creates its scale lazily
+    for gs in grads:
+        scale = ref_scaler.get_scale()
+        for y, g in zip(b, gs):
+            y.grad = (g * scale).to(DEV)
+        ref_scaler.step(ref)
+        ref_scaler.update()
+    a, opt, scaler = _scaled_run(ps, grads, unscale_first=False)
+    assert scaler.state()["scale"] == ref_scaler.get_scale() == 2.0 and scaler.state()["steps_done"] == 2
+    p64, b64 = _ref_run(ps, grads, SCALED_GROUPS, first_step=1)
+    _compare(a, opt, b, ref, p64, b64, "scaled")
+    # unscale_ then step: the launch does not unscale again -- the same two fp32 products, the same bits
+    a2, opt2, scaler2 = _scaled_run(ps, grads, unscale_first=True)
+    for x, y in zip(a, a2):
+        assert torch.equal(x.detach(), y.detach())
+        assert torch.equal(opt.state[x]["momentum_buffer"], opt2.state[y]["momentum_buffer"])
+    assert scaler2.state() == scaler.state()
+    with pytest.raises(RuntimeError, match="LossScaler"):
+        opt.step()                                                                 # a scaled optimizer is stepped through its scaler
+    # a state dict taken after taken steps carries the buffers and loads into torch
+    twin = torch.optim.SGD(_split([torch.nn.Parameter(p.clone().to(DEV)) for p in ps], SCALED_GROUPS))
+    twin.load_state_dict(opt.state_dict())
+    assert torch.equal(twin.state[twin.param_groups[0]["params"][0]]["momentum_buffer"], opt.state[a[0]]["momentum_buffer"])
+
+
+# ---- 5: clipping -----------------------------------------------------------------------------------------------------------------
+def test_max_grad_norm_is_clip_grad_norm():
+    """5: max_grad_norm over two groups against clip_grad_norm_ + torch.optim.SGD; the norm on the device; .grad untouched."""
+    ps, grads = _random(13, 3)
+    grads = [[g * (0.02 if step == 1 else 1.0) for g in gs] for step, gs in enumerate(grads)]      # step 1 is under the bound
+    norms = [torch.sqrt(sum((g.double() ** 2).sum() for g in gs)).item() for gs in grads]
+    max_norm = 10.0
+    assert norms[1] < max_norm < norms[0]                                                          # both branches of the clamp
+    a, fused, b, ref = _twins(ps, lambda q: optim.FusedSGD(_split(q), max_grad_norm=max_norm),
+                              lambda q: torch.optim.SGD(_split(q), foreach=True))
+    for step, gs in enumerate(grads):
+        for x, y, g in zip(a, b, gs):
+            x.grad, y.grad = g.to(DEV), g.to(DEV)
+        fused.step()
+        torch.nn.utils.clip_grad_norm_(b, max_norm)
+        ref.step()
+        got = fused.grad_norm
+        assert got.is_cuda and got.dim() == 0
+        assert abs(got.item() - norms[step]) <= 1e-6 * norms[step], (step, got.item(), norms[step])
+        for x, g in zip(a, gs):
+            assert torch.equal(x.grad.cpu(), g)                                                    # not rewritten
+    coefs = [min(1.0, max_norm / (n + 1e-6)) for n in norms]
+    p64, b64 = _ref_run(ps, grads, coefs=coefs)
+    _compare(a, fused, b, ref, p64, b64, "clipped")
+
+
+# ---- 6: averaging ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("decay", [0.5, None])
+def test_weight_average_rides_in_the_sgd_launch(decay):
+    """6: WeightAverage(FusedSGD) over 3 taken steps against AveragedModel over torch.optim.SGD, held to the bars
+    tests/test_weight_average_gpu.py holds FusedAdam's average to ((2e-6 + B) * max|ref|, B = 2^-23 / (1 - d) for an EMA and
+    steps * 2^-23 for the equal-weight mean).  A step the scaler skips (the second) leaves n_averaged and the shadows alone."""
+    steps = 4
+    ps, grads = _random(14, steps)
+    grads[1][2].view(-1)[0] = float("nan")
+    holder = _Holder([p.to(DEV) for p in ps])
+    b = list(holder.ps)
+    ref = torch.optim.SGD(_split(b), foreach=True)
+    ref_avg = _averaged(holder, decay)
+    a = [torch.nn.Parameter(p.clone().to(DEV)) for p in ps]
+    opt = optim.FusedSGD(_split(a))
+    avg = optim.WeightAverage(opt, decay=decay)
+    scaler = optim.LossScaler(init_scale=8.0)
+    for step, gs in enumerate(grads):
+        scale = scaler.get_scale()
+        for x, g in zip(a, gs):
+            x.grad = (g * scale).to(DEV)
+        held = [s.clone() for s in avg.shadows().values()]
+        scaler.step(opt)
+        scaler.update()
+        if step == 1:
+            assert int(avg.n_averaged) == 1
+            for s, h in zip(avg.shadows().values(), held):
+                assert torch.equal(s, h)
+            continue
+        for y, g in zip(b, gs):
+            y.grad = g.to(DEV)
+        ref.step()
+        ref_avg.update_parameters(holder)
+    assert int(avg.n_averaged) == steps - 1 and scaler.state()["steps_done"] == steps - 1
+    bar = _bar_ema(decay) if decay is not None else 2e-6 + (steps - 1) * EPS
+    _close(avg.shadows().values(), list(ref_avg.module.ps), bar, f"sgd average d={decay}")
+    with pytest.raises(RuntimeError, match="already has a WeightAverage"):
+        optim.WeightAverage(opt)
+
+
+# ---- 7: buckets ------------------------------------------------------------------------------------------------------------------
+def _tiny_model():
+    from zeroshotvideoclassification_amd import network, synthetic
+    model = network.get_network(SimpleNamespace(network="r2plus1d_18", fixconvs=False, nopretrained=False))
+    model.load_state_dict(synthetic.keyed_state_dict(model.state_dict(), seed=0))
+    return model.to(DEV).train()
+
+
+def test_bucket_path_builds_its_table_once_and_matches_the_dynamic_path():
+    """7: GradientSync(local=True) + FusedSGD(grad_buckets=) on a tiny R(2+1)D-18, two train_steps: the static table from the
+    moment the buckets exist, built once; momentum buffers are views of flat tensors; parameters bit-equal to a twin stepped
+    without buckets (same kernel, same values, other addresses)."""
+    from zeroshotvideoclassification_amd import synthetic
+    x = synthetic.synthetic_clips(2, 4, 32).to(DEV)
+    _, z = synthetic.synthetic_targets(2)
+    z = z.to(DEV)
+    crit = torch.nn.MSELoss()
+    hp = dict(lr=1e-2, momentum=0.9, weight_decay=1e-4)
+
+    model = _tiny_model()
+    sync = ddp.GradientSync(model, local=True)
+    opt = optim.FusedSGD(model.parameters(), grad_buckets=sync, **hp)
+    statics = []
+    for _ in range(3):
+        train.train_step(model, opt, crit, x, z, sync)
+        statics.append(opt._static)
+    assert sync.ready
+    built = [s for s in statics if s is not None]
+    assert len(built) >= 2 and built[0][0] == sync.layout_version
+    assert all(s is built[0] for s in built), "the table was rebuilt although the layout did not change"
+    assert statics[1] is not None and statics[2] is statics[1]                     # from the moment the buckets exist
+    flats = opt._static[5]
+    layout = sync.bucket_layout()
+    assert len(flats) == len(layout)
+    for (flat, rows), (buf_flat,) in zip(layout, flats):
+        assert buf_flat.shape == flat.shape
+        for p, off in rows:
+            assert opt.state[p]["momentum_buffer"].data_ptr() == buf_flat.data_ptr() + 4 * off
+            assert p.grad.data_ptr() == flat.data_ptr() + 4 * off
+    sync.remove()
+
+    twin = _tiny_model()
+    twin_opt = optim.FusedSGD(twin.parameters(), **hp)
+    for _ in range(3):
+        train.train_step(twin, twin_opt, crit, x, z)
+    assert twin_opt._static is None
+    for (k, p), (_, q) in zip(model.named_parameters(), twin.named_parameters()):
+        assert torch.equal(p.detach(), q.detach()), k
+        if p.grad is not None:
+            assert torch.equal(opt.state[p]["momentum_buffer"], twin_opt.state[q]["momentum_buffer"]), k
+
+
+# ---- 8: resume -------------------------------------------------------------------------------------------------------------------
+RESUME_GROUPS = [dict(lr=0.05, momentum=0.9, dampening=0.5, weight_decay=1e-2), dict(lr=0.02, momentum=0.9, dampening=0.5)]
+
+
+def test_resume_from_torch_and_back():
+    """8: torch.optim.SGD(momentum 0.9, dampening 0.5) takes two steps on the device; FusedSGD loads its state and both take two
+    more on the same gradients -- no "first step" is replayed after a load.  Then the reverse: torch loads FusedSGD's state."""
+    ps, grads = _random(15, 6)
+    b = [torch.nn.Parameter(p.clone().to(DEV)) for p in ps]
+    ref = torch.optim.SGD(_split(b, RESUME_GROUPS), foreach=True)
+
+    def torch_steps(opt, params, some):
+        for gs in some:
+            for y, g in zip(params, gs):
+                y.grad = g.to(DEV)
+            opt.step()
+
+    torch_steps(ref, b, grads[:2])
+    a = [torch.nn.Parameter(y.detach().clone()) for y in b]
+    fused = optim.FusedSGD(_split(a, [dict(lr=1.0), dict(lr=1.0)]))               # the groups come from the state dict
+    fused.load_state_dict(copy.deepcopy(ref.state_dict()))
+    assert [g["dampening"] for g in fused.param_groups] == [0.5, 0.5]
+    for gs in grads[2:4]:
+        for x, g in zip(a, gs):
+            x.grad = g.to(DEV)
+        fused.step()
+    torch_steps(ref, b, grads[2:4])
+    p64, b64 = _ref_run(ps, grads[:4], RESUME_GROUPS)
+    _compare(a, fused, b, ref, p64, b64, "torch -> fused")
+    # the reverse: a fresh torch optimizer continues from FusedSGD's state
+    c = [torch.nn.Parameter(x.detach().clone()) for x in a]
+    back = torch.optim.SGD(_split(c, [dict(lr=1.0), dict(lr=1.0)]), foreach=True)
+    back.load_state_dict(copy.deepcopy(fused.state_dict()))
+    torch_steps(back, c, grads[4:])
+    torch_steps(ref, b, grads[4:])
+    for gs in grads[4:]:
+        for x, g in zip(a, gs):
+            x.grad = g.to(DEV)
+        fused.step()
+    p64, b64 = _ref_run(ps, grads, RESUME_GROUPS)
+    _compare(a, fused, b, ref, p64, b64, "six steps")
+    _compare(c, back, b, ref, p64, b64, "fused -> torch")
+
+
+# ---- 9: the default path ----------------------------------------------------------------------------------------------------------
+def _adam_steps():
+    ps, grads = _random(11, 2)
+    a = [torch.nn.Parameter(p.to(DEV)) for p in ps]
+    adam = optim.FusedAdam(a, lr=1e-2)
+    for gs in grads:
+        for x, g in zip(a, gs):
+            x.grad = g.to(DEV)
+        adam.step()
+    return [x.detach().cpu() for x in a]
+
+
+_ADAM_PROBE = """
+import sys, torch
+sys.path.insert(0, sys.argv[1])
+import test_sgd_gpu as T
+assert not hasattr(T.optim.FusedSGD, "_built")
+torch.save(T._adam_steps(), sys.argv[2])
+"""
+
+
+def test_fused_adam_is_untouched_by_a_fused_sgd_in_the_process(tmp_path):
+    """9: FusedAdam on the operands of test 3 in a process that never built a FusedSGD (a child process: that is a property of a
+    process), against the same steps here after a FusedSGD with every option on has been built and stepped on other tensors:
+    bit-identical parameters."""
+    import os
+    here = os.path.dirname(os.path.abspath(__file__))
+    path = str(tmp_path / "plain.pt")
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(here), here] + os.environ.get("PYTHONPATH", "").split(os.pathsep)))
+    child = subprocess.Popen([sys.executable, "-c", _ADAM_PROBE, here, path], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                             text=True)
+    other = [torch.nn.Parameter(torch.randn(3000, device=DEV))]
+    sgd = optim.FusedSGD(other, lr=0.1, momentum=0.9, dampening=0.5, weight_decay=0.1, max_grad_norm=1.0)
+    optim.WeightAverage(sgd, decay=0.5)
+    other[0].grad = torch.randn(3000, device=DEV)
+    sgd.step()
+    after = _adam_steps()
+    log, _ = child.communicate(timeout=300)
+    assert child.returncode == 0, log[-2000:]
+    plain = torch.load(path)
+    for i, (x, y) in enumerate(zip(plain, after)):
+        assert torch.equal(x, y), i

@@ -129,6 +129,10 @@ SIGNATURES = {
     "zsv_adamw_multi_scaled": (c_int, [_P, c_int32, c_int64, c_double, c_float, c_float, c_float, c_double, c_int32, _P, _P,
                                        c_int32, _P]),
     "zsv_grad_accum_multi": (c_int, [_P, c_int32, c_int64, c_float, c_int32, _P]),
+    # table, count, chunks, lr, momentum, dampening, nesterov, weight_decay, maximize, clip, scaler state, grads_unscaled, first_step,
+    # shadows, avg state, ema_weight, stream
+    "zsv_sgd_multi": (c_int, [_P, c_int32, c_int64, c_double, c_float, c_float, c_int32, c_double, c_int32, _P, _P, c_int32, c_int32,
+                              _P, _P, c_float, _P]),
     # the four Adam launches with weight averaging: their own arguments up to the stream, then shadows, avg state, ema_weight
     "zsv_adam_multi_avg": (c_int, [_P, c_int32, c_int64, c_float, c_float, c_float, c_float, c_int32, _P, _P, c_float, _P]),
     "zsv_adam_multi_scaled_avg": (c_int, [_P, c_int32, c_int64, c_float, c_float, c_float, c_float, _P, _P, _P, c_float, _P]),

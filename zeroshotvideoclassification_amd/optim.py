@@ -1,4 +1,4 @@
-"""Fused multi-tensor Adam and an on-device loss scaler (main.py:131-137,195-203).
+"""Fused multi-tensor Adam and SGD and an on-device loss scaler (main.py:131-137,195-203).
 
 The reference steps ``torch.optim.Adam(model.parameters(), lr)`` (betas (0.9, 0.999), eps 1e-8, no weight
 decay, no amsgrad) under ``torch.cuda.amp.GradScaler``: ``scaler.scale(loss).backward();
@@ -45,6 +45,14 @@ every parameter of a ``FusedAdam`` -- ``torch.optim.swa_utils.AveragedModel`` fo
 averaged steps is device state (a step the scaler skips averages nothing, and the host never learns which it was), and
 ``applied()`` swaps the averaged values INTO the live tensors for evaluation.  Without a ``WeightAverage`` the step launches
 what it always did.
+
+``FusedSGD`` is ``torch.optim.SGD`` -- momentum, dampening, Nesterov, L2 weight decay, ``maximize``, the recipe torchvision trained
+these trunks with -- on the same machinery, which lives in ``_FusedOptimizer``, the base class of both: descriptor tables (per step
+or once per bucket layout, the momentum buffers then flat like the buckets), ``max_grad_norm``, ``LossScaler``, ``WeightAverage``.  One
+``zsv_sgd_multi`` launch per parameter group (csrc/sgd.hip: 16 bytes per lane where a tensor's pointers allow it); clip record, scaler
+state and shadows are NULL-able arguments of that ONE entry point.  The state is torch's (``momentum_buffer``).  torch's first step
+copies the gradient into the new buffer; here the launch is told -- by the host, or under a scaler by the device-resident count of
+steps taken, so that a skipped first step leaves the next one the first -- whether it is that step.
 """
 from __future__ import annotations
 
@@ -90,7 +98,7 @@ class LossScaler:
 
     def step(self, optimizer) -> None:
         """``scaler.step(optimizer)`` (main.py:200): unscale + non-finite check + (skipped-if-inf) Adam step."""
-        if not isinstance(optimizer, FusedAdam):
+        if not isinstance(optimizer, _FusedOptimizer):
             raise RuntimeError("LossScaler.step drives optim.FusedAdam (the check, unscale and skip run inside its kernels)")
         optimizer.step(scaler=self)
 
@@ -100,7 +108,7 @@ class LossScaler:
         ``step(optimizer)`` does not unscale again; a second call before ``update()`` raises, as torch's does.  For
         ``scaler.unscale_(opt); torch.nn.utils.clip_grad_norm_(...); scaler.step(opt)``; ``FusedAdam(max_grad_norm=)``
         is the fused route, which needs no ``unscale_``."""
-        if not isinstance(optimizer, FusedAdam):
+        if not isinstance(optimizer, _FusedOptimizer):
             raise RuntimeError("LossScaler.unscale_ drives optim.FusedAdam")
         if id(optimizer) in self._unscaled:
             raise RuntimeError("unscale_() has already been called on this optimizer since the last update().")
@@ -149,43 +157,29 @@ class LossScaler:
         self._state.copy_(host)
 
 
-class FusedAdam(torch.optim.Optimizer):
-    """``torch.optim.Adam`` / ``torch.optim.AdamW`` in one launch per parameter group (module docstring).
+class _FusedOptimizer(torch.optim.Optimizer):
+    """What ``FusedAdam`` and ``FusedSGD`` share: the descriptor tables {p, g, state, state, n, first_chunk} -- rebuilt per step and
+    uploaded through a pinned ring, or built once per layout over the flat gradient buckets -- the ``LossScaler`` they are driven
+    by, ``LossScaler.unscale_``, the norm pass of ``max_grad_norm`` and the ``WeightAverage`` that rides in their launches.  A
+    subclass names its per-parameter state tensors (``_state_keys``), creates them (``_entry_state``) and launches its update."""
 
-    ``weight_decay`` and ``decoupled_weight_decay`` are per parameter group, like ``lr``: ``decoupled_weight_decay=False``
-    is ``Adam(weight_decay=)`` (L2: ``g += wd * p``), ``True`` is ``AdamW`` (``p *= 1 - lr * wd``).  Parameters without a
-    gradient are skipped, decay included, as torch does; a step the ``LossScaler`` skips applies no decay either.
-
-    ``max_grad_norm`` belongs to the optimizer and spans all groups: the gradients are scaled by
-    ``min(1, max_grad_norm / (total_norm + 1e-6))`` -- ``clip_grad_norm_`` with ``norm_type=2`` over all parameters -- on
-    their way into the update.  ``.grad`` itself is not rewritten (torch's ``clip_grad_norm_`` rewrites it).  With
-    ``grad_buckets=`` the norm is that of the averaged gradients, identical on every rank."""
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False,
-                 max_grad_norm=None, grad_buckets=None):
-        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1):
-            raise ValueError("invalid Adam hyper-parameters")
-        self._check_decay(weight_decay)
-        if max_grad_norm is not None:
-            max_grad_norm = float(max_grad_norm)
-            if not (math.isfinite(max_grad_norm) and max_grad_norm > 0):
-                raise ValueError(f"max_grad_norm must be a finite positive number or None, not {max_grad_norm}")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      decoupled_weight_decay=bool(decoupled_weight_decay)))
-        for group in self.param_groups:
-            self._check_decay(group["weight_decay"])
-            if not (math.isfinite(group["lr"]) and group["lr"] >= 0):
-                raise ValueError(f"invalid learning rate {group['lr']}")
+    def _init_fused(self, max_grad_norm, grad_buckets):
         self.max_grad_norm = max_grad_norm
         self._clip = None                                 # zsv_clip_record {total_norm, clip_coef} on the device
         self._partials = None                             # one float per gradient chunk (zsv_grad_norm_multi)
         self._ring = PinnedRing(4)                        # staging for the per-step descriptor tables
         self.grad_buckets = grad_buckets                  # ddp.GradientSync (or None)
         self._static = None                               # (layout_version, table, count, chunks, [(p, grad ptr)], flats)
-        self._host_steps = 0                              # steps taken without a scaler
-        self._resumed = False                             # state came from load_state_dict (a scaler may then join late)
         self._scaler: Optional[LossScaler] = None
         self._average: Optional["WeightAverage"] = None   # set by WeightAverage(optimizer): the update launches average too
+
+    @staticmethod
+    def _check_max_grad_norm(max_grad_norm):
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (math.isfinite(max_grad_norm) and max_grad_norm > 0):
+                raise ValueError(f"max_grad_norm must be a finite positive number or None, not {max_grad_norm}")
+        return max_grad_norm
 
     @staticmethod
     def _check_decay(weight_decay):
@@ -198,39 +192,42 @@ class FusedAdam(torch.optim.Optimizer):
         does not synchronise.  Valid after a step when ``max_grad_norm`` is set.  On a step the scaler skipped it holds
         what the non-finite gradients gave (inf or NaN)."""
         if self._clip is None:
-            raise RuntimeError("FusedAdam.grad_norm is available after step() of an optimizer built with max_grad_norm=")
+            raise RuntimeError(f"{type(self).__name__}.grad_norm is available after step() of an optimizer built with max_grad_norm=")
         return self._clip[0]
 
     # -- descriptor tables ------------------------------------------------------------------------
-    def _ensure_state(self, p):
-        st = self.state[p]
-        if not st:
-            st["step"] = torch.tensor(0.0)
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        return st
-
-    @staticmethod
-    def _check_param(p):
+    @classmethod
+    def _check_param(cls, p):
         if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-            raise RuntimeError("FusedAdam needs contiguous fp32 parameters on a HIP device (no CPU fallback)")
+            raise RuntimeError(f"{cls.__name__} needs contiguous fp32 parameters on a HIP device (no CPU fallback)")
 
     def _upload(self, raw: bytearray, dev) -> torch.Tensor:
         return self._ring.upload(raw, dev)                # pinned ring guarded by events (_tables.PinnedRing)
 
+    def _state_keys(self, group):
+        """Names of the per-parameter state tensors behind the `exp_avg` / `exp_avg_sq` fields of the descriptor (at most two)."""
+        raise NotImplementedError
+
+    def _entry_state(self, p, group):
+        """The state dict of a parameter about to enter a table, created (and checked) as the update rule needs it."""
+        raise NotImplementedError
+
+    def _rehome(self, st, keys, views):
+        """Move the state tensors of one parameter into their views of the flat buffers of the bucket path."""
+        raise NotImplementedError
+
     def _dynamic_table(self, group):
+        keys = self._state_keys(group)
         entries, first, keep, live = [], 0, [], []
         for p in group["params"]:
             if p.grad is None:
                 continue
             self._check_param(p)
             g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-            st = self._ensure_state(p)
-            if self._scaler is None and int(st["step"].item()) != self._host_steps:
-                raise RuntimeError("FusedAdam: every parameter that receives gradients must do so from the first step "
-                                   "(one bias correction per launch)")
+            st = self._entry_state(p, group)
+            ptrs = [st[k].data_ptr() for k in keys] + [0] * (2 - len(keys))
             n = p.numel()
-            entries.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), n, first))
+            entries.append((p.data_ptr(), g.data_ptr(), ptrs[0], ptrs[1], n, first))
             keep.append(g)
             live.append(p)
             first += (n + _CHUNK - 1) // _CHUNK
@@ -249,28 +246,24 @@ class FusedAdam(torch.optim.Optimizer):
         if sync is None or not sync.ready or len(self.param_groups) != 1:
             return None
         if self._static is None or self._static[0] != sync.layout_version:
+            keys = self._state_keys(group)
             mine = {id(p) for p in group["params"]}
             entries, first, expect, flats = [], 0, [], []
             for flat, rows in sync.bucket_layout():
                 if not flat.is_cuda:
                     return None
-                m_flat, v_flat = torch.zeros_like(flat), torch.zeros_like(flat)
-                flats.append((m_flat, v_flat))
+                state_flats = tuple(torch.zeros_like(flat) for _ in keys)
+                flats.append(state_flats)
                 for p, off in rows:
                     if id(p) not in mine:
-                        raise RuntimeError("FusedAdam: a bucketed parameter is not in this optimizer")
+                        raise RuntimeError(f"{type(self).__name__}: a bucketed parameter is not in this optimizer")
                     self._check_param(p)
                     n = p.numel()
-                    m, v = m_flat[off:off + n].view_as(p), v_flat[off:off + n].view_as(p)
-                    st = self.state[p]
-                    if st:                                   # state from the discovery step(s): move it into the flat buffers
-                        m.copy_(st["exp_avg"])
-                        v.copy_(st["exp_avg_sq"])
-                    else:
-                        st["step"] = torch.tensor(0.0)
-                    st["exp_avg"], st["exp_avg_sq"] = m, v
+                    views = [f[off:off + n].view_as(p) for f in state_flats]
+                    self._rehome(self.state[p], keys, views)      # state from the discovery step(s) moves into the flat buffers
+                    ptrs = [v.data_ptr() for v in views] + [0] * (2 - len(keys))
                     gptr = flat.data_ptr() + 4 * off
-                    entries.append((p.data_ptr(), gptr, m.data_ptr(), v.data_ptr(), n, first))
+                    entries.append((p.data_ptr(), gptr, ptrs[0], ptrs[1], n, first))
                     expect.append((p, gptr))
                     first += (n + _CHUNK - 1) // _CHUNK
             raw = bytearray(b"".join(struct.pack("<QQQQqq", *e) for e in entries))
@@ -288,6 +281,135 @@ class FusedAdam(torch.optim.Optimizer):
             if p.grad is not None and id(p) not in bucketed:
                 return None
         return table, count, chunks, []
+
+    def _on_adopt(self, scaler: "LossScaler") -> None:
+        """A scaler drives this optimizer from now on: what the update rule needs to know at that moment."""
+
+    def _adopt(self, scaler: Optional[LossScaler]) -> None:
+        if scaler is not None and self._scaler is None:
+            self._on_adopt(scaler)
+            self._scaler = scaler
+        if self._scaler is not None and scaler is not self._scaler:
+            raise RuntimeError(f"{type(self).__name__}: this optimizer is driven by a LossScaler; step through scaler.step(optimizer)")
+
+    def _avg_args(self, table, count):
+        """(shadow-pointer array, averaging state, EMA weight) of a launch: the pointers sit behind the ``count`` descriptors."""
+        return table.data_ptr() + 48 * count, self._average._state_ptr(table.device), self._average._ema_weight
+
+    def _tables(self):
+        work = []
+        for group in self.param_groups:
+            built = self._static_table(group) or self._dynamic_table(group)
+            if built is not None:
+                work.append((group, built))
+        return work
+
+    def _unscale(self, scaler: LossScaler) -> None:
+        """``LossScaler.unscale_``: g *= 1/scale in place + the non-finite check, one launch per parameter group."""
+        self._adopt(scaler)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is not None and not p.grad.is_contiguous():
+                    raise RuntimeError("LossScaler.unscale_ rewrites the gradients in place and needs them contiguous")
+        lib = _lib.load()
+        for _, (table, count, chunks, keep) in self._tables():
+            with torch.cuda.device(table.device):
+                _lib.check(lib.zsv_grad_unscale_multi(table.data_ptr(), count, chunks, scaler.state_ptr, _stream()),
+                           "zsv_grad_unscale_multi")
+            table.record_stream(torch.cuda.current_stream())
+            del keep
+        _lib.note_raw_write()                      # gradients rewritten through raw pointers
+
+    def _norm_pass(self, lib, work, scaler: Optional[LossScaler], unscaled: bool):
+        """What comes before the update launches of a step: with ``max_grad_norm`` the norm pass per group (which is the scaler's
+        non-finite check as well) and the finalize, otherwise the check alone under a scaler whose gradients are still scaled in
+        memory -- every group before any is updated.  Returns the device address of the clip record, or None."""
+        state_ptr = scaler.state_ptr if scaler is not None else None
+        scaled_in_memory = scaler is not None and not unscaled
+        clip_ptr = None
+        if self.max_grad_norm is not None:
+            dev = work[0][1][0].device
+            total = sum(chunks for _, (_, _, chunks, _) in work)
+            nbytes = int(lib.zsv_grad_norm_workspace_bytes(total))
+            if self._clip is None or self._clip.device != dev:
+                self._clip = torch.zeros(2, dtype=torch.float32, device=dev)
+            if self._partials is None or self._partials.device != dev or self._partials.numel() * 4 < nbytes:
+                self._partials = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+            offset = 0
+            with torch.cuda.device(dev):
+                for _, (table, count, chunks, _keep) in work:
+                    # with a scaler this read of the gradients is the non-finite check as well (all groups before any update)
+                    _lib.check(lib.zsv_grad_norm_multi(table.data_ptr(), count, chunks, offset, self._partials.data_ptr(),
+                                                       self._partials.numel() * 4, state_ptr if scaled_in_memory else None,
+                                                       _stream()), "zsv_grad_norm_multi")
+                    offset += chunks
+                _lib.check(lib.zsv_grad_norm_finalize(self._partials.data_ptr(), total, self.max_grad_norm,
+                                                      state_ptr if scaled_in_memory else None, self._clip.data_ptr(),
+                                                      _stream()), "zsv_grad_norm_finalize")
+            clip_ptr = self._clip.data_ptr()
+        elif scaled_in_memory:
+            for _, (table, count, chunks, _keep) in work:
+                with torch.cuda.device(table.device):
+                    _lib.check(lib.zsv_grad_check_multi(table.data_ptr(), count, chunks, state_ptr, _stream()),
+                               "zsv_grad_check_multi")
+        return clip_ptr
+
+
+class FusedAdam(_FusedOptimizer):
+    """``torch.optim.Adam`` / ``torch.optim.AdamW`` in one launch per parameter group (module docstring).
+
+    ``weight_decay`` and ``decoupled_weight_decay`` are per parameter group, like ``lr``: ``decoupled_weight_decay=False``
+    is ``Adam(weight_decay=)`` (L2: ``g += wd * p``), ``True`` is ``AdamW`` (``p *= 1 - lr * wd``).  Parameters without a
+    gradient are skipped, decay included, as torch does; a step the ``LossScaler`` skips applies no decay either.
+
+    ``max_grad_norm`` belongs to the optimizer and spans all groups: the gradients are scaled by
+    ``min(1, max_grad_norm / (total_norm + 1e-6))`` -- ``clip_grad_norm_`` with ``norm_type=2`` over all parameters -- on
+    their way into the update.  ``.grad`` itself is not rewritten (torch's ``clip_grad_norm_`` rewrites it).  With
+    ``grad_buckets=`` the norm is that of the averaged gradients, identical on every rank."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False,
+                 max_grad_norm=None, grad_buckets=None):
+        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1):
+            raise ValueError("invalid Adam hyper-parameters")
+        self._check_decay(weight_decay)
+        max_grad_norm = self._check_max_grad_norm(max_grad_norm)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      decoupled_weight_decay=bool(decoupled_weight_decay)))
+        for group in self.param_groups:
+            self._check_decay(group["weight_decay"])
+            if not (math.isfinite(group["lr"]) and group["lr"] >= 0):
+                raise ValueError(f"invalid learning rate {group['lr']}")
+        self._init_fused(max_grad_norm, grad_buckets)
+        self._host_steps = 0                              # steps taken without a scaler
+        self._resumed = False                             # state came from load_state_dict (a scaler may then join late)
+
+    # -- descriptor tables ------------------------------------------------------------------------
+    def _ensure_state(self, p):
+        st = self.state[p]
+        if not st:
+            st["step"] = torch.tensor(0.0)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
+    def _state_keys(self, group):
+        return ("exp_avg", "exp_avg_sq")
+
+    def _entry_state(self, p, group):
+        st = self._ensure_state(p)
+        if self._scaler is None and int(st["step"].item()) != self._host_steps:
+            raise RuntimeError("FusedAdam: every parameter that receives gradients must do so from the first step "
+                               "(one bias correction per launch)")
+        return st
+
+    def _rehome(self, st, keys, views):
+        if st:                                   # state from the discovery step(s): move it into the flat buffers
+            for k, v in zip(keys, views):
+                v.copy_(st[k])
+        else:
+            st["step"] = torch.tensor(0.0)
+        for k, v in zip(keys, views):
+            st[k] = v
 
     # -- step -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -348,82 +470,24 @@ class FusedAdam(torch.optim.Optimizer):
             _lib.note_raw_write()                  # parameters updated through raw pointers
         return loss
 
-    def _adopt(self, scaler: Optional[LossScaler]) -> None:
-        if scaler is not None and self._scaler is None:
-            if self._host_steps:
-                if not self._resumed:
-                    raise RuntimeError("FusedAdam: a LossScaler must drive the optimizer from its first step "
-                                       "(the count of steps taken lives in the scaler's device state)")
-                # resumed from a checkpoint (load_state_dict): the scaler takes over the loaded step count unless its own
-                # loaded state already carries one
-                if scaler.state()["steps_done"] == 0:
-                    scaler._seed_steps_done(self._host_steps)
-                elif scaler.state()["steps_done"] != self._host_steps:
-                    raise RuntimeError("FusedAdam: the loaded optimizer and scaler states disagree on the steps taken")
-            self._scaler = scaler
-        if self._scaler is not None and scaler is not self._scaler:
-            raise RuntimeError("FusedAdam: this optimizer is driven by a LossScaler; step through scaler.step(optimizer)")
-
-    def _avg_args(self, table, count):
-        """(shadow-pointer array, averaging state, EMA weight) of a launch: the pointers sit behind the ``count`` descriptors."""
-        return table.data_ptr() + 48 * count, self._average._state_ptr(table.device), self._average._ema_weight
-
-    def _tables(self):
-        work = []
-        for group in self.param_groups:
-            built = self._static_table(group) or self._dynamic_table(group)
-            if built is not None:
-                work.append((group, built))
-        return work
-
-    def _unscale(self, scaler: LossScaler) -> None:
-        """``LossScaler.unscale_``: g *= 1/scale in place + the non-finite check, one launch per parameter group."""
-        self._adopt(scaler)
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.grad is not None and not p.grad.is_contiguous():
-                    raise RuntimeError("LossScaler.unscale_ rewrites the gradients in place and needs them contiguous")
-        lib = _lib.load()
-        for _, (table, count, chunks, keep) in self._tables():
-            with torch.cuda.device(table.device):
-                _lib.check(lib.zsv_grad_unscale_multi(table.data_ptr(), count, chunks, scaler.state_ptr, _stream()),
-                           "zsv_grad_unscale_multi")
-            table.record_stream(torch.cuda.current_stream())
-            del keep
-        _lib.note_raw_write()                      # gradients rewritten through raw pointers
+    def _on_adopt(self, scaler: LossScaler) -> None:
+        if self._host_steps:
+            if not self._resumed:
+                raise RuntimeError("FusedAdam: a LossScaler must drive the optimizer from its first step "
+                                   "(the count of steps taken lives in the scaler's device state)")
+            # resumed from a checkpoint (load_state_dict): the scaler takes over the loaded step count unless its own
+            # loaded state already carries one
+            if scaler.state()["steps_done"] == 0:
+                scaler._seed_steps_done(self._host_steps)
+            elif scaler.state()["steps_done"] != self._host_steps:
+                raise RuntimeError("FusedAdam: the loaded optimizer and scaler states disagree on the steps taken")
 
     def _step_decay_clip(self, lib, work, scaler: Optional[LossScaler], unscaled: bool) -> bool:
         """The step with weight decay and / or clipping: [norm pass per group, finalize,] one update launch per group."""
         if not work:
             return False
         state_ptr = scaler.state_ptr if scaler is not None else None
-        scaled_in_memory = scaler is not None and not unscaled
-        clip_ptr = None
-        if self.max_grad_norm is not None:
-            dev = work[0][1][0].device
-            total = sum(chunks for _, (_, _, chunks, _) in work)
-            nbytes = int(lib.zsv_grad_norm_workspace_bytes(total))
-            if self._clip is None or self._clip.device != dev:
-                self._clip = torch.zeros(2, dtype=torch.float32, device=dev)
-            if self._partials is None or self._partials.device != dev or self._partials.numel() * 4 < nbytes:
-                self._partials = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
-            offset = 0
-            with torch.cuda.device(dev):
-                for _, (table, count, chunks, _keep) in work:
-                    # with a scaler this read of the gradients is the non-finite check as well (all groups before any update)
-                    _lib.check(lib.zsv_grad_norm_multi(table.data_ptr(), count, chunks, offset, self._partials.data_ptr(),
-                                                       self._partials.numel() * 4, state_ptr if scaled_in_memory else None,
-                                                       _stream()), "zsv_grad_norm_multi")
-                    offset += chunks
-                _lib.check(lib.zsv_grad_norm_finalize(self._partials.data_ptr(), total, self.max_grad_norm,
-                                                      state_ptr if scaled_in_memory else None, self._clip.data_ptr(),
-                                                      _stream()), "zsv_grad_norm_finalize")
-            clip_ptr = self._clip.data_ptr()
-        elif scaled_in_memory:
-            for _, (table, count, chunks, _keep) in work:
-                with torch.cuda.device(table.device):
-                    _lib.check(lib.zsv_grad_check_multi(table.data_ptr(), count, chunks, state_ptr, _stream()),
-                               "zsv_grad_check_multi")
+        clip_ptr = self._norm_pass(lib, work, scaler, unscaled)
         for group, (table, count, chunks, keep) in work:
             lr, (b1, b2), eps = float(group["lr"]), group["betas"], float(group["eps"])
             wd, decoupled = float(group["weight_decay"]), int(bool(group["decoupled_weight_decay"]))
@@ -476,6 +540,153 @@ class FusedAdam(torch.optim.Optimizer):
         return super().state_dict()
 
 
+class FusedSGD(_FusedOptimizer):
+    """``torch.optim.SGD`` -- momentum, dampening, Nesterov, L2 weight decay, ``maximize`` -- in one ``zsv_sgd_multi`` launch per
+    parameter group (csrc/sgd.hip), with everything ``FusedAdam`` carries: ``max_grad_norm``, ``grad_buckets=``, ``LossScaler`` and
+    ``WeightAverage``.  Every option is per parameter group except ``max_grad_norm`` and ``grad_buckets``.
+
+    The state is torch's: ``state[p]["momentum_buffer"]`` (none with ``momentum == 0``), so ``state_dict()`` /
+    ``load_state_dict()`` interchange with ``torch.optim.SGD``.  torch creates the buffer on the first step as a copy of the
+    gradient; here it is allocated as zeros and the launch is told whether it is the first one, which matters only with
+    ``dampening != 0`` (``momentum * 0 + g`` is ``g``).  Without a scaler the host knows; under a ``LossScaler`` the device
+    decides from the scaler's count of steps taken, so a first step that is skipped leaves the next one the first.  One flag per
+    launch: a parameter that first receives a gradient after the first step is fine with ``dampening == 0`` and raises
+    otherwise."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
+                 max_grad_norm=None, grad_buckets=None):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        max_grad_norm = self._check_max_grad_norm(max_grad_norm)
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                      nesterov=bool(nesterov), maximize=bool(maximize)))
+        for group in self.param_groups:
+            self._check_group(group)
+        self._init_fused(max_grad_norm, grad_buckets)
+        self._started = False                             # an update has been launched, or buffers were loaded: no host-side "first"
+        self._first_at = -1                               # under a scaler: the launch is the first iff steps_done == this (-1: never)
+
+    @staticmethod
+    def _check_group(group):
+        lr, momentum, dampening, wd = group["lr"], group["momentum"], group["dampening"], group["weight_decay"]
+        if not (math.isfinite(lr) and lr >= 0):
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not (math.isfinite(momentum) and momentum >= 0):
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if not (math.isfinite(wd) and wd >= 0):
+            raise ValueError(f"Invalid weight_decay value: {wd}")
+        if not math.isfinite(dampening):
+            raise ValueError(f"Invalid dampening value: {dampening}")
+        if group["nesterov"] and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+
+    @staticmethod
+    def _needs_first(group) -> bool:
+        return group["momentum"] != 0 and group["dampening"] != 0
+
+    # -- descriptor tables ------------------------------------------------------------------------
+    def _state_keys(self, group):
+        return ("momentum_buffer",) if group["momentum"] != 0 else ()
+
+    def _entry_state(self, p, group):
+        st = self.state[p]
+        if group["momentum"] != 0 and st.get("momentum_buffer") is None:
+            if self._started and self._needs_first(group):
+                raise RuntimeError("FusedSGD: with dampening != 0 every parameter that receives gradients must do so from the first "
+                                   "step (one 'the momentum buffer does not exist yet' flag per launch)")
+            st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
+    def _rehome(self, st, keys, views):
+        for k, v in zip(keys, views):
+            if st.get(k) is not None:            # a buffer from the discovery step(s) or a checkpoint: move it into the flat one
+                v.copy_(st[k])
+            elif self._started and self._needs_first(self.param_groups[0]):
+                raise RuntimeError("FusedSGD: with dampening != 0 every parameter that receives gradients must do so from the first "
+                                   "step (one 'the momentum buffer does not exist yet' flag per launch)")
+            st[k] = v
+
+    def _on_adopt(self, scaler: LossScaler) -> None:
+        # the device decides "first" from the scaler's count of steps taken: remember what it reads now, while no buffer exists
+        # (one sync, and only for an update rule that can tell a first step from a zero buffer)
+        if not self._started and any(self._needs_first(g) for g in self.param_groups):
+            self._first_at = scaler.state()["steps_done"]
+        else:
+            self._first_at = -1
+
+    # -- step -------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None, scaler: Optional[LossScaler] = None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._adopt(scaler)
+        lib = _lib.load()
+        avg = self._average
+        if avg is not None:
+            avg._check_live()
+        for group in self.param_groups:
+            self._check_group(group)
+        work = self._tables()
+        if not work:
+            return loss
+        unscaled = scaler is not None and id(self) in scaler._unscaled      # LossScaler.unscale_ has run on these gradients
+        state_ptr = scaler.state_ptr if scaler is not None else None
+        # GradScaler.step checks EVERY gradient before the optimizer touches anything: the norm pass or the check, all groups first
+        clip_ptr = self._norm_pass(lib, work, scaler, unscaled)
+        if scaler is not None:
+            first_step = self._first_at
+        else:
+            first_step = -1 if self._started else 0
+        for group, (table, count, chunks, keep) in work:
+            shadows, avg_state, ema_weight = self._avg_args(table, count) if avg is not None else (None, None, 0.0)
+            with torch.cuda.device(table.device):
+                _lib.check(lib.zsv_sgd_multi(table.data_ptr(), count, chunks, float(group["lr"]), float(group["momentum"]),
+                                             float(group["dampening"]), int(bool(group["nesterov"])), float(group["weight_decay"]),
+                                             int(bool(group["maximize"])), clip_ptr, state_ptr, int(unscaled), first_step,
+                                             shadows, avg_state, ema_weight, _stream()), "zsv_sgd_multi")
+            # keep the uploaded table and any contiguous gradient copies alive until the stream is past the launch
+            table.record_stream(torch.cuda.current_stream())
+            del keep
+        del work
+        if avg is not None:
+            avg._after_update(lib, scaler)         # BatchNorm statistics, then n_averaged += !found_inf (before scaler.update())
+        self._started = True
+        _lib.note_raw_write()                      # parameters updated through raw pointers
+        return loss
+
+    # -- state ------------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:            # torch.optim.SGD's groups carry more keys (foreach, fused, ...): they are kept
+            group.setdefault("nesterov", False)
+            group.setdefault("maximize", False)
+            self._check_group(group)
+        for st in self.state.values():
+            if st.get("momentum_buffer", 0) is None:       # torch stores None with momentum == 0
+                del st["momentum_buffer"]
+        # a loaded state that has buffers is past its first step
+        self._started = any(st.get("momentum_buffer") is not None for st in self.state.values())
+        self._first_at = -1
+        self._scaler = None
+        self._static = None                        # the buffers are re-homed into the flat ones on the next step
+
+    def state_dict(self):
+        """torch.optim.SGD's layout.  Under a ``LossScaler`` whether the first step has been taken is device state: fetched here
+        (one sync) when it matters, and buffers that no taken step has written are left out, as torch has none then."""
+        out = super().state_dict()
+        if self._scaler is not None and self._first_at >= 0 and self._scaler.state()["steps_done"] == self._first_at:
+            out["state"] = {k: {n: v for n, v in st.items() if n != "momentum_buffer"} for k, st in out["state"].items()}
+        return out
+
+
 class WeightAverage:
     """A running average of the weights for evaluation, kept by the optimizer's own launches.
 
@@ -497,13 +708,13 @@ class WeightAverage:
     same update to equal parameters, so the shadows are equal without a collective."""
 
     def __init__(self, optimizer, decay: Optional[float] = 0.999, model: Optional[torch.nn.Module] = None, buffers: bool = True):
-        if not isinstance(optimizer, FusedAdam):
+        if not isinstance(optimizer, _FusedOptimizer):
             raise TypeError("WeightAverage averages inside optim.FusedAdam's update launch; got " + type(optimizer).__name__)
         if decay is not None:
             if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not (0.0 <= decay < 1.0):
                 raise ValueError(f"decay must be None (equal-weight) or a number in [0, 1), not {decay!r}")
         if optimizer._average is not None:
-            raise RuntimeError("this FusedAdam already has a WeightAverage (one per optimizer)")
+            raise RuntimeError(f"this {type(optimizer).__name__} already has a WeightAverage (one per optimizer)")
         self._set_decay(decay)
         self._applied = False
         own = getattr(model, "module", model) if model is not None else None
@@ -517,7 +728,7 @@ class WeightAverage:
         else:
             keys = list(range(len(params)))
         for p in params:
-            FusedAdam._check_param(p)
+            optimizer._check_param(p)
         live = list(zip(keys, params))
         self._n_params = len(live)
         if own is not None and buffers:
