@@ -66,7 +66,7 @@ def _workspace(nbytes: int, device) -> Optional[torch.Tensor]:
 # (ZSV_WGRAD_STREAM=0 keeps it on the backward stream): the matrix-bound wgrad kernels then share the chip with the HBM-bound
 # BatchNorm / pooling passes of the layers below instead of queueing in front of them (step 50.1 -> 47.7 ms on one device,
 # profiles/r02_wgrad_side_stream_ab.txt; gradients are bit-identical, the kernels are the same).  The autograd engine runs a callback at the end of the backward pass that makes
-# the calling stream wait for the side stream, so `.grad` is safe to read right after `loss.backward()`.
+# the stream the backward nodes ran on (the forward's) AND the stream `backward()` was called from wait for the side stream, so `.grad` is safe to read right after `loss.backward()` on either.
 _WGRAD_SIDE = {}
 _WGRAD_JOIN_QUEUED = {}
 _WGRAD_SEEN = {}          # device index -> (graph task id, ids of the parameters that already produced a dw in that pass)
@@ -170,7 +170,8 @@ class deferred_wgrad_join:
 
 def _queue_wgrad_join(device) -> bool:
     """Once per backward pass (autograd graph task) and device: a callback that runs when the pass ends and makes the
-    stream the pass was launched on wait for the weight-gradient stream.  Keyed by the graph task id, so a pass that died
+    stream the backward nodes run on (the one the forward ran on) and, when it is another one, the stream ``backward()`` was
+    called from wait for the weight-gradient stream.  Keyed by the graph task id, so a pass that died
     with an exception cannot leave a stale "already queued" mark behind.  False: this torch has no such hook (the caller
     joins at once instead)."""
     if _current_graph_task_id is None or _queue_engine_callback is None:
@@ -184,7 +185,19 @@ def _queue_wgrad_join(device) -> bool:
     _WGRAD_JOIN_QUEUED[key] = task
     main = torch.cuda.current_stream(device)
     side = _WGRAD_SIDE[key]
-    _queue_engine_callback(lambda: main.wait_stream(side))
+
+    def join():
+        main.wait_stream(side)
+        # `main` is the stream the backward nodes run on, i.e. the one the FORWARD ran on.  `backward()` may have been called
+        # from another one (forward under `with torch.cuda.stream(s):`, backward outside it, or the other way round), and that
+        # is where `.grad` is read next.  The engine has synchronised the caller's stream with the leaf streams BEFORE the
+        # final callbacks, so a wait queued on `main` here no longer reaches it; the callbacks run with the caller's streams
+        # current, so this is that stream.
+        caller = torch.cuda.current_stream(device)
+        if caller != main:
+            caller.wait_stream(side)
+
+    _queue_engine_callback(join)
     return True
 
 
