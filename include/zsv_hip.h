@@ -249,6 +249,27 @@ int zsv_cosine_topk(const float* embed, const float* class_embed, int32_t rows, 
                     int32_t k, int32_t* out_index, double* out_dist, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* evaluate()'s scoring in one device pass: top-1 / top-5 over the whole class table (main.py:264-266 ->
+ * compute_accuracy, main.py:316-325) and over the ten np.random.seed(split) half-class splits (main.py:281-304),
+ * without gathering a sub-table.  pred, true_embed (rows, dim) and class_embed (n_classes, dim) fp32; labels (rows)
+ * int64 (may be NULL when n_tables == 1).  split_pos (n_tables, n_classes) int32 describes the class tables:
+ * split_pos[t][c] = the row of class c in class_embedding[sel_classes] (main.py:286-288; permutation order, not
+ * sorted), -1 when c is not in table t; table 0 is the whole table (split_pos[0][c] = c).  Table 0 scores every row and
+ * does not look at the labels; table t >= 1 scores the rows with 0 <= label < n_classes and split_pos[t][label] >= 0
+ * (`l in sel_classes`, main.py:287).  Both embeddings are measured against the full table once with the double-precision
+ * distances of zsv_cosine_topk (same kernel, same bits; a NaN distance ranks last).  Inside a table classes are ordered by
+ * (distance, split_pos[t][c]) -- the stable argsort of the gathered sub-table; y = the first class of the true row
+ * (argmin), rank = the number of classes of the table before y in the pred row; top-1 hit: rank == 0, top-5 hit: rank < 5.
+ * counts (n_tables, 3) int32 = rows scored, top-1 hits, top-5 hits per table; class_counts (n_classes, 3) int32, may be
+ * NULL: the same three numbers of table 0 per true class y (main.py:322, not the label).  Both are zeroed by the call, on
+ * the stream.  workspace = the two (rows, n_classes rounded up to 16) double distance matrices.  ZSV_E_NULL,
+ * ZSV_E_BAD_SHAPE for rows / dim / n_classes / n_tables <= 0, ZSV_E_TOO_LARGE at zsv_cosine_topk's bounds or for more
+ * than 2048 tables, ZSV_E_WORKSPACE; all before any launch. */
+size_t zsv_split_accuracy_workspace_bytes(int32_t rows, int32_t n_classes);
+int zsv_split_accuracy(const float* pred, const float* true_embed, const int64_t* labels, const float* class_embed,
+                       int32_t rows, int32_t dim, int32_t n_classes, const int32_t* split_pos, int32_t n_tables,
+                       int32_t* counts, int32_t* class_counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser ------------------------------------------------------------------ */
 /* One torch.optim.Adam step (main.py:131; betas (0.9, 0.999), eps 1e-8, no weight decay,
  * no amsgrad) over a flat fp32 buffer: p, g, exp_avg, exp_avg_sq of n elements.

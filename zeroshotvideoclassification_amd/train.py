@@ -10,7 +10,8 @@ does not stall the queue.
 
 ``evaluate`` / ``compute_accuracy`` restate main.py:224-325: eval-mode forward under
 ``no_grad``, cosine nearest class in the 300-d embedding space, top-1 / top-5, and the ten
-seeded half-class splits.
+seeded half-class splits.  The scoring is one device pass (``score_splits`` -> ``zsv_split_accuracy``)
+and one device -> host copy of its integers.
 
 ``load_weights`` / ``save_checkpoint`` keep the reference's checkpoint format (main.py:114-124,
 361-365): ``{'state_dict' ('module.'-prefixed keys), 'opt', 'accuracy'}``, loaded by key
@@ -243,17 +244,89 @@ def train_accuracy(y: torch.Tensor, class_embed: torch.Tensor, labels: torch.Ten
     return (pred == labels.to(pred.device).reshape(-1)).float().mean() * 100.0
 
 
+_split_table_cache: dict = {}      # (n_classes, splits, device) -> (host table, its device copy)
+
+
+def split_tables(n_classes: int, splits: int) -> np.ndarray:
+    """The class tables ``evaluate`` scores, as ``(splits + 1, n_classes)`` int32 positions for ``zsv_split_accuracy``: row 0 is
+    the whole table (``pos[0][c] = c``); row ``s + 1`` is split ``s`` of main.py:281-288 -- ``np.random.seed(s)``, ``chosen =
+    np.random.permutation(C)[:C // 2]`` -- with ``pos[s + 1][chosen[j]] = j`` (the class's row in
+    ``class_embedding[sel_classes]``: permutation order, not sorted) and -1 everywhere else.  The draws are made on numpy's
+    GLOBAL generator on every call, like the reference does: it leaves that generator seeded and later draws
+    (``camera_motion_trajectory``) come from it, so the host table is never cached."""
+    n_classes, splits = int(n_classes), int(splits)
+    pos = np.full((splits + 1, n_classes), -1, dtype=np.int32)
+    pos[0] = np.arange(n_classes, dtype=np.int32)
+    for split in range(splits):
+        np.random.seed(split)                                             # main.py:284
+        chosen = np.random.permutation(n_classes)[:n_classes // 2]
+        pos[split + 1][chosen] = np.arange(len(chosen), dtype=np.int32)
+    return pos
+
+
+def _device_split_tables(n_classes: int, splits: int, device: torch.device) -> torch.Tensor:
+    pos = split_tables(n_classes, splits)                                 # replayed every call; only the upload is cached
+    key = (int(n_classes), int(splits), str(device))
+    hit = _split_table_cache.get(key)
+    if hit is None or not np.array_equal(hit[0], pos):
+        hit = (pos, torch.from_numpy(pos).to(device))
+        _split_table_cache[key] = hit
+    return hit[1]
+
+
+def _score_splits(pred, true, labels, class_embed, splits, per_class) -> Tuple[torch.Tensor, int]:
+    """One int32 device buffer ``(splits + 1 [+ C], 3)``: ``counts`` and, below it, ``class_counts``; and the number of tables."""
+    tensors = [pred, true, class_embed] + ([labels] if labels is not None else [])
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError("score_splits runs on an MI355X HIP device only (no CPU fallback)")
+    assert len(pred) == len(true), "True and predicted labels must have the same number of samples"
+    c = class_embed.detach().float().contiguous()
+    if c.dim() != 2:
+        raise RuntimeError(f"score_splits: class table {tuple(c.shape)}")
+    n_classes, dim = int(c.shape[0]), int(c.shape[1])
+    p = pred.detach().float().reshape(len(pred), dim).contiguous()
+    t = true.detach().float().reshape(len(true), dim).contiguous()
+    rows, tables = int(p.shape[0]), int(splits) + 1
+    if tables > 1:
+        if labels is None or labels.numel() != rows:
+            raise RuntimeError("score_splits: the class splits need one label per row")
+        labels = labels.detach().reshape(-1).long().contiguous()
+    pos = _device_split_tables(n_classes, int(splits), p.device)
+    if rows == 0 or n_classes == 0:
+        return torch.zeros((tables + (n_classes if per_class else 0), 3), dtype=torch.int32, device=p.device), tables
+    out = torch.empty((tables + (n_classes if per_class else 0), 3), dtype=torch.int32, device=p.device)
+    lib = _lib.load()
+    nbytes = lib.zsv_split_accuracy_workspace_bytes(rows, n_classes)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=p.device)
+    with torch.cuda.device(p.device):
+        _lib.check(lib.zsv_split_accuracy(p.data_ptr(), t.data_ptr(), labels.data_ptr() if tables > 1 else None, c.data_ptr(),
+                                          rows, dim, n_classes, pos.data_ptr(), tables, out.data_ptr(),
+                                          out[tables:].data_ptr() if per_class else None, ws.data_ptr(), nbytes,
+                                          c_void_p(torch.cuda.current_stream().cuda_stream)), "zsv_split_accuracy")
+    return out, tables
+
+
+def score_splits(pred: torch.Tensor, true: torch.Tensor, labels: Optional[torch.Tensor], class_embed: torch.Tensor,
+                 splits: int = 10, per_class: bool = False):
+    """The integers behind ``evaluate``'s accuracies, left on the device (``zsv_split_accuracy``, csrc/nearest_class.hip; no host
+    synchronisation): ``counts (splits + 1, 3)`` int32 = rows scored, top-1 hits, top-5 hits over the whole class table (row 0,
+    main.py:264-266) and over each ``np.random.seed(split)`` half-class split (row ``split + 1``, main.py:281-304; the tables are
+    ``split_tables(C, splits)``).  Inside a split ties are ordered as the stable argsort of the gathered sub-table orders them:
+    by the class's position in ``sel_classes``.  ``per_class=True`` also returns ``class_counts (C, 3)``: the same three numbers of
+    the whole table per true class (main.py:322: the class nearest to the true embedding, not the label).  ``labels`` may be None
+    when ``splits == 0``.  HIP tensors only; no rows: zeros, without a launch."""
+    out, tables = _score_splits(pred, true, labels, class_embed, splits, per_class)
+    return (out[:tables], out[tables:]) if per_class else out
+
+
 def compute_accuracy(predicted_embed: torch.Tensor, class_embed: torch.Tensor,
                      true_embed: torch.Tensor) -> Tuple[float, float]:
-    """Top-1 / top-5 accuracy (percent) to the closest class embedding (main.py:316-325)."""
+    """Top-1 / top-5 accuracy (percent) to the closest class embedding (main.py:316-325): one ``score_splits`` and one read."""
     assert len(predicted_embed) == len(true_embed), "True and predicted labels must have the same number of samples"
-    order = nearest_classes(predicted_embed, class_embed, 5)
-    y = nearest_classes(true_embed, class_embed, 1)[:, 0]
-    n = max(len(y), 1)
+    rows, hit1, hit5 = score_splits(predicted_embed, true_embed, None, class_embed, splits=0)[0].tolist()
+    n = max(rows, 1)
     # counts are exact integers; the reference's np.mean of booleans is the same count / n in double
-    top1 = float((order[:, 0] == y).sum().item()) / n * 100
-    top5 = float((order == y[:, None]).any(dim=1).sum().item()) / n * 100
-    return top1, top5
+    return float(hit1) / n * 100, float(hit5) / n * 100
 
 
 def _gather_rows(t: torch.Tensor, group) -> torch.Tensor:
@@ -276,7 +349,7 @@ def _gather_rows(t: torch.Tensor, group) -> torch.Tensor:
 def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], class_embed: torch.Tensor,
              device: Optional[torch.device] = None, splits: int = 10, dtype: Optional[torch.dtype] = None,
              group=None, sharded: Optional[bool] = None, local_batches: bool = False,
-             sync_state: bool = True, average=None) -> dict:
+             sync_state: bool = True, average=None, per_class: bool = False) -> dict:
     """main.py:224-313 for one test set.  ``batches`` yields ``(X, labels, Z, ...)``; samples with
     label -1 (failed loads, auxiliary_dataset.py:502-505) are dropped like main.py:246-248.
     ``dtype=torch.bfloat16`` runs the forward on the bf16 engine (``inference.Bf16Engine``, the
@@ -299,11 +372,16 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], 
     replicas are identical (e.g. right after ``load_weights`` on every rank).
 
     ``average`` (``optim.WeightAverage``): the evaluation runs on the averaged weights, swapped into the live tensors for
-    its duration (``with average.applied():``)."""
+    its duration (``with average.applied():``).
+
+    The scoring is one ``score_splits`` call and one device -> host copy of its integers; the percentages and the mean / std
+    over the splits are formed from them on the host.  ``per_class=True`` adds ``"class_counts"`` (``(C, 3)`` int64: rows,
+    top-1 hits, top-5 hits per true class over the whole table) and ``"mean_class_accuracy"`` (the mean of the per-class top-1
+    over the classes that have rows); the other keys do not change."""
     if average is not None:
         with average.applied():
             return evaluate(model, batches, class_embed, device=device, splits=splits, dtype=dtype, group=group, sharded=sharded,
-                            local_batches=local_batches, sync_state=sync_state)
+                            local_batches=local_batches, sync_state=sync_state, per_class=per_class)
     import torch.distributed as dist
     if sharded is None:
         sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
@@ -346,21 +424,24 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], 
     label_dev = torch.cat(labels).to(device).long() if labels else torch.zeros((0,), dtype=torch.int64, device=device)
     if sharded:
         pred, true, label_dev = (_gather_rows(t, group) for t in (pred, true, label_dev))
-    label = label_dev.cpu().numpy()
-    acc, acc5 = compute_accuracy(pred, class_embed, true)
-    out = {"accuracy": acc, "accuracy_top5": acc5, "n": int(len(pred))}
+    if not splits and not per_class:                      # the whole table alone: compute_accuracy is that one call and one read
+        acc, acc5 = compute_accuracy(pred, class_embed, true)
+        return {"accuracy": acc, "accuracy_top5": acc5, "n": int(len(pred))}
+    # the whole table and every split in one launch chain, then ONE device -> host copy of the integers
+    buf, tables = _score_splits(pred, true, label_dev, class_embed, int(splits), per_class)
+    host = buf.cpu().numpy()
+    n = max(int(len(pred)), 1)
+    out = {"accuracy": float(host[0, 1]) / n * 100, "accuracy_top5": float(host[0, 2]) / n * 100, "n": int(len(pred))}
     if splits:
-        a1, a5 = [], []
-        for split in range(splits):
-            np.random.seed(split)                                     # main.py:284
-            sel_classes = np.random.permutation(len(class_embed))[:len(class_embed) // 2]
-            sel = torch.from_numpy(np.isin(label, sel_classes)).to(device)
-            if sel.sum() == 0:
-                continue
-            s1, s5 = compute_accuracy(pred[sel], class_embed[torch.from_numpy(sel_classes).to(device)], true[sel])
-            a1.append(s1)
-            a5.append(s5)
+        scored = [row for row in host[1:tables] if row[0]]                   # a split none of whose classes occurs is left out
+        a1 = [float(row[1]) / int(row[0]) * 100 for row in scored]
+        a5 = [float(row[2]) / int(row[0]) * 100 for row in scored]
         if a1:
             out.update(split_accuracy=float(np.mean(a1)), split_accuracy_std=float(np.std(a1)),
                        split_accuracy_top5=float(np.mean(a5)), split_accuracy_top5_std=float(np.std(a5)))
+    if per_class:
+        per = host[tables:].astype(np.int64)
+        seen = per[:, 0] > 0
+        out["class_counts"] = per
+        out["mean_class_accuracy"] = float(np.mean(per[seen, 1] / per[seen, 0] * 100)) if seen.any() else 0.0
     return out
