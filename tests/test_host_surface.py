@@ -244,3 +244,96 @@ def test_environment_switches_are_snapshotted_and_reloaded():
     csrc = os.path.join(ROOT, "zeroshotvideoclassification_amd", "csrc")
     src = "".join(open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith(".hip") and f != "knobs.hip")
     assert "getenv(" not in src                         # the launch path never walks the environment
+
+
+_WATCH_ENV_CHILD = r"""
+import json, os, sys
+from ctypes import byref
+from zeroshotvideoclassification_amd import _lib, ops
+os.environ.pop("ZSV_NO_WINO", None)
+d = ops.conv_desc((2, 64, 8, 56, 56), (144, 64, 1, 3, 3), 1, (0, 1, 1))
+size = lambda: int(_lib.load().zsv_conv3d_fwd_workspace_bytes(byref(d)))
+_lib.load()                                              # installs the hook
+out ={"first": (_lib.knob_generation(), size())}
+os.environ["ZSV_NO_WINO"] = "1"
+_lib.load()                                              # the first call after the write: must return
+out["second"] = (_lib.knob_generation(), size())
+_lib.load()
+out["third"] = (_lib.knob_generation(), size())
+del os.environ["ZSV_NO_WINO"]
+_lib.load()
+out["restored"] = (_lib.knob_generation(), size())
+print(json.dumps(out))
+"""
+
+
+def test_watched_environment_reloads_once_per_write_without_recursing():
+    """ZSV_WATCH_ENV=1: an audit hook marks every ZSV_* write and the next load() re-reads the switches.  load() and reload_knobs()
+    call each other there; the flag has to be down before the inner call, or the first op after a write never returns
+    (RecursionError).  An audit hook cannot be removed, so this runs in a child process: one reload per write, none without."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ, ZSV_WATCH_ENV="1")
+    env.pop("ZSV_NO_WINO", None)
+    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
+    r = subprocess.run([sys.executable, "-c", _WATCH_ENV_CHILD], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    (g0, base), (g1, direct), (g2, again), (g3, back) = out["first"], out["second"], out["third"], out["restored"]
+    assert g1 == g0 + 1 and direct != base               # exactly one reload, and the library really re-read the switch
+    assert (g2, again) == (g1, direct)                   # nothing written since: nothing advances
+    assert g3 == g1 + 1 and back == base
+
+
+def test_cached_bf16_path_follows_replaced_parameters_and_modules():
+    """amp.train_path_for / amp._graph_state on a CPU model (building a path launches nothing): the cached path survives what leaves
+    its modules and Parameters in place, is rebuilt when a Parameter or module object is replaced, and the tuple a captured trunk
+    is checked against before a replay sees every moved tensor and changed BatchNorm hyper-parameter.  (The steps themselves:
+    tests/test_amp_stale_gpu.py.)"""
+    from zeroshotvideoclassification_amd import amp
+    model = network.get_network(make_opt("r2plus1d_18"))
+    trunk = model.model
+    path = amp.train_path_for(trunk)
+    assert amp.train_path_for(trunk) is path
+    state = amp._graph_state(path)
+    assert len(state) == len(path.params) + 5 * len(path.units)
+
+    def moved(change, undo=None):
+        nonlocal state
+        change()
+        now = amp._graph_state(path)
+        assert now != state and amp.train_path_for(trunk) is path          # same objects: the path stays, a capture would not
+        if undo is not None:
+            undo()
+            assert amp._graph_state(path) == state
+        else:
+            state = now
+    bn = trunk.layer3[0].conv1[1]
+    moved(lambda: setattr(bn, "momentum", 0.5), lambda: setattr(bn, "momentum", 0.1))
+    moved(lambda: setattr(bn, "eps", 1e-3), lambda: setattr(bn, "eps", 1e-5))
+    w = trunk.layer1[0].conv1[0][0].weight
+    moved(lambda: setattr(w, "data", w.data.clone()))
+    for name in ("running_mean", "running_var", "num_batches_tracked"):
+        moved(lambda: setattr(bn, name, getattr(bn, name).clone()))
+    model.float()                                                           # (no new tensors: nothing to re-capture for)
+    assert amp._graph_state(path) == state
+
+    model.load_state_dict({k: v.clone() for k, v in model.state_dict().items()}, assign=True)
+    fresh = amp.train_path_for(trunk)
+    assert fresh is not path and amp.train_path_for(trunk) is fresh
+    held = {id(p) for p in trunk.parameters()}
+    assert all(id(p) in held for p in fresh.params) and not any(id(p) in held for p in path.params)
+    seq = trunk.layer1[1].conv1[0]
+    seq[1] = layers.BatchNorm3d(seq[1].num_features)
+    newer = amp.train_path_for(trunk)
+    assert newer is not fresh and any(u.bn is seq[1] for u in newer.units)
+    bn2 = trunk.stem[4]
+    bn2.weight = torch.nn.Parameter(bn2.weight.detach().clone())
+    assert amp.train_path_for(trunk) is not newer
+
+    c3d = network.get_network(make_opt("c3d"))
+    sig = amp._c3d_signature(c3d)
+    assert amp._c3d_signature(c3d) == sig and amp.Bf16TrainPathC3D(c3d).signature == sig
+    c3d.conv4a.bias = torch.nn.Parameter(c3d.conv4a.bias.detach().clone())
+    assert amp._c3d_signature(c3d) != sig

@@ -189,10 +189,12 @@ def reload_knobs() -> bool:
     ``ZSV_*`` variable in a live process and before the next launch; not meant to race with launches on other threads.
     Returns True when something had changed."""
     global _knob_generation, _knob_snapshot, _knobs_dirty
+    # (the flag goes down before load(): load() calls back here while it is up, and would never return.  A write that lands
+    # after this line raises it again and is picked up by the next load(); the snapshot below is taken after it either way.)
+    _knobs_dirty = False
     lib = load()
     with _lock:
         now = _zsv_environment()
-        _knobs_dirty = False
         if now == _knob_snapshot:
             return False
         _knob_snapshot = now

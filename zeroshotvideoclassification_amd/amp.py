@@ -43,10 +43,11 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
 from ._lib import ConvDesc
-from .inference import (ConvGeometry, c3d_layers, channel_pitch, clip_to_bf16, conv_bf16, maxpool3d_bf16, meanpool_bf16, pack_conv,
-                        run_blocks, video_resnet_ops)
+from .inference import (ConvGeometry, c3d_layers, channel_pitch, clip_to_bf16, conv_bf16, conv_bn_relu_chain, maxpool3d_bf16,
+                        meanpool_bf16, pack_conv, run_blocks, video_resnet_ops)
 
 _state = threading.local()
+_C3D_CONVS = ("conv1", "conv2", "conv3a", "conv3b", "conv4a", "conv4b", "conv5a", "conv5b")      # inference.c3d_layers' order
 
 
 class autocast:
@@ -295,6 +296,7 @@ class Bf16TrainPath:
         self.params = []
         for u in self.units:
             self.params += [p for p in (u.conv.weight, u.bn.weight, u.bn.bias) if p is not None]      # (affine=False: no gamma / beta)
+        self.signature = _trunk_signature(trunk)     # what train_path_for checks the cached path against
 
     # -- forward -------------------------------------------------------------------------------------------------------
     def _unit_fwd(self, u: _Unit, x: torch.Tensor, tape, residual=None, clips=None, wo=None):
@@ -499,6 +501,7 @@ class Bf16TrainPathC3D:
         self.params = []
         for u, _ in self.layers:
             self.params += [u.conv.weight, u.conv.bias]
+        self.signature = _c3d_signature(model)       # what c3d_features checks the cached path against
 
     def forward(self, clips: torch.Tensor, tape):
         x, wo = self.layers[0][0].clip_input(clips)
@@ -588,7 +591,7 @@ def c3d_features(model: nn.Module, clips: torch.Tensor) -> torch.Tensor:
     if not clips.is_cuda:
         raise RuntimeError("amp: MI355X HIP tensors only (there is no CPU fallback)")
     path = model.__dict__.get("_zsv_bf16_train_path")
-    if path is None:
+    if path is None or path.signature != _c3d_signature(model):     # (a replaced module or Parameter: see train_path_for)
         path = model.__dict__["_zsv_bf16_train_path"] = Bf16TrainPathC3D(model)
     return _C3DTrunkBf16.apply(clips, path, torch.is_grad_enabled(), *path.params)
 
@@ -599,8 +602,11 @@ class _GraphedTrunk:
     the side stream and joined at the end -- is captured once; a step replays the two graphs (12 us of host time each instead of
     ~8 ms of Python per pass, and no launch gaps on the device).  Inputs and outputs are static buffers: the clip is copied in,
     the pooled feature and the parameter gradients are copied out.  The kernels read the parameters, BatchNorm running
-    statistics and counters through their (fixed) addresses, so the optimizer's updates are seen by the next replay.  One
-    forward per backward: a second graphed forward before the first one's backward would overwrite its tape (checked)."""
+    statistics and counters through the addresses they had at capture, so the optimizer's updates are seen by the next replay;
+    each BatchNorm's ``momentum`` and ``eps`` are captured by value.  ``captured`` records all of that (``_graph_state``) and
+    ``_TrunkBf16.forward`` compares it before every replay: a moved tensor (``p.data = ...``, a re-assigned buffer) or a changed
+    ``momentum`` / ``eps`` drops the pair and captures again.  One forward per backward: a second graphed forward before the
+    first one's backward would overwrite its tape (checked)."""
 
     def __init__(self, path: "Bf16TrainPath", clips: torch.Tensor):
         self.path = path
@@ -608,6 +614,7 @@ class _GraphedTrunk:
         dev = clips.device
         self.clips = clips.detach().clone()
         self.generation = 0
+        self.captured = _graph_state(path)
         bns = [u.bn for u in path.units]
         saved = [(bn.running_mean.clone(), bn.running_var.clone(), bn.num_batches_tracked.clone()) for bn in bns if bn.running_mean is not None]
 
@@ -675,9 +682,53 @@ class _GraphedTrunk:
         return [next(it) if (g is not None and need) else None for g, need in zip(self.grad_list, needs)]
 
 
+def _trunk_signature(trunk: nn.Module) -> tuple:
+    """What a cached ``Bf16TrainPath`` holds by reference, read off the trunk as it is now: the ``id()`` of every unit's Conv3d and
+    BatchNorm3d module and of the Parameters behind ``path.params`` (same walk as ``video_resnet_ops``)."""
+    sig = []
+
+    def chain(mods):
+        for conv, bn, _ in conv_bn_relu_chain(mods, "amp"):
+            sig.extend((id(conv), id(bn), id(conv.weight), id(getattr(bn, "weight", None)), id(getattr(bn, "bias", None))))
+    chain(trunk.stem)
+    for layer in (trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4):
+        for block in layer:
+            chain(block.conv1)
+            chain(block.conv2)
+            if block.downsample is not None:
+                chain(block.downsample)
+    return tuple(sig)
+
+
+def _c3d_signature(model: nn.Module) -> tuple:
+    """``_trunk_signature`` for ``network.C3D``: its eight convolutions, their weights and biases."""
+    sig = []
+    for name in _C3D_CONVS:
+        conv = getattr(model, name)
+        sig.extend((id(conv), id(conv.weight), id(conv.bias)))
+    return tuple(sig)
+
+
+def _graph_state(path: "Bf16TrainPath") -> tuple:
+    """Everything a captured ``_GraphedTrunk`` froze that the model can change under it without the graph key noticing: the
+    address of every parameter and BatchNorm buffer (``num_batches_tracked`` included), and each BatchNorm's ``momentum`` / ``eps``."""
+    state = [p.data_ptr() for p in path.params]
+    for u in path.units:
+        bn = u.bn
+        for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
+            state.append(0 if b is None else b.data_ptr())
+        state.append(bn.momentum)
+        state.append(bn.eps)
+    return tuple(state)
+
+
 def train_path_for(trunk: nn.Module) -> Bf16TrainPath:
+    """The trunk's cached ``Bf16TrainPath``.  The path holds module objects and a list of Parameters: after a module was replaced
+    (``block.conv1[0][0] = ...``) or a Parameter object was (``load_state_dict(assign=True)``, ``bn.weight = nn.Parameter(...)``)
+    it would run the old weights, or hand autograd's gradients to Parameters the model no longer owns.  So the cache is checked
+    against ``_trunk_signature`` on every call and rebuilt on a mismatch; the captured graphs (``path._graphs``) go with it."""
     path = trunk.__dict__.get("_zsv_bf16_train_path")
-    if path is None:
+    if path is None or path.signature != _trunk_signature(trunk):
         path = trunk.__dict__["_zsv_bf16_train_path"] = Bf16TrainPath(trunk)
     return path
 
@@ -696,6 +747,11 @@ class _TrunkBf16(Function):
             key = (tuple(clips.shape), clips.device.index, tuple(u.bn.training for u in path.units))
             with torch.cuda.device(clips.device):
                 g = graphs.get(key)
+                if g is not None and g.captured != _graph_state(path):
+                    # a tensor moved or a BatchNorm's momentum / eps changed since capture: the replay would read and write memory
+                    # the model no longer owns.  The stale pair goes first (its private pool holds a whole tape), then a new capture.
+                    del graphs[key]
+                    g = None
                 if g is None:
                     while len(graphs) >= 2:                     # (a captured pair keeps its whole tape in a private pool: two shapes at most)
                         graphs.pop(next(iter(graphs)))

@@ -3,17 +3,20 @@
 //
 // Host C++ only (built with g++ against the torch headers; no device code, nothing generated): every operator builds the POD
 // descriptor from the tensor sizes, takes the stream torch is currently recording on, allocates the workspace from torch's caching
-// allocator and calls the same `zsv_*` entry point the ctypes glue (`_lib.py` / `ops.py`) calls.  The differentiable forms
+// allocator and calls the same `zsv_*` entry point the ctypes glue (`_lib.py` / `ops.py`) calls -- after checking every operand
+// (`want`, `describe`, `fit`) and under a device guard on the operands' device.  The differentiable forms
 // (`zsv::conv3d`, `zsv::batch_norm_relu`, `zsv::batch_norm_relu_eval`, `zsv::relu`, `zsv::linear`) register an Autograd kernel,
 // so C++ / TorchScript callers get the reference's
 // `nn.Conv3d` (resnet.py:23-30,40-52; network.py:102-117) and `nn.BatchNorm3d (+ ReLU)` (resnet.py:46-49,94-98) semantics
 // without Python.  The training harness of this repo keeps the ctypes path (panel cache, side-stream weight gradients, fused
 // block tails live in ops.py); tests/test_torch_binding_gpu.py checks both bindings against each other bit for bit.
 #include <ATen/ATen.h>
+#include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
 
+#include <cstdint>
 #include <vector>
 
 #include "zsv_hip.h"
@@ -26,45 +29,88 @@ void* stream_of(const at::Tensor& t) {
     return static_cast<void*>(c10::hip::getCurrentHIPStream(t.device().index()).stream());
 }
 
-void want(const at::Tensor& t, const char* name, int64_t dim) {
+// One tensor operand, completely, in this order: device (a GPU, and the one the operator runs on: `dev`, its first operand's),
+// dtype, rank, contiguity, extents (`sizes`; -1: any).  Every operand of every operator goes through here before anything is
+// allocated or launched: the kernels take raw pointers and trust the descriptor.
+void want(const at::Tensor& t, const char* name, c10::Device dev, at::IntArrayRef sizes) {
     TORCH_CHECK(t.is_cuda(), name, " must live on the GPU");       // (ROCm devices are `cuda` devices to torch)
-    TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32");
-    TORCH_CHECK(t.dim() == dim, name, " must have ", dim, " dimensions");
+    TORCH_CHECK(t.device() == dev, name, " is on ", t.device(), ", the operator's first operand on ", dev, ": one device per call");
+    TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32, not ", t.scalar_type());
+    TORCH_CHECK(t.dim() == (int64_t)sizes.size(), name, " must have ", sizes.size(), " dimensions, not ", t.dim());
     TORCH_CHECK(t.is_contiguous(), name, " must be contiguous (NCDHW)");
+    for (size_t i = 0; i < sizes.size(); ++i)
+        TORCH_CHECK(sizes[i] < 0 || t.size(i) == sizes[i], name, " has shape ", t.sizes(), ", expected ", sizes, " (-1: any)");
+}
+
+const int64_t ANY5[5] = {-1, -1, -1, -1, -1};
+
+// an extent on its way into an `int32_t` field of the C ABI
+int32_t fit(int64_t v, const char* name, int64_t index = -1) {
+    if (index < 0) {
+        TORCH_CHECK(v >= 0 && v <= INT32_MAX, name, " = ", v, " does not fit the C ABI's int32 field");
+    } else {
+        TORCH_CHECK(v >= 0 && v <= INT32_MAX, name, "[", index, "] = ", v, " does not fit the C ABI's int32 field");
+    }
+    return (int32_t)v;
+}
+
+// T * H * W of an (N, C, T, H, W) shape whose entries already fit int32: the kernels index one channel's voxels with an int32
+int32_t voxels(int64_t t, int64_t h, int64_t w, const char* name) {
+    const int64_t th = t * h;
+    TORCH_CHECK(th <= INT32_MAX && th * w <= INT32_MAX, name, ": T*H*W = ", t, "*", h, "*", w, " does not fit the C ABI's int32 field");
+    return (int32_t)(th * w);
 }
 
 at::Tensor scratch(size_t bytes, const at::Tensor& like) {
     return at::empty({static_cast<int64_t>(bytes ? bytes : 1)}, like.options().dtype(at::kByte));
 }
 
-zsv_conv_desc describe(at::IntArrayRef x, at::IntArrayRef w, at::IntArrayRef stride, at::IntArrayRef padding) {
+// `xname` / `wname`: what the caller calls the two shapes (an operand, or the `x_sizes` / `w_sizes` list), for the refusals
+zsv_conv_desc describe(at::IntArrayRef x, const char* xname, at::IntArrayRef w, const char* wname, at::IntArrayRef stride,
+                       at::IntArrayRef padding) {
     TORCH_CHECK(x.size() == 5 && w.size() == 5 && stride.size() == 3 && padding.size() == 3,
-                "conv3d: x and w are 5-d, stride and padding have three entries");
+                "conv3d: ", xname, " and ", wname, " are 5-d, stride and padding have three entries");
+    for (int i = 0; i < 3; ++i) {
+        TORCH_CHECK(stride[i] >= 1, "conv3d: stride[", i, "] = ", stride[i], " must be >= 1");
+        TORCH_CHECK(padding[i] >= 0, "conv3d: padding[", i, "] = ", padding[i], " must be >= 0");
+    }
     TORCH_CHECK(x[1] == w[1], "conv3d: x has ", x[1], " channels, w expects ", w[1]);
     zsv_conv_desc d;
-    d.N = (int32_t)x[0]; d.Cin = (int32_t)x[1]; d.Ti = (int32_t)x[2]; d.Hi = (int32_t)x[3]; d.Wi = (int32_t)x[4];
-    d.Cout = (int32_t)w[0]; d.kT = (int32_t)w[2]; d.kH = (int32_t)w[3]; d.kW = (int32_t)w[4];
-    d.sT = (int32_t)stride[0]; d.sH = (int32_t)stride[1]; d.sW = (int32_t)stride[2];
-    d.pT = (int32_t)padding[0]; d.pH = (int32_t)padding[1]; d.pW = (int32_t)padding[2];
-    d.To = (d.Ti + 2 * d.pT - d.kT) / d.sT + 1;
-    d.Ho = (d.Hi + 2 * d.pH - d.kH) / d.sH + 1;
-    d.Wo = (d.Wi + 2 * d.pW - d.kW) / d.sW + 1;
-    TORCH_CHECK(d.To > 0 && d.Ho > 0 && d.Wo > 0, "conv3d: empty output");
+    d.N = fit(x[0], xname, 0); d.Cin = fit(x[1], xname, 1); d.Ti = fit(x[2], xname, 2); d.Hi = fit(x[3], xname, 3); d.Wi = fit(x[4], xname, 4);
+    d.Cout = fit(w[0], wname, 0); d.kT = fit(w[2], wname, 2); d.kH = fit(w[3], wname, 3); d.kW = fit(w[4], wname, 4);
+    d.sT = fit(stride[0], "stride", 0); d.sH = fit(stride[1], "stride", 1); d.sW = fit(stride[2], "stride", 2);
+    d.pT = fit(padding[0], "padding", 0); d.pH = fit(padding[1], "padding", 1); d.pW = fit(padding[2], "padding", 2);
+    const int64_t to = (x[2] + 2 * padding[0] - w[2]) / stride[0] + 1;          // (64-bit: 2 * padding can leave int32)
+    const int64_t ho = (x[3] + 2 * padding[1] - w[3]) / stride[1] + 1;
+    const int64_t wo = (x[4] + 2 * padding[2] - w[4]) / stride[2] + 1;
+    TORCH_CHECK(x[2] + 2 * padding[0] >= w[2] && x[3] + 2 * padding[1] >= w[3] && x[4] + 2 * padding[2] >= w[4] && to > 0 && ho > 0 &&
+                    wo > 0, "conv3d: empty output");
+    d.To = fit(to, "output T"); d.Ho = fit(ho, "output H"); d.Wo = fit(wo, "output W");
+    voxels(x[2], x[3], x[4], xname);
+    voxels(to, ho, wo, "conv3d output");
     return d;
+}
+
+struct BnShape { int32_t N, C, S; };
+
+BnShape bn_shape(const at::Tensor& x) {
+    return {fit(x.size(0), "x", 0), fit(x.size(1), "x", 1),
+            voxels(fit(x.size(2), "x", 2), fit(x.size(3), "x", 3), fit(x.size(4), "x", 4), "x")};
 }
 
 // ---- plain operators: one C-ABI call each -----------------------------------------------------------------------------------
 at::Tensor conv3d_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, at::IntArrayRef stride,
                       at::IntArrayRef padding, bool relu) {
-    want(x, "x", 5);
-    want(w, "w", 5);
-    const zsv_conv_desc d = describe(x.sizes(), w.sizes(), stride, padding);
+    const c10::Device dev = x.device();
+    want(x, "x", dev, ANY5);
+    want(w, "w", dev, ANY5);
+    const zsv_conv_desc d = describe(x.sizes(), "x", w.sizes(), "w", stride, padding);
     const float* b = nullptr;
     if (bias.has_value() && bias->defined()) {
-        want(*bias, "bias", 1);
-        TORCH_CHECK(bias->numel() == d.Cout, "conv3d: bias has ", bias->numel(), " entries for ", d.Cout, " channels");
+        want(*bias, "bias", dev, {d.Cout});
         b = bias->data_ptr<float>();
     }
+    const c10::DeviceGuard guard(dev);               // allocation, workspace query and launch on the operands' device
     at::Tensor y = at::empty({d.N, d.Cout, d.To, d.Ho, d.Wo}, x.options());
     const size_t bytes = zsv_conv3d_fwd_workspace_bytes(&d);
     at::Tensor ws = scratch(bytes, x);
@@ -76,11 +122,12 @@ at::Tensor conv3d_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optio
 
 at::Tensor conv3d_dgrad(const at::Tensor& dy, const at::Tensor& w, at::IntArrayRef x_sizes, at::IntArrayRef stride,
                         at::IntArrayRef padding) {
-    want(dy, "dy", 5);
-    want(w, "w", 5);
-    const zsv_conv_desc d = describe(x_sizes, w.sizes(), stride, padding);
-    TORCH_CHECK(dy.size(0) == d.N && dy.size(1) == d.Cout && dy.size(2) == d.To && dy.size(3) == d.Ho && dy.size(4) == d.Wo,
-                "conv3d_dgrad: dy does not have the output's shape");
+    const c10::Device dev = dy.device();
+    want(dy, "dy", dev, ANY5);
+    want(w, "w", dev, ANY5);
+    const zsv_conv_desc d = describe(x_sizes, "x_sizes", w.sizes(), "w", stride, padding);
+    want(dy, "dy", dev, {d.N, d.Cout, d.To, d.Ho, d.Wo});
+    const c10::DeviceGuard guard(dev);
     at::Tensor dx = at::empty(x_sizes, dy.options());
     const size_t bytes = zsv_conv3d_dgrad_workspace_bytes(&d);
     at::Tensor ws = scratch(bytes, dy);
@@ -91,11 +138,12 @@ at::Tensor conv3d_dgrad(const at::Tensor& dy, const at::Tensor& w, at::IntArrayR
 
 at::Tensor conv3d_wgrad(const at::Tensor& x, const at::Tensor& dy, at::IntArrayRef w_sizes, at::IntArrayRef stride,
                         at::IntArrayRef padding) {
-    want(x, "x", 5);
-    want(dy, "dy", 5);
-    const zsv_conv_desc d = describe(x.sizes(), w_sizes, stride, padding);
-    TORCH_CHECK(dy.size(0) == d.N && dy.size(1) == d.Cout && dy.size(2) == d.To && dy.size(3) == d.Ho && dy.size(4) == d.Wo,
-                "conv3d_wgrad: dy does not have the output's shape");
+    const c10::Device dev = x.device();
+    want(x, "x", dev, ANY5);
+    want(dy, "dy", dev, ANY5);
+    const zsv_conv_desc d = describe(x.sizes(), "x", w_sizes, "w_sizes", stride, padding);
+    want(dy, "dy", dev, {d.N, d.Cout, d.To, d.Ho, d.Wo});
+    const c10::DeviceGuard guard(dev);
     at::Tensor dw = at::empty(w_sizes, x.options());
     const size_t bytes = zsv_conv3d_wgrad_workspace_bytes(&d);
     at::Tensor ws = scratch(bytes, x);
@@ -108,14 +156,14 @@ at::Tensor conv3d_wgrad(const at::Tensor& x, const at::Tensor& dy, at::IntArrayR
 std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at::Tensor& x, const at::Tensor& gamma, const at::Tensor& beta,
                                                             at::Tensor running_mean, at::Tensor running_var, double momentum,
                                                             double eps, bool relu) {
-    want(x, "x", 5);
-    want(gamma, "weight", 1);
-    want(beta, "bias", 1);
-    want(running_mean, "running_mean", 1);
-    want(running_var, "running_var", 1);
-    const int32_t N = (int32_t)x.size(0), C = (int32_t)x.size(1), S = (int32_t)(x.size(2) * x.size(3) * x.size(4));
-    TORCH_CHECK(gamma.numel() == C && beta.numel() == C && running_mean.numel() == C && running_var.numel() == C,
-                "batch_norm: per-channel tensors must have ", C, " entries");
+    const c10::Device dev = x.device();
+    want(x, "x", dev, ANY5);
+    const auto [N, C, S] = bn_shape(x);
+    want(gamma, "weight", dev, {C});
+    want(beta, "bias", dev, {C});
+    want(running_mean, "running_mean", dev, {C});
+    want(running_var, "running_var", dev, {C});
+    const c10::DeviceGuard guard(dev);
     at::Tensor y = at::empty_like(x), mean = at::empty({C}, x.options()), invstd = at::empty({C}, x.options());
     const size_t bytes = zsv_bn_workspace_bytes(N, C, S);
     at::Tensor ws = scratch(bytes, x);
@@ -123,6 +171,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at::Tensor& x,
                         y.data_ptr<float>(), mean.data_ptr<float>(), invstd.data_ptr<float>(), running_mean.data_ptr<float>(),
                         running_var.data_ptr<float>(), (float)momentum, (float)eps, ws.data_ptr(), bytes, stream_of(x)),
        "zsv_bn_fwd_train");
+    // the kernel wrote the two running statistics through raw pointers, below the ADInplaceOrView key: move their version
+    // counters by hand, as an in-place torch operator would, so that saved-tensor checks and caches keyed on `_version`
+    // (inference.engine_for) see the write
+    running_mean.unsafeGetTensorImpl()->bump_version();
+    running_var.unsafeGetTensorImpl()->bump_version();
     return {y, mean, invstd};
 }
 
@@ -130,10 +183,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at::Tensor& x,
 std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_train_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& y,
                                                             const at::Tensor& gamma, const at::Tensor& beta, const at::Tensor& mean,
                                                             const at::Tensor& invstd, bool relu) {
-    want(dy, "dy", 5);
-    want(x, "x", 5);
-    want(y, "y", 5);
-    const int32_t N = (int32_t)x.size(0), C = (int32_t)x.size(1), S = (int32_t)(x.size(2) * x.size(3) * x.size(4));
+    const c10::Device dev = x.device();
+    want(x, "x", dev, ANY5);
+    const auto [N, C, S] = bn_shape(x);
+    want(dy, "dy", dev, x.sizes());
+    want(y, "y", dev, x.sizes());
+    want(gamma, "weight", dev, {C});
+    want(beta, "bias", dev, {C});
+    want(mean, "save_mean", dev, {C});
+    want(invstd, "save_invstd", dev, {C});
+    const c10::DeviceGuard guard(dev);
     at::Tensor dx = at::empty_like(x), dgamma = at::empty({C}, x.options()), dbeta = at::empty({C}, x.options());
     const size_t bytes = zsv_bn_workspace_bytes(N, C, S);
     at::Tensor ws = scratch(bytes, x);
@@ -147,14 +206,14 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_train_bwd(const at::Tensor& dy
 // eval-mode (frozen statistics) BatchNorm3d (+ ReLU): y = relu?(x * a + b) from the running statistics, which are only read
 at::Tensor bn_eval_fwd(const at::Tensor& x, const at::Tensor& gamma, const at::Tensor& beta, const at::Tensor& running_mean,
                        const at::Tensor& running_var, double eps, bool relu) {
-    want(x, "x", 5);
-    want(gamma, "weight", 1);
-    want(beta, "bias", 1);
-    want(running_mean, "running_mean", 1);
-    want(running_var, "running_var", 1);
-    const int32_t N = (int32_t)x.size(0), C = (int32_t)x.size(1), S = (int32_t)(x.size(2) * x.size(3) * x.size(4));
-    TORCH_CHECK(gamma.numel() == C && beta.numel() == C && running_mean.numel() == C && running_var.numel() == C,
-                "batch_norm: per-channel tensors must have ", C, " entries");
+    const c10::Device dev = x.device();
+    want(x, "x", dev, ANY5);
+    const auto [N, C, S] = bn_shape(x);
+    want(gamma, "weight", dev, {C});
+    want(beta, "bias", dev, {C});
+    want(running_mean, "running_mean", dev, {C});
+    want(running_var, "running_var", dev, {C});
+    const c10::DeviceGuard guard(dev);
     at::Tensor y = at::empty_like(x);
     const size_t bytes = zsv_bn_workspace_bytes(N, C, S);
     at::Tensor ws = scratch(bytes, x);
@@ -170,16 +229,15 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_eval_bwd(const at::Tensor& dy,
                                                            const at::Tensor& beta, const at::Tensor& running_mean,
                                                            const at::Tensor& running_var, double eps, bool relu,
                                                            bool want_dgamma = true, bool want_dbeta = true) {
-    want(dy, "dy", 5);
-    want(x, "x", 5);
-    want(gamma, "weight", 1);
-    want(beta, "bias", 1);
-    want(running_mean, "running_mean", 1);
-    want(running_var, "running_var", 1);
-    TORCH_CHECK(dy.sizes() == x.sizes(), "bn_eval_bwd: dy does not have x's shape");
-    const int32_t N = (int32_t)x.size(0), C = (int32_t)x.size(1), S = (int32_t)(x.size(2) * x.size(3) * x.size(4));
-    TORCH_CHECK(gamma.numel() == C && beta.numel() == C && running_mean.numel() == C && running_var.numel() == C,
-                "batch_norm: per-channel tensors must have ", C, " entries");
+    const c10::Device dev = x.device();
+    want(x, "x", dev, ANY5);
+    const auto [N, C, S] = bn_shape(x);
+    want(dy, "dy", dev, x.sizes());
+    want(gamma, "weight", dev, {C});
+    want(beta, "bias", dev, {C});
+    want(running_mean, "running_mean", dev, {C});
+    want(running_var, "running_var", dev, {C});
+    const c10::DeviceGuard guard(dev);
     at::Tensor dx = at::empty_like(x);
     at::Tensor dgamma = want_dgamma ? at::empty({C}, x.options()) : at::Tensor();
     at::Tensor dbeta = want_dbeta ? at::empty({C}, x.options()) : at::Tensor();
@@ -201,15 +259,17 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_eval_bwd_op(const at::Tensor& 
 
 // nn.ReLU (resnet.py:49; network.py:147-166,614) and its backward (mask from the saved output, like ReLU(inplace=True))
 at::Tensor relu_fwd(const at::Tensor& x) {
-    TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), "relu: contiguous float32 GPU tensor expected");
+    want(x, "x", x.device(), x.sizes());                     // (any rank)
+    const c10::DeviceGuard guard(x.device());
     at::Tensor y = at::empty_like(x);
     ok(zsv_relu_fwd(x.data_ptr<float>(), y.data_ptr<float>(), x.numel(), stream_of(x)), "zsv_relu_fwd");
     return y;
 }
 
 at::Tensor relu_bwd(const at::Tensor& dy, const at::Tensor& y) {
-    TORCH_CHECK(dy.is_cuda() && y.is_cuda() && dy.scalar_type() == at::kFloat && y.scalar_type() == at::kFloat && dy.is_contiguous() &&
-                    y.is_contiguous() && dy.numel() == y.numel(), "relu_bwd: two contiguous float32 GPU tensors of one size expected");
+    want(dy, "dy", dy.device(), dy.sizes());                 // (any rank)
+    want(y, "y", dy.device(), dy.sizes());
+    const c10::DeviceGuard guard(dy.device());
     at::Tensor dx = at::empty_like(dy);
     ok(zsv_relu_bwd(dy.data_ptr<float>(), y.data_ptr<float>(), dx.data_ptr<float>(), dy.numel(), stream_of(dy)), "zsv_relu_bwd");
     return dx;
@@ -217,16 +277,16 @@ at::Tensor relu_bwd(const at::Tensor& dy, const at::Tensor& y) {
 
 // nn.Linear (+ ReLU) of network.MLP (network.py:603-617): y = relu?(x w^T + b), x (rows, in), w (out, in)
 at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, bool relu) {
-    want(x, "x", 2);
-    want(w, "w", 2);
-    TORCH_CHECK(x.size(1) == w.size(1), "linear: x has ", x.size(1), " features, w expects ", w.size(1));
-    const int32_t rows = (int32_t)x.size(0), in = (int32_t)x.size(1), out = (int32_t)w.size(0);
+    const c10::Device dev = x.device();
+    want(x, "x", dev, {-1, -1});
+    want(w, "w", dev, {-1, x.size(1)});
+    const int32_t rows = fit(x.size(0), "x", 0), in = fit(x.size(1), "x", 1), out = fit(w.size(0), "w", 0);
     const float* b = nullptr;
     if (bias.has_value() && bias->defined()) {
-        want(*bias, "bias", 1);
-        TORCH_CHECK(bias->numel() == out, "linear: bias has ", bias->numel(), " entries for ", out, " outputs");
+        want(*bias, "bias", dev, {out});
         b = bias->data_ptr<float>();
     }
+    const c10::DeviceGuard guard(dev);
     at::Tensor y = at::empty({rows, out}, x.options());
     const size_t bytes = zsv_linear_fwd_workspace_bytes(rows, in, out);
     at::Tensor ws = scratch(bytes, x);
@@ -237,10 +297,11 @@ at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optio
 }
 
 at::Tensor linear_dgrad(const at::Tensor& dy, const at::Tensor& w) {
-    want(dy, "dy", 2);
-    want(w, "w", 2);
-    TORCH_CHECK(dy.size(1) == w.size(0), "linear_dgrad: dy has ", dy.size(1), " columns, w has ", w.size(0), " rows");
-    const int32_t rows = (int32_t)dy.size(0), in = (int32_t)w.size(1), out = (int32_t)w.size(0);
+    const c10::Device dev = dy.device();
+    want(dy, "dy", dev, {-1, -1});
+    want(w, "w", dev, {dy.size(1), -1});
+    const int32_t rows = fit(dy.size(0), "dy", 0), in = fit(w.size(1), "w", 1), out = fit(w.size(0), "w", 0);
+    const c10::DeviceGuard guard(dev);
     at::Tensor dx = at::empty({rows, in}, dy.options());
     const size_t bytes = zsv_linear_dgrad_workspace_bytes(rows, in, out);
     at::Tensor ws = scratch(bytes, dy);
@@ -250,10 +311,11 @@ at::Tensor linear_dgrad(const at::Tensor& dy, const at::Tensor& w) {
 }
 
 at::Tensor linear_wgrad(const at::Tensor& x, const at::Tensor& dy) {
-    want(x, "x", 2);
-    want(dy, "dy", 2);
-    TORCH_CHECK(x.size(0) == dy.size(0), "linear_wgrad: x and dy must have the same number of rows");
-    const int32_t rows = (int32_t)x.size(0), in = (int32_t)x.size(1), out = (int32_t)dy.size(1);
+    const c10::Device dev = x.device();
+    want(x, "x", dev, {-1, -1});
+    want(dy, "dy", dev, {x.size(0), -1});
+    const int32_t rows = fit(x.size(0), "x", 0), in = fit(x.size(1), "x", 1), out = fit(dy.size(1), "dy", 1);
+    const c10::DeviceGuard guard(dev);
     at::Tensor dw = at::empty({out, in}, x.options());
     const size_t bytes = zsv_linear_wgrad_workspace_bytes(rows, in, out);
     at::Tensor ws = scratch(bytes, x);
