@@ -485,6 +485,8 @@ typedef struct zsv_adam_tensor {
     int64_t n;
     int64_t first_chunk;
 } zsv_adam_tensor;
+/* `lr` is a float in the four zsv_adam_multi* entry points and a double in the four zsv_adamw_multi*; both families form
+ * lr / (1 - beta1^step) in double, the first from (double)(float)lr. */
 int zsv_adam_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, float lr,
                    float beta1, float beta2, float eps, int32_t step, void* stream);
 

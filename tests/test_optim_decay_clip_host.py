@@ -1,5 +1,6 @@
 """Host side of weight decay / gradient clipping in ``optim.FusedAdam``: constructor validation, the C ABI surface and the
 state-dict compatibility.  Nothing here touches a device."""
+import ctypes
 import inspect
 import os
 import re
@@ -67,6 +68,62 @@ def test_new_symbols_are_declared_and_have_prototypes():
         assert lib.zsv_grad_norm_multi(None, 1, 1, 0, None, 0, None, None) != 0
         assert lib.zsv_grad_norm_finalize(None, 1, 1.0, None, None, None) != 0
         assert lib.zsv_adamw_multi(None, 1, 1, 1e-3, 0.9, 0.999, 1e-8, 0.1, 1, None, 1, None) != 0
+
+
+OK, BAD_SHAPE, NULL = 0, 1, 2                                 # ZSV_OK, ZSV_E_BAD_SHAPE, ZSV_E_NULL (include/zsv_hip.h)
+ADAM_FORMS = [(decay, scaled, avg) for decay in (False, True) for scaled in (False, True) for avg in (False, True)]
+
+
+def _adam_call(lib, form, table, count=3, chunks=3, lr=1e-3, weight_decay=0.1, step=1, state=None, shadows=None, avg_state=None,
+               ema_weight=0.1):
+    """One of the eight multi-tensor Adam entry points with the argument list its form takes."""
+    decay, scaled, avg = form
+    name = "zsv_adam" + ("w" if decay else "") + "_multi" + ("_scaled" if scaled else "") + ("_avg" if avg else "")
+    args = [table, count, chunks, lr, 0.9, 0.999, 1e-8]
+    if decay:
+        args += [weight_decay, 1, None]                        # decoupled, no clip record
+    args += [state, 0] if decay and scaled else [state] if scaled else [step]
+    if avg:
+        args += [shadows, avg_state, ema_weight]
+    return getattr(lib, name)(*args, None)
+
+
+@pytest.mark.parametrize("form", ADAM_FORMS, ids=lambda f: "adam" + "w" * f[0] + "_multi" + "_scaled" * f[1] + "_avg" * f[2])
+def test_adam_entry_points_decide_their_status_before_any_launch(form):
+    """Every refusal below is decided on the host, in this order: NULL table or scaler state, an empty table (which is fine even
+    with a bad step), the table's shape and the step number, the averaging arguments, lr / weight_decay.  The pointers are host
+    addresses: nothing here reaches a launch."""
+    decay, scaled, avg = form
+    lib = _lib.load()
+    host = (ctypes.c_char * 64)()
+    there = ctypes.addressof(host)
+    good = dict(state=there if scaled else None, shadows=there if avg else None, avg_state=there if avg else None)
+    assert _adam_call(lib, form, None, **good) == NULL
+    assert _adam_call(lib, form, None, count=0, **good) == NULL                           # the NULL table comes first
+    assert _adam_call(lib, form, there, count=0, chunks=0, step=0, **good) == OK
+    assert _adam_call(lib, form, there, count=0, chunks=0, step=-3, **good) == OK
+    assert _adam_call(lib, form, there, count=-1, **good) == BAD_SHAPE
+    assert _adam_call(lib, form, there, chunks=0, **good) == BAD_SHAPE
+    assert _adam_call(lib, form, there, chunks=1 << 31, **good) == BAD_SHAPE
+    if scaled:
+        assert _adam_call(lib, form, there, **dict(good, state=None)) == NULL
+        assert _adam_call(lib, form, there, count=0, **dict(good, state=None)) == NULL    # ... before the empty table
+    else:
+        assert _adam_call(lib, form, there, step=0, **good) == BAD_SHAPE
+        assert _adam_call(lib, form, there, step=-1, **good) == BAD_SHAPE
+    if avg:
+        assert _adam_call(lib, form, there, **dict(good, shadows=None)) == NULL
+        assert _adam_call(lib, form, there, **dict(good, avg_state=None)) == NULL
+        assert _adam_call(lib, form, there, ema_weight=1.5, **dict(good, avg_state=None)) == NULL   # NULL wins over the weight
+        assert _adam_call(lib, form, there, ema_weight=1.5, **good) == BAD_SHAPE
+        assert _adam_call(lib, form, there, ema_weight=float("nan"), **good) == BAD_SHAPE
+        assert _adam_call(lib, form, there, count=0, chunks=0, **dict(good, shadows=None)) == OK    # the empty table before these
+    if decay:
+        for bad in (-1e-3, float("nan"), float("inf"), float("-inf")):
+            assert _adam_call(lib, form, there, lr=bad, **good) == BAD_SHAPE, bad
+            assert _adam_call(lib, form, there, weight_decay=bad, **good) == BAD_SHAPE, bad
+        if avg:                                                                           # the averaging arguments come first
+            assert _adam_call(lib, form, there, lr=-1.0, **dict(good, shadows=None)) == NULL
 
 
 def test_state_dict_round_trip_and_old_state_dicts():

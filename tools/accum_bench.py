@@ -113,14 +113,13 @@ def run_kernel(args):
                 sync._accumulate(b, g, 1.0, assign)
         return fn
 
-    import struct
     from ctypes import c_void_p
-    from zeroshotvideoclassification_amd import _lib
+    from zeroshotvideoclassification_amd import _lib, _tables
     lib = _lib.load()
     tables = []                                              # uploaded once: the launches alone, without the per-pass table upload
     for b, g in zip(buckets, grads):
-        raw = b"".join(struct.pack("<QQqq", acc, g[i].data_ptr(), n, first) for i, acc, n, first in b.slices)
-        tables.append((torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(x.device), len(b.slices), b.chunks))
+        raw, chunks = _tables.pack_rows([(acc, g[i].data_ptr(), n) for i, acc, n in b.slices])
+        tables.append((torch.frombuffer(raw, dtype=torch.uint8).to(x.device), len(b.slices), chunks))
 
     def hip_launch_only():
         stream = c_void_p(torch.cuda.current_stream().cuda_stream)

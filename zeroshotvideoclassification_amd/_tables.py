@@ -6,13 +6,32 @@ and uploaded through ``PinnedRing``.
 """
 from __future__ import annotations
 
+import struct
+
 import torch
 
-CHUNK = 4096
+CHUNK = 4096                  # CHUNK of csrc/multi_tensor.h
 
 
 def chunks(n: int) -> int:
     return (n + CHUNK - 1) // CHUNK
+
+
+_ROW = {3: struct.Struct("<QQqq"), 5: struct.Struct("<QQQQqq")}       # zsv_pair_tensor / zsv_accum_tensor, zsv_adam_tensor
+
+
+def pack_rows(rows):
+    """The bytes of a descriptor table and its total chunk count.  A row is ``(*addresses, n)`` -- four addresses for a
+    ``zsv_adam_tensor``, two for a ``zsv_pair_tensor`` or ``zsv_accum_tensor`` -- and gets its ``first_chunk`` here.  (On the
+    host path of every optimizer step: one precompiled ``Struct`` per row shape, one join.)"""
+    if not rows:
+        return bytearray(), 0
+    pack = _ROW[len(rows[0])].pack
+    packed, first = [], 0
+    for row in rows:
+        packed.append(pack(*row, first))
+        first += (row[-1] + CHUNK - 1) // CHUNK
+    return bytearray(b"".join(packed)), first
 
 
 class PinnedRing:

@@ -1,6 +1,6 @@
-// adam_update.h -- the per-element Adam update and the weight-averaging rule, shared by every multi-tensor Adam kernel
-// (elementwise_pool.hip: zsv_adam_multi[_scaled]; optim.hip: their *_avg forms and zsv_avg_multi).  One body per mode, so the
-// parameters and moments of a step with averaging carry the bits of the same step without it.
+// adam_update.h -- the per-element Adam update, plain and with weight decay / clipping, and the weight-averaging rule: what the
+// one Adam kernel template of optim.hip runs per element, and what sgd.hip and zsv_avg_multi average with.  One body per mode, so
+// the parameters and moments of a step with averaging carry the bits of the same step without it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,6 +62,32 @@ __device__ __forceinline__ void adam_element(const zsv_adam_tensor& t, long i, f
     t.exp_avg[i] = mi;
     t.exp_avg_sq[i] = vi;
     const float pi = t.p[i] - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+    t.p[i] = pi;
+    if (AVG) avg_element(shadow, i, pi, k);
+}
+
+// ---- torch.optim.Adam(weight_decay=) / AdamW with the clip coefficient: element i of tensor t --------------------------------
+// g = g_mem * inv_scale * clip; L2: g += wd_l2 * p; moments; decoupled: p *= decay_factor (1 - lr * wd); the Adam update.
+struct AdamDecay {
+    float wd_l2;            // L2 mode: g += wd_l2 * p                (0 otherwise)
+    float decay_factor;     // decoupled mode: p *= decay_factor      (1 otherwise)
+    int decoupled;
+};
+
+template <bool AVG>
+__device__ __forceinline__ void adamw_element(const zsv_adam_tensor& t, long i, float inv_scale, float clip, const AdamDecay& d,
+                                              float b1, float b2, float eps, float step_size, float inv_sqrt_bc2,
+                                              float* __restrict__ shadow, const AvgWeight k) {
+    float pi = t.p[i];
+    float gi = t.g[i] * inv_scale;                 // two separate fp32 products, as unscale_ and clip_grad_norm_ store them
+    gi = gi * clip;
+    if (!d.decoupled) gi = gi + d.wd_l2 * pi;      // grad.add(param, alpha=weight_decay)
+    const float mi = b1 * t.exp_avg[i] + (1.f - b1) * gi;
+    const float vi = b2 * t.exp_avg_sq[i] + (1.f - b2) * gi * gi;
+    t.exp_avg[i] = mi;
+    t.exp_avg_sq[i] = vi;
+    if (d.decoupled) pi *= d.decay_factor;         // param.mul_(1 - lr * weight_decay)
+    pi = pi - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
     t.p[i] = pi;
     if (AVG) avg_element(shadow, i, pi, k);
 }

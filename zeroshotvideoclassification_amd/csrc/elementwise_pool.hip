@@ -1,4 +1,4 @@
-// elementwise_pool.hip -- ReLU, residual add, pooling, channel sums and Adam for gfx950.
+// elementwise_pool.hip -- ReLU, residual add, pooling, channel sums and the single-tensor Adam step for gfx950.
 //
 // HBM-bound passes that the reference reaches through torch.nn:
 //   relu        nn.ReLU / F.relu          resnet.py:49,95,98  network.py:147-166,614
@@ -6,14 +6,14 @@
 //   meanpool    torch.mean(f,(2,3,4))     network.py:595 (AdaptiveAvgPool3d resnet.py:251)
 //   maxpool3d   nn.MaxPool3d              network.py:103-118 (C3D)
 //   channel_sum bias gradient             network.py:102-117 convs, nn.Linear biases
-//   adam        torch.optim.Adam.step     main.py:131,200
+//   adam        torch.optim.Adam.step     main.py:131,200     (zsv_adam_step, one tensor)
+// The multi-tensor optimiser step that training runs, the loss scaler included, is optim.hip (SGD: sgd.hip).
 // Everything is float4-wide along the contiguous axis where alignment allows, grid-strided
 // with at most 2048 workgroups (8 per CU), reductions use 64-lane wave shuffles.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "zsv_hip.h"
 #include "zsv_common.h"
-#include "adam_update.h"
 
 namespace zsv {
 
@@ -400,133 +400,6 @@ extern "C" int zsv_adam_step(float* p, const float* g, float* exp_avg, float* ex
     const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
     hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_avg_sq, (long)n,
                        beta1, beta2, eps, step_size, inv_sqrt_bc2);
-    return launch_status();
-}
-
-// ---- multi-tensor Adam: one launch for every parameter tensor of the model ---------------------
-// table[i] = {p, g, exp_avg, exp_avg_sq, n, first_chunk}; a chunk is 256 threads x 16 elements.  The per-element update is
-// adam_element (adam_update.h), shared with the weight-averaging forms of optim.hip.
-namespace zsv {
-constexpr int ADAM_CHUNK = 4096;
-__global__ __launch_bounds__(256) void adam_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count, float b1,
-                                                         float b2, float eps, float step_size, float inv_sqrt_bc2) {
-    // binary search: last tensor whose first_chunk <= blockIdx.x
-    int lo = 0, hi = count - 1;
-    const long chunk = blockIdx.x;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
-    }
-    const zsv_adam_tensor t = table[lo];
-    const long base = (chunk - t.first_chunk) * ADAM_CHUNK;
-    const long end = min(t.n, base + ADAM_CHUNK);
-    for (long i = base + threadIdx.x; i < end; i += 256)
-        adam_element<false>(t, i, t.g[i], b1, b2, eps, step_size, inv_sqrt_bc2, nullptr, AvgWeight{});
-}
-}  // namespace zsv
-
-extern "C" int zsv_adam_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, float lr,
-                              float beta1, float beta2, float eps, int32_t step, void* stream) {
-    if (!table_device) return ZSV_E_NULL;
-    if (count <= 0 || total_chunks <= 0 || step <= 0 || total_chunks > 0x7fffffffL) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(zsv::adam_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
-                       count, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)));
-    return launch_status();
-}
-
-// ---- loss scaling (torch.cuda.amp.GradScaler, main.py:137,195-203) on the device -----------------------
-// scaler.scale(loss).backward(); scaler.step(optimizer); scaler.update() without a host round trip:
-//   grad_check_multi : found_inf |= any non-finite scaled gradient   (_amp_foreach_non_finite_check_and_unscale_)
-//   adam_multi_scaled: skipped when found_inf; gradients multiplied by 1/scale in registers; the bias correction
-//                      uses the device-side count of steps actually taken
-//   scaler_update    : _amp_update_scale_ (backoff / growth) + steps_done += !found_inf, found_inf = 0
-namespace zsv {
-__global__ __launch_bounds__(256) void grad_check_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count,
-                                                               zsv_scaler_state* __restrict__ st) {
-    int lo = 0, hi = count - 1;
-    const long chunk = blockIdx.x;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
-    }
-    const zsv_adam_tensor t = table[lo];
-    const long base = (chunk - t.first_chunk) * ADAM_CHUNK;
-    const long end = min(t.n, base + ADAM_CHUNK);
-    bool bad = false;
-    for (long i = base + threadIdx.x; i < end; i += 256) {
-        const float g = t.g[i];
-        bad |= !(fabsf(g) <= 3.402823466e38f);                    // inf or NaN
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) st->found_inf = 1;   // benign race: every writer stores 1
-}
-
-__global__ __launch_bounds__(256) void adam_multi_scaled_kernel(const zsv_adam_tensor* __restrict__ table, int count, float lr,
-                                                                float b1, float b2, float eps,
-                                                                const zsv_scaler_state* __restrict__ st) {
-    if (st->found_inf) return;                                     // scaler.step skips optimizer.step (main.py:200)
-    const float inv_scale = (float)(1.0 / (double)st->scale);      // as GradScaler: scale.double().reciprocal().float()
-    const int step = st->steps_done + 1;
-    const float step_size = (float)((double)lr / (1.0 - pow((double)b1, (double)step)));
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, (double)step)));
-    int lo = 0, hi = count - 1;
-    const long chunk = blockIdx.x;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
-    }
-    const zsv_adam_tensor t = table[lo];
-    const long base = (chunk - t.first_chunk) * ADAM_CHUNK;
-    const long end = min(t.n, base + ADAM_CHUNK);
-    for (long i = base + threadIdx.x; i < end; i += 256)
-        adam_element<false>(t, i, t.g[i] * inv_scale, b1, b2, eps, step_size, inv_sqrt_bc2, nullptr, AvgWeight{});
-}
-
-__global__ void scaler_update_kernel(zsv_scaler_state* st, float growth, float backoff, int interval) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (st->found_inf) {
-        st->scale *= backoff;
-        st->growth_tracker = 0;
-    } else {
-        const int ok = st->growth_tracker + 1;
-        if (ok == interval) {
-            const float grown = st->scale * growth;
-            if (fabsf(grown) <= 3.402823466e38f) st->scale = grown;   // torch keeps the old scale if growth overflows
-            st->growth_tracker = 0;
-        } else {
-            st->growth_tracker = ok;
-        }
-        st->steps_done += 1;
-    }
-    st->found_inf = 0;
-}
-}  // namespace zsv
-
-extern "C" int zsv_grad_check_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks,
-                                    zsv_scaler_state* state_device, void* stream) {
-    if (!table_device || !state_device) return ZSV_E_NULL;
-    if (count <= 0 || total_chunks <= 0 || total_chunks > 0x7fffffffL) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
-    hipLaunchKernelGGL(zsv::grad_check_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
-                       count, state_device);
-    return launch_status();
-}
-
-extern "C" int zsv_adam_multi_scaled(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, float lr,
-                                     float beta1, float beta2, float eps, const zsv_scaler_state* state_device, void* stream) {
-    if (!table_device || !state_device) return ZSV_E_NULL;
-    if (count <= 0 || total_chunks <= 0 || total_chunks > 0x7fffffffL) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
-    hipLaunchKernelGGL(zsv::adam_multi_scaled_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
-                       count, lr, beta1, beta2, eps, state_device);
-    return launch_status();
-}
-
-extern "C" int zsv_scaler_update(zsv_scaler_state* state_device, float growth_factor, float backoff_factor,
-                                 int32_t growth_interval, void* stream) {
-    if (!state_device) return ZSV_E_NULL;
-    if (!(growth_factor > 1.f) || !(backoff_factor > 0.f && backoff_factor < 1.f) || growth_interval <= 0) return ZSV_E_BAD_SHAPE;
-    hipLaunchKernelGGL(zsv::scaler_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state_device, growth_factor,
-                       backoff_factor, growth_interval);
     return launch_status();
 }
 

@@ -1,64 +1,80 @@
-// optim.hip -- weight decay and global-norm gradient clipping for the multi-tensor Adam step (include/zsv_hip.h).
+// optim.hip -- the multi-tensor optimiser step (include/zsv_hip.h): Adam with all its options, the loss scaler, the gradient
+// norm, gradient accumulation and weight averaging.  (SGD: sgd.hip.  The single-tensor zsv_adam_step: elementwise_pool.hip.)
 //
 //   torch                                          here
+//   Adam.step() over every parameter               adam_multi_kernel<DECAY_CLIP, SCALED, AVG>: ONE kernel template behind the eight
+//                                                  zsv_adam[w]_multi[_scaled][_avg] entry points, one launch per table
+//   GradScaler.step / .update                      grad_check_multi (found_inf), the SCALED forms (skipped on found_inf, 1/scale
+//                                                  folded into the gradient read, step number read on the device), scaler_update
 //   clip_grad_norm_(params, max_norm)              grad_norm_multi (sum of squares per 4096-element chunk, + the non-finite
 //                                                  check of the loss scaler) and grad_norm_finalize (fixed-order sum in double,
 //                                                  1/scale, {total_norm, clip_coef}); the coefficient is applied on the
 //                                                  gradient's way into the update, the gradients in memory are not rewritten
-//   Adam(weight_decay=) / AdamW                    adamw_multi / adamw_multi_scaled
+//   Adam(weight_decay=) / AdamW                    the DECAY_CLIP forms (zsv_adamw_multi*)
 //   GradScaler.unscale_                            grad_unscale_multi
 //   k x loss.backward() accumulating into .grad    grad_accum_multi (table of {acc, g}: acc = [acc +] scale * g, one launch per
 //                                                  gradient bucket and backward pass; ddp.GradientSync)
-//   swa_utils.AveragedModel.update_parameters      the *_avg forms of the four Adam launches (the shadow is updated with the
-//                                                  parameter value still in a register), avg_multi for BatchNorm running
-//                                                  statistics, avg_advance (the device-resident count), swap_multi
+//   swa_utils.AveragedModel.update_parameters      the AVG forms (the shadow is updated with the parameter value still in a
+//                                                  register), avg_multi for BatchNorm running statistics, avg_advance (the
+//                                                  device-resident count), swap_multi
 //
-// All of them walk the zsv_adam_tensor table of zsv_adam_multi (elementwise_pool.hip) the same way: one workgroup of 256
-// threads per chunk, a binary search over first_chunk.  No floating-point atomics: every sum has a fixed order, so the same
-// gradients give the same norm bits and the same parameter bits on every run.
+// All of them walk a descriptor table the same way (multi_tensor.h): one workgroup of 256 threads per chunk, a binary search
+// over first_chunk.  The per-element Adam updates and the averaging rule are adam_update.h.  No floating-point atomics: every
+// sum has a fixed order, so the same gradients give the same norm bits and the same parameter bits on every run.
+//
+// lr: the four zsv_adam_multi* entry points take it as float, the four zsv_adamw_multi* as double, and both families form
+// lr / (1 - beta1^step) in double -- of (double)(float)lr in the first, which is what their callers have always got.
 #include "zsv_common.h"
 #include "zsv_hip.h"
+#include "multi_tensor.h"
 #include "adam_update.h"
 
 #include <math.h>
 
 namespace zsv {
-constexpr int OPT_CHUNK = 4096;                       // = ADAM_CHUNK of elementwise_pool.hip
 
-// index of the last tensor whose first_chunk <= chunk
-template <typename T> __device__ __forceinline__ int find_index(const T* __restrict__ table, int count, long chunk) {
-    int lo = 0, hi = count - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
+// ---- the loss scaler: found_inf |= any non-finite gradient; scaler.update() -----------------------------------------------------
+__global__ __launch_bounds__(256) void grad_check_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count,
+                                                               zsv_scaler_state* __restrict__ st) {
+    const long chunk = blockIdx.x;
+    const zsv_adam_tensor t = find_tensor(table, count, chunk);
+    const Span s = chunk_span(t, chunk);
+    bool bad = false;
+    for (long i = s.base + threadIdx.x; i < s.end; i += 256) bad |= non_finite(t.g[i]);
+    if (__any(bad) && (threadIdx.x & 63) == 0) st->found_inf = 1;   // benign race: every writer stores 1
+}
+
+// _amp_update_scale_ (backoff / growth) + steps_done += !found_inf, found_inf = 0
+__global__ void scaler_update_kernel(zsv_scaler_state* st, float growth, float backoff, int interval) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (st->found_inf) {
+        st->scale *= backoff;
+        st->growth_tracker = 0;
+    } else {
+        const int ok = st->growth_tracker + 1;
+        if (ok == interval) {
+            const float grown = st->scale * growth;
+            if (!non_finite(grown)) st->scale = grown;              // torch keeps the old scale if growth overflows
+            st->growth_tracker = 0;
+        } else {
+            st->growth_tracker = ok;
+        }
+        st->steps_done += 1;
     }
-    return lo;
+    st->found_inf = 0;
 }
 
-__device__ __forceinline__ zsv_adam_tensor find_tensor(const zsv_adam_tensor* __restrict__ table, int count, long chunk) {
-    return table[find_index(table, count, chunk)];
-}
-
-// where a launch with weight averaging finds the shadows and the rule
-struct AvgArgs {
-    float* const* shadows;          // count pointers, parallel to the table
-    const zsv_avg_state* state;
-    float ema_weight;               // >= 0: EMA weight of the new value; < 0: equal-weight
-};
-
-__device__ __forceinline__ bool non_finite(float g) { return !(fabsf(g) <= 3.402823466e38f); }     // inf or NaN
-
+// ---- the gradient norm and unscale_ ---------------------------------------------------------------------------------------------
 // partials[blockIdx.x] = sum of g^2 over the chunk: <= 16 serial adds per lane, then a fixed 8-level tree over 256 lanes.
 __global__ __launch_bounds__(256) void grad_norm_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count,
                                                               float* __restrict__ partials, zsv_scaler_state* __restrict__ st) {
     __shared__ float red[4];
     const long chunk = blockIdx.x;
     const zsv_adam_tensor t = find_tensor(table, count, chunk);
-    const long base = (chunk - t.first_chunk) * OPT_CHUNK;
-    const long end = min(t.n, base + OPT_CHUNK);
+    const Span span = chunk_span(t, chunk);
     float s = 0.f;
     bool bad = false;
-    for (long i = base + threadIdx.x; i < end; i += 256) {
+    for (long i = span.base + threadIdx.x; i < span.end; i += 256) {
         const float g = t.g[i];
         bad |= non_finite(g);
         s += g * g;
@@ -89,11 +105,10 @@ __global__ __launch_bounds__(256) void grad_unscale_multi_kernel(const zsv_adam_
     const float inv_scale = (float)(1.0 / (double)st->scale);
     const long chunk = blockIdx.x;
     const zsv_adam_tensor t = find_tensor(table, count, chunk);
-    const long base = (chunk - t.first_chunk) * OPT_CHUNK;
-    const long end = min(t.n, base + OPT_CHUNK);
+    const Span span = chunk_span(t, chunk);
     float* g = const_cast<float*>(t.g);
     bool bad = false;
-    for (long i = base + threadIdx.x; i < end; i += 256) {
+    for (long i = span.base + threadIdx.x; i < span.end; i += 256) {
         const float gi = g[i];
         bad |= non_finite(gi);
         g[i] = gi * inv_scale;
@@ -101,100 +116,52 @@ __global__ __launch_bounds__(256) void grad_unscale_multi_kernel(const zsv_adam_
     if (__any(bad) && (threadIdx.x & 63) == 0) st->found_inf = 1;
 }
 
-struct AdamwArgs {
+// ---- Adam: one kernel template, one argument struct --------------------------------------------------------------------------
+// What a form does not use stays unset and is never read: the flags are compile-time, so an instantiation holds the loads and
+// the arithmetic of its options and nothing else.
+struct AdamArgs {
+    double lr;                          // SCALED: step_size is formed on the device, from the scaler's count of steps taken
     float b1, b2, eps;
-    float wd_l2;            // L2 mode: g += wd_l2 * p                (0 otherwise)
-    float decay_factor;     // decoupled mode: p *= decay_factor      (1 otherwise)
-    int decoupled;
-    const zsv_clip_record* clip;
+    int grads_unscaled;                 // DECAY_CLIP && SCALED: zsv_grad_unscale_multi has already run on this table
+    const zsv_scaler_state* st;         // SCALED
+    const zsv_clip_record* clip;        // DECAY_CLIP; NULL: no clipping
+    AdamDecay decay;                    // DECAY_CLIP
+    float ema_weight;                   // AVG; >= 0: EMA weight of the new value; < 0: equal-weight
+    float* const* shadows;              // AVG: count pointers, parallel to the table
+    const zsv_avg_state* avg;           // AVG
 };
 
-// g = g_mem * inv_scale * clip_coef; L2: g += wd * p; moments; decoupled: p *= 1 - lr * wd; Adam update; AVG: the shadow takes
-// the new p.
-template <bool AVG>
-__device__ __forceinline__ void adamw_chunk(const zsv_adam_tensor* __restrict__ table, int count, const AdamwArgs& a,
-                                            float inv_scale, float step_size, float inv_sqrt_bc2, const AvgArgs& avg) {
-    const float clip = a.clip != nullptr ? a.clip->clip_coef : 1.f;
+// step_size = lr / (1 - b1^step) and inv_sqrt_bc2 = 1 / sqrt(1 - b2^step) come from the host, formed in double, in the !SCALED
+// forms.  They are arguments of their own and not fields of AdamArgs: which product of `b1 * m + (1 - b1) * g` the compiler
+// contracts into the fma depends on it, and this is the choice every build so far has made.
+template <bool DECAY_CLIP, bool SCALED, bool AVG>
+__global__ __launch_bounds__(256) void adam_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count, AdamArgs a,
+                                                         float step_size, float inv_sqrt_bc2) {
+    float inv_scale = 1.f;
+    if (SCALED) {
+        if (a.st->found_inf) return;           // scaler.step skips optimizer.step: weight decay and the average included
+        if (!(DECAY_CLIP && a.grads_unscaled)) inv_scale = (float)(1.0 / (double)a.st->scale);   // scale.double().reciprocal().float()
+        const int step = a.st->steps_done + 1;
+        step_size = (float)(a.lr / (1.0 - pow((double)a.b1, (double)step)));
+        inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.b2, (double)step)));
+    }
+    const float clip = DECAY_CLIP && a.clip != nullptr ? a.clip->clip_coef : 1.f;
     const long chunk = blockIdx.x;
     const int index = find_index(table, count, chunk);
     const zsv_adam_tensor t = table[index];
     float* shadow = nullptr;
     AvgWeight k{};
     if (AVG) {
-        shadow = avg.shadows[index];
-        k = avg_weight(avg.state, avg.ema_weight);
+        shadow = a.shadows[index];
+        k = avg_weight(a.avg, a.ema_weight);
     }
-    const long base = (chunk - t.first_chunk) * OPT_CHUNK;
-    const long end = min(t.n, base + OPT_CHUNK);
-    for (long i = base + threadIdx.x; i < end; i += 256) {
-        float pi = t.p[i];
-        float gi = t.g[i] * inv_scale;                 // two separate fp32 products, as unscale_ and clip_grad_norm_ store them
-        gi = gi * clip;
-        if (!a.decoupled) gi = gi + a.wd_l2 * pi;      // grad.add(param, alpha=weight_decay)
-        const float mi = a.b1 * t.exp_avg[i] + (1.f - a.b1) * gi;
-        const float vi = a.b2 * t.exp_avg_sq[i] + (1.f - a.b2) * gi * gi;
-        t.exp_avg[i] = mi;
-        t.exp_avg_sq[i] = vi;
-        if (a.decoupled) pi *= a.decay_factor;         // param.mul_(1 - lr * weight_decay)
-        pi = pi - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + a.eps));
-        t.p[i] = pi;
-        if (AVG) avg_element(shadow, i, pi, k);
+    const Span s = chunk_span(t, chunk);
+    for (long i = s.base + threadIdx.x; i < s.end; i += 256) {
+        if (DECAY_CLIP)
+            adamw_element<AVG>(t, i, inv_scale, clip, a.decay, a.b1, a.b2, a.eps, step_size, inv_sqrt_bc2, shadow, k);
+        else            // the unscaled plain form has no product on the gradient at all
+            adam_element<AVG>(t, i, SCALED ? t.g[i] * inv_scale : t.g[i], a.b1, a.b2, a.eps, step_size, inv_sqrt_bc2, shadow, k);
     }
-}
-
-template <bool AVG>
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count, AdamwArgs a,
-                                                          float step_size, float inv_sqrt_bc2, AvgArgs avg) {
-    adamw_chunk<AVG>(table, count, a, 1.f, step_size, inv_sqrt_bc2, avg);
-}
-
-template <bool AVG>
-__global__ __launch_bounds__(256) void adamw_multi_scaled_kernel(const zsv_adam_tensor* __restrict__ table, int count, AdamwArgs a,
-                                                                 double lr, const zsv_scaler_state* __restrict__ st,
-                                                                 int grads_unscaled, AvgArgs avg) {
-    if (st->found_inf) return;                     // scaler.step skips optimizer.step, weight decay and averaging included
-    const float inv_scale = grads_unscaled ? 1.f : (float)(1.0 / (double)st->scale);
-    const int step = st->steps_done + 1;
-    const float step_size = (float)(lr / (1.0 - pow((double)a.b1, (double)step)));
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.b2, (double)step)));
-    adamw_chunk<AVG>(table, count, a, inv_scale, step_size, inv_sqrt_bc2, avg);
-}
-
-// ---- zsv_adam_multi[_scaled] with the average: the plain update (adam_element, the body elementwise_pool.hip runs) ------------
-__device__ __forceinline__ void adam_avg_chunk(const zsv_adam_tensor* __restrict__ table, int count, float b1, float b2, float eps,
-                                               float inv_scale, bool scaled, float step_size, float inv_sqrt_bc2,
-                                               const AvgArgs& avg) {
-    const long chunk = blockIdx.x;
-    const int index = find_index(table, count, chunk);
-    const zsv_adam_tensor t = table[index];
-    float* shadow = avg.shadows[index];
-    const AvgWeight k = avg_weight(avg.state, avg.ema_weight);
-    const long base = (chunk - t.first_chunk) * OPT_CHUNK;
-    const long end = min(t.n, base + OPT_CHUNK);
-    if (scaled) {
-        for (long i = base + threadIdx.x; i < end; i += 256)
-            adam_element<true>(t, i, t.g[i] * inv_scale, b1, b2, eps, step_size, inv_sqrt_bc2, shadow, k);
-    } else {
-        for (long i = base + threadIdx.x; i < end; i += 256)
-            adam_element<true>(t, i, t.g[i], b1, b2, eps, step_size, inv_sqrt_bc2, shadow, k);
-    }
-}
-
-__global__ __launch_bounds__(256) void adam_multi_avg_kernel(const zsv_adam_tensor* __restrict__ table, int count, float b1,
-                                                             float b2, float eps, float step_size, float inv_sqrt_bc2,
-                                                             AvgArgs avg) {
-    adam_avg_chunk(table, count, b1, b2, eps, 1.f, false, step_size, inv_sqrt_bc2, avg);
-}
-
-__global__ __launch_bounds__(256) void adam_multi_scaled_avg_kernel(const zsv_adam_tensor* __restrict__ table, int count, float lr,
-                                                                    float b1, float b2, float eps,
-                                                                    const zsv_scaler_state* __restrict__ st, AvgArgs avg) {
-    if (st->found_inf) return;                                     // a skipped step averages nothing
-    const float inv_scale = (float)(1.0 / (double)st->scale);
-    const int step = st->steps_done + 1;
-    const float step_size = (float)((double)lr / (1.0 - pow((double)b1, (double)step)));
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, (double)step)));
-    adam_avg_chunk(table, count, b1, b2, eps, inv_scale, true, step_size, inv_sqrt_bc2, avg);
 }
 
 // ---- pairs of arrays: b = rule(b, a) (avg_multi) and a <-> b (swap_multi) ------------------------------------------------------
@@ -207,12 +174,12 @@ typedef float pair_v4f __attribute__((ext_vector_type(4)));
 template <bool WRITE_A, typename F>
 __device__ __forceinline__ void pair_chunk(const zsv_pair_tensor* __restrict__ table, int count, F f) {
     const long chunk = blockIdx.x;
-    const zsv_pair_tensor t = table[find_index(table, count, chunk)];
-    const long base = (chunk - t.first_chunk) * OPT_CHUNK;
-    if (base >= t.n) return;
-    const int len = (int)min((long)OPT_CHUNK, t.n - base);
-    float* __restrict__ a = t.a + base;
-    float* __restrict__ b = t.b + base;
+    const zsv_pair_tensor t = find_tensor(table, count, chunk);
+    const Span s = chunk_span(t, chunk);
+    if (s.base >= s.end) return;
+    const int len = (int)(s.end - s.base);
+    float* __restrict__ a = t.a + s.base;
+    float* __restrict__ b = t.b + s.base;
 
     const int head = min(len, (int)(((16u - (unsigned)((uintptr_t)b & 15u)) & 15u) >> 2));
     const int nvec = (len - head) >> 2;
@@ -300,17 +267,12 @@ __device__ __forceinline__ float accum_one(float a, float g, float scale, bool a
 __global__ __launch_bounds__(256) void grad_accum_multi_kernel(const zsv_accum_tensor* __restrict__ table, int count, float scale,
                                                                int assign) {
     const long chunk = blockIdx.x;
-    int lo = 0, hi = count - 1;                       // last tensor whose first_chunk <= chunk
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
-    }
-    const zsv_accum_tensor t = table[lo];
-    const long base = (chunk - t.first_chunk) * OPT_CHUNK;
-    if (base >= t.n) return;
-    const int len = (int)min((long)OPT_CHUNK, t.n - base);
-    float* __restrict__ acc = t.acc + base;
-    const float* __restrict__ g = t.g + base;
+    const zsv_accum_tensor t = find_tensor(table, count, chunk);
+    const Span s = chunk_span(t, chunk);
+    if (s.base >= s.end) return;
+    const int len = (int)(s.end - s.base);
+    float* __restrict__ acc = t.acc + s.base;
+    const float* __restrict__ g = t.g + s.base;
     const bool set = assign != 0;
 
     const int head = min(len, (int)(((16u - (unsigned)((uintptr_t)acc & 15u)) & 15u) >> 2));
@@ -353,17 +315,54 @@ static inline bool bad_table(int32_t count, int64_t total_chunks) {
     return count <= 0 || total_chunks <= 0 || total_chunks > 0x7fffffffL;
 }
 
-static inline bool make_args(AdamwArgs& a, double lr, float beta1, float beta2, float eps, double weight_decay, int32_t decoupled,
-                             const zsv_clip_record* clip) {
-    if (!(lr >= 0.0) || !(weight_decay >= 0.0) || !isfinite(lr) || !isfinite(weight_decay)) return false;
+// ---- the host half of every Adam launch ------------------------------------------------------------------------------------------
+static inline AdamArgs adam_args(double lr, float beta1, float beta2, float eps) {
+    AdamArgs a{};                       // every pointer NULL until an entry point sets it
+    a.lr = lr;
     a.b1 = beta1;
     a.b2 = beta2;
     a.eps = eps;
-    a.decoupled = decoupled != 0 && weight_decay != 0.0;
-    a.wd_l2 = a.decoupled ? 0.f : (float)weight_decay;
-    a.decay_factor = a.decoupled ? (float)(1.0 - lr * weight_decay) : 1.f;
-    a.clip = clip;
-    return true;
+    return a;
+}
+
+// Validates in the order every entry point has always used -- NULL table / scaler state; an empty table is fine; the table's shape
+// (and the step number, which only the unscaled forms take); the averaging arguments; lr and weight_decay, which only the
+// DECAY_CLIP forms check -- and launches the instantiation the three flags name.
+static int adam_launch(bool decay_clip, bool scaled, bool avg, const zsv_adam_tensor* table, int32_t count, int64_t total_chunks,
+                       AdamArgs a, double weight_decay, int32_t decoupled, int32_t step, void* stream) {
+    if (!table || (scaled && !a.st)) return ZSV_E_NULL;
+    if (bad_table(count, total_chunks) || (!scaled && step <= 0)) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
+    if (avg) {
+        if (!a.shadows || !a.avg) return ZSV_E_NULL;
+        if (!(a.ema_weight <= 1.f)) return ZSV_E_BAD_SHAPE;                 // (a NaN weight is refused too)
+    }
+    a.decay = AdamDecay{0.f, 1.f, 0};
+    if (decay_clip) {
+        if (!(a.lr >= 0.0) || !(weight_decay >= 0.0) || !isfinite(a.lr) || !isfinite(weight_decay)) return ZSV_E_BAD_SHAPE;
+        a.decay.decoupled = decoupled != 0 && weight_decay != 0.0;
+        if (a.decay.decoupled) a.decay.decay_factor = (float)(1.0 - a.lr * weight_decay);
+        else a.decay.wd_l2 = (float)weight_decay;
+    }
+    float step_size = 0.f, inv_sqrt_bc2 = 0.f;                              // SCALED: formed on the device
+    if (!scaled) {
+        step_size = (float)(a.lr / (1.0 - pow((double)a.b1, (double)step)));
+        inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.b2, (double)step)));
+    }
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table, count, a, step_size,
+                           inv_sqrt_bc2);
+    };
+    switch ((decay_clip ? 4 : 0) | (scaled ? 2 : 0) | (avg ? 1 : 0)) {
+        case 0: launch(adam_multi_kernel<false, false, false>); break;
+        case 1: launch(adam_multi_kernel<false, false, true>); break;
+        case 2: launch(adam_multi_kernel<false, true, false>); break;
+        case 3: launch(adam_multi_kernel<false, true, true>); break;
+        case 4: launch(adam_multi_kernel<true, false, false>); break;
+        case 5: launch(adam_multi_kernel<true, false, true>); break;
+        case 6: launch(adam_multi_kernel<true, true, false>); break;
+        case 7: launch(adam_multi_kernel<true, true, true>); break;
+    }
+    return launch_status();
 }
 }  // namespace zsv
 
@@ -401,33 +400,6 @@ extern "C" int zsv_grad_unscale_multi(const zsv_adam_tensor* table_device, int32
     return launch_status();
 }
 
-extern "C" int zsv_adamw_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr, float beta1,
-                               float beta2, float eps, double weight_decay, int32_t decoupled,
-                               const zsv_clip_record* clip_device, int32_t step, void* stream) {
-    if (!table_device) return ZSV_E_NULL;
-    if (bad_table(count, total_chunks) || step <= 0) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
-    AdamwArgs a;
-    if (!make_args(a, lr, beta1, beta2, eps, weight_decay, decoupled, clip_device)) return ZSV_E_BAD_SHAPE;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
-                       count, a, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), AvgArgs{});
-    return launch_status();
-}
-
-extern "C" int zsv_adamw_multi_scaled(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr,
-                                      float beta1, float beta2, float eps, double weight_decay, int32_t decoupled,
-                                      const zsv_clip_record* clip_device, const zsv_scaler_state* state_device,
-                                      int32_t grads_unscaled, void* stream) {
-    if (!table_device || !state_device) return ZSV_E_NULL;
-    if (bad_table(count, total_chunks)) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
-    AdamwArgs a;
-    if (!make_args(a, lr, beta1, beta2, eps, weight_decay, decoupled, clip_device)) return ZSV_E_BAD_SHAPE;
-    hipLaunchKernelGGL(adamw_multi_scaled_kernel<false>, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream,
-                       table_device, count, a, lr, state_device, grads_unscaled, AvgArgs{});
-    return launch_status();
-}
-
 extern "C" int zsv_grad_accum_multi(const zsv_accum_tensor* table_device, int32_t count, int64_t total_chunks, float scale,
                                     int32_t assign, void* stream) {
     if (!table_device) return ZSV_E_NULL;
@@ -437,51 +409,90 @@ extern "C" int zsv_grad_accum_multi(const zsv_accum_tensor* table_device, int32_
     return launch_status();
 }
 
-// ---- weight averaging -------------------------------------------------------------------------------------------------------
-static inline bool bad_avg(float* const* shadows_device, const zsv_avg_state* avg_state_device, float ema_weight) {
-    return !shadows_device || !avg_state_device || !(ema_weight <= 1.f);          // (a NaN weight is refused too)
+// ---- the loss scaler ------------------------------------------------------------------------------------------------------------
+extern "C" int zsv_grad_check_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks,
+                                    zsv_scaler_state* state_device, void* stream) {
+    if (!table_device || !state_device) return ZSV_E_NULL;
+    if (bad_table(count, total_chunks)) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
+    hipLaunchKernelGGL(grad_check_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
+                       count, state_device);
+    return launch_status();
+}
+
+extern "C" int zsv_scaler_update(zsv_scaler_state* state_device, float growth_factor, float backoff_factor,
+                                 int32_t growth_interval, void* stream) {
+    if (!state_device) return ZSV_E_NULL;
+    if (!(growth_factor > 1.f) || !(backoff_factor > 0.f && backoff_factor < 1.f) || growth_interval <= 0) return ZSV_E_BAD_SHAPE;
+    hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state_device, growth_factor,
+                       backoff_factor, growth_interval);
+    return launch_status();
+}
+
+// ---- Adam: the eight entry points fill AdamArgs; adam_launch does the rest --------------------------------------------------------
+// (a float `lr` widens here, exactly: the header comment)
+extern "C" int zsv_adam_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, float lr, float beta1,
+                              float beta2, float eps, int32_t step, void* stream) {
+    return adam_launch(false, false, false, table_device, count, total_chunks, adam_args(lr, beta1, beta2, eps), 0.0, 0, step, stream);
+}
+
+extern "C" int zsv_adam_multi_scaled(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, float lr,
+                                     float beta1, float beta2, float eps, const zsv_scaler_state* state_device, void* stream) {
+    AdamArgs a = adam_args(lr, beta1, beta2, eps);
+    a.st = state_device;
+    return adam_launch(false, true, false, table_device, count, total_chunks, a, 0.0, 0, 0, stream);
+}
+
+extern "C" int zsv_adamw_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr, float beta1,
+                               float beta2, float eps, double weight_decay, int32_t decoupled,
+                               const zsv_clip_record* clip_device, int32_t step, void* stream) {
+    AdamArgs a = adam_args(lr, beta1, beta2, eps);
+    a.clip = clip_device;
+    return adam_launch(true, false, false, table_device, count, total_chunks, a, weight_decay, decoupled, step, stream);
+}
+
+extern "C" int zsv_adamw_multi_scaled(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr,
+                                      float beta1, float beta2, float eps, double weight_decay, int32_t decoupled,
+                                      const zsv_clip_record* clip_device, const zsv_scaler_state* state_device,
+                                      int32_t grads_unscaled, void* stream) {
+    AdamArgs a = adam_args(lr, beta1, beta2, eps);
+    a.clip = clip_device;
+    a.st = state_device;
+    a.grads_unscaled = grads_unscaled;
+    return adam_launch(true, true, false, table_device, count, total_chunks, a, weight_decay, decoupled, 0, stream);
+}
+
+static inline void set_average(AdamArgs& a, float* const* shadows_device, const zsv_avg_state* avg_state_device, float ema_weight) {
+    a.shadows = shadows_device;
+    a.avg = avg_state_device;
+    a.ema_weight = ema_weight;
 }
 
 extern "C" int zsv_adam_multi_avg(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, float lr, float beta1,
                                   float beta2, float eps, int32_t step, float* const* shadows_device,
                                   const zsv_avg_state* avg_state_device, float ema_weight, void* stream) {
-    if (!table_device) return ZSV_E_NULL;
-    if (bad_table(count, total_chunks) || step <= 0) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
-    if (bad_avg(shadows_device, avg_state_device, ema_weight)) return shadows_device && avg_state_device ? ZSV_E_BAD_SHAPE : ZSV_E_NULL;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(adam_multi_avg_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device, count,
-                       beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)),
-                       AvgArgs{shadows_device, avg_state_device, ema_weight});
-    return launch_status();
+    AdamArgs a = adam_args(lr, beta1, beta2, eps);
+    set_average(a, shadows_device, avg_state_device, ema_weight);
+    return adam_launch(false, false, true, table_device, count, total_chunks, a, 0.0, 0, step, stream);
 }
 
 extern "C" int zsv_adam_multi_scaled_avg(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, float lr,
                                          float beta1, float beta2, float eps, const zsv_scaler_state* state_device,
                                          float* const* shadows_device, const zsv_avg_state* avg_state_device,
                                          float ema_weight, void* stream) {
-    if (!table_device || !state_device) return ZSV_E_NULL;
-    if (bad_table(count, total_chunks)) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
-    if (bad_avg(shadows_device, avg_state_device, ema_weight)) return shadows_device && avg_state_device ? ZSV_E_BAD_SHAPE : ZSV_E_NULL;
-    hipLaunchKernelGGL(adam_multi_scaled_avg_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
-                       count, lr, beta1, beta2, eps, state_device, AvgArgs{shadows_device, avg_state_device, ema_weight});
-    return launch_status();
+    AdamArgs a = adam_args(lr, beta1, beta2, eps);
+    a.st = state_device;
+    set_average(a, shadows_device, avg_state_device, ema_weight);
+    return adam_launch(false, true, true, table_device, count, total_chunks, a, 0.0, 0, 0, stream);
 }
 
 extern "C" int zsv_adamw_multi_avg(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr,
                                    float beta1, float beta2, float eps, double weight_decay, int32_t decoupled,
                                    const zsv_clip_record* clip_device, int32_t step, float* const* shadows_device,
                                    const zsv_avg_state* avg_state_device, float ema_weight, void* stream) {
-    if (!table_device) return ZSV_E_NULL;
-    if (bad_table(count, total_chunks) || step <= 0) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
-    if (bad_avg(shadows_device, avg_state_device, ema_weight)) return shadows_device && avg_state_device ? ZSV_E_BAD_SHAPE : ZSV_E_NULL;
-    AdamwArgs a;
-    if (!make_args(a, lr, beta1, beta2, eps, weight_decay, decoupled, clip_device)) return ZSV_E_BAD_SHAPE;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device,
-                       count, a, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), AvgArgs{shadows_device, avg_state_device, ema_weight});
-    return launch_status();
+    AdamArgs a = adam_args(lr, beta1, beta2, eps);
+    a.clip = clip_device;
+    set_average(a, shadows_device, avg_state_device, ema_weight);
+    return adam_launch(true, false, true, table_device, count, total_chunks, a, weight_decay, decoupled, step, stream);
 }
 
 extern "C" int zsv_adamw_multi_scaled_avg(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, double lr,
@@ -489,16 +500,15 @@ extern "C" int zsv_adamw_multi_scaled_avg(const zsv_adam_tensor* table_device, i
                                           const zsv_clip_record* clip_device, const zsv_scaler_state* state_device,
                                           int32_t grads_unscaled, float* const* shadows_device,
                                           const zsv_avg_state* avg_state_device, float ema_weight, void* stream) {
-    if (!table_device || !state_device) return ZSV_E_NULL;
-    if (bad_table(count, total_chunks)) return count == 0 ? ZSV_OK : ZSV_E_BAD_SHAPE;
-    if (bad_avg(shadows_device, avg_state_device, ema_weight)) return shadows_device && avg_state_device ? ZSV_E_BAD_SHAPE : ZSV_E_NULL;
-    AdamwArgs a;
-    if (!make_args(a, lr, beta1, beta2, eps, weight_decay, decoupled, clip_device)) return ZSV_E_BAD_SHAPE;
-    hipLaunchKernelGGL(adamw_multi_scaled_kernel<true>, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream,
-                       table_device, count, a, lr, state_device, grads_unscaled,
-                       AvgArgs{shadows_device, avg_state_device, ema_weight});
-    return launch_status();
+    AdamArgs a = adam_args(lr, beta1, beta2, eps);
+    a.clip = clip_device;
+    a.st = state_device;
+    a.grads_unscaled = grads_unscaled;
+    set_average(a, shadows_device, avg_state_device, ema_weight);
+    return adam_launch(true, true, true, table_device, count, total_chunks, a, weight_decay, decoupled, 0, stream);
 }
+
+// ---- weight averaging on its own ------------------------------------------------------------------------------------------------
 
 extern "C" int zsv_avg_multi(const zsv_pair_tensor* table_device, int32_t count, int64_t total_chunks,
                              const zsv_avg_state* avg_state_device, float ema_weight,

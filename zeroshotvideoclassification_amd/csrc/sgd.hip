@@ -2,7 +2,8 @@
 // zsv_adam_multi, with the loss scaler, the clip coefficient and the weight average folded into the same launch
 // (include/zsv_hip.h: zsv_sgd_multi).  ONE entry point: what a step does not use is a NULL pointer, tested once per workgroup.
 //
-// One workgroup of 256 threads per 4096-element chunk, a binary search over first_chunk, as in optim.hip.  The pass is
+// One workgroup of 256 threads per 4096-element chunk, found through multi_tensor.h as in optim.hip; the averaging rule is
+// adam_update.h's.  The pass is
 // HBM-bound (read p, g, buf, write p, buf: 20 bytes per element, 28 with the average), so the body moves 16 bytes per lane:
 //   * every pointer of the tensor (p, g, and buf / shadow where present) 16-byte aligned at the chunk's base -- a chunk is 16 KiB,
 //     so that is the alignment of the tensor itself: float4 loads and stores, then a scalar tail of 0-3 elements;
@@ -12,14 +13,13 @@
 // run (no atomics).  No element outside [0, n) of any array is read or written.
 #include "zsv_common.h"
 #include "zsv_hip.h"
+#include "multi_tensor.h"
 #include "adam_update.h"
 
 #include <math.h>
 
 namespace zsv {
 namespace sgd {
-constexpr int CHUNK = 4096;                           // = OPT_CHUNK of optim.hip, ADAM_CHUNK of elementwise_pool.hip
-
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct Args {
@@ -67,19 +67,15 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(const zsv_adam_tensor* _
     s.first = (a.st != nullptr ? a.st->steps_done : 0) == a.first_step;
 
     const long chunk = blockIdx.x;
-    int lo = 0, hi = count - 1;                           // last tensor whose first_chunk <= chunk
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
-    }
-    const zsv_adam_tensor t = table[lo];
-    const long base = (chunk - t.first_chunk) * CHUNK;
-    if (base >= t.n) return;
-    const int len = (int)min((long)CHUNK, t.n - base);
-    float* __restrict__ p = t.p + base;
-    const float* __restrict__ g = t.g + base;
-    float* __restrict__ buf = a.use_momentum ? t.exp_avg + base : nullptr;
-    float* __restrict__ shadow = a.shadows != nullptr ? a.shadows[lo] + base : nullptr;
+    const int index = find_index(table, count, chunk);
+    const zsv_adam_tensor t = table[index];
+    const Span span = chunk_span(t, chunk);
+    if (span.base >= span.end) return;
+    const int len = (int)(span.end - span.base);
+    float* __restrict__ p = t.p + span.base;
+    const float* __restrict__ g = t.g + span.base;
+    float* __restrict__ buf = a.use_momentum ? t.exp_avg + span.base : nullptr;
+    float* __restrict__ shadow = a.shadows != nullptr ? a.shadows[index] + span.base : nullptr;
     AvgWeight k{};
     if (shadow != nullptr) k = avg_weight(a.avg, a.ema_weight);
     const bool load_buf = buf != nullptr && !s.first;     // a first step never reads the buffer (torch has none yet)

@@ -43,7 +43,6 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional
 
-import struct
 import weakref
 from ctypes import c_void_p
 
@@ -51,7 +50,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from ._tables import PinnedRing, chunks as _chunks
+from ._tables import PinnedRing, chunks as _chunks, pack_rows
 
 DEFAULT_BUCKET_BYTES = 25 * 1024 * 1024
 
@@ -92,14 +91,9 @@ class _Bucket:
             off += p.numel()
         self.pending = len(params)
         self.work = None
-        # static half of the zsv_grad_accum_multi table: (accumulator slice address, n, first_chunk) per non-empty parameter
-        self.slices, first = [], 0
-        if self.flat.is_cuda:
-            for i, v in enumerate(self.views):
-                if v.numel():
-                    self.slices.append((i, v.data_ptr(), v.numel(), first))
-                    first += _chunks(v.numel())
-        self.chunks = first
+        # static half of the zsv_grad_accum_multi table: (index, accumulator slice address, n) per non-empty parameter
+        self.slices = [(i, v.data_ptr(), v.numel()) for i, v in enumerate(self.views) if v.numel()] if self.flat.is_cuda else []
+        self.chunks = sum(_chunks(n) for _, _, n in self.slices)
 
 
 class GradientSync:
@@ -285,8 +279,8 @@ class GradientSync:
         """One ``zsv_grad_accum_multi`` launch on the current (side) stream: every slice of the bucket = [itself +] scale * its
         gradient.  The gradients are fresh allocations every pass, so the table is built and uploaded per launch."""
         dev = b.flat.device
-        entries, keep = [], []
-        for i, acc, n, first in b.slices:
+        rows, keep = [], []
+        for i, acc, n in b.slices:
             g = grads[i]
             if g is None or not g.is_cuda or g.dtype != torch.float32 or b.flat.dtype != torch.float32 or g.numel() != n:
                 raise RuntimeError("GradientSync: gradient accumulation needs dense fp32 gradients on the HIP device "
@@ -294,12 +288,13 @@ class GradientSync:
             if not g.is_contiguous():
                 g = g.contiguous()
                 keep.append(g)
-            entries.append(struct.pack("<QQqq", acc, g.data_ptr(), n, first))
-        if not entries:
+            rows.append((acc, g.data_ptr(), n))
+        if not rows:
             return
+        raw, chunks = pack_rows(rows)
         with torch.cuda.device(dev):
-            table = self._ring.upload(bytearray(b"".join(entries)), dev)
-            _lib.check(_lib.load().zsv_grad_accum_multi(table.data_ptr(), len(entries), b.chunks, float(scale), int(bool(assign)),
+            table = self._ring.upload(raw, dev)
+            _lib.check(_lib.load().zsv_grad_accum_multi(table.data_ptr(), len(rows), chunks, float(scale), int(bool(assign)),
                                                         c_void_p(torch.cuda.current_stream().cuda_stream)),
                        "zsv_grad_accum_multi")
         del keep, table                            # allocated on this stream: reused only behind the launch

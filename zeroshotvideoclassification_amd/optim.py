@@ -40,15 +40,17 @@ Fine-tuning options (csrc/optim.hip), all off by default -- with ``weight_decay 
 No floating-point atomics: the same gradients give the same norm bits and the same parameter bits on every run.
 
 ``WeightAverage(optimizer, decay=)`` keeps an exponential moving average (``decay=None``: an equal-weight running mean, SWA) of
-every parameter of a ``FusedAdam`` -- ``torch.optim.swa_utils.AveragedModel`` folded into the optimizer's own launch: the
-``*_avg`` forms of the four update kernels apply the average with the new parameter value still in a register, the count of
-averaged steps is device state (a step the scaler skips averages nothing, and the host never learns which it was), and
-``applied()`` swaps the averaged values INTO the live tensors for evaluation.  Without a ``WeightAverage`` the step launches
-what it always did.
+every parameter of a ``FusedAdam`` or ``FusedSGD`` -- ``torch.optim.swa_utils.AveragedModel`` folded into the optimizer's own
+launch: the ``*_avg`` entry points (the same kernel with the average compiled in, csrc/optim.hip) apply it with the new parameter
+value still in a register, the count of averaged steps is device state (a step the scaler skips averages nothing, and the host
+never learns which it was), and ``applied()`` swaps the averaged values INTO the live tensors for evaluation.  Without a
+``WeightAverage`` the step launches what it always did.
 
 ``FusedSGD`` is ``torch.optim.SGD`` -- momentum, dampening, Nesterov, L2 weight decay, ``maximize``, the recipe torchvision trained
 these trunks with -- on the same machinery, which lives in ``_FusedOptimizer``, the base class of both: descriptor tables (per step
-or once per bucket layout, the momentum buffers then flat like the buckets), ``max_grad_norm``, ``LossScaler``, ``WeightAverage``.  One
+or once per bucket layout, the momentum buffers then flat like the buckets), ``max_grad_norm``, ``LossScaler``, ``WeightAverage`` and
+``step()`` itself (tables, the norm pass or the check for every group, then one update launch per group, the average's own
+launches, the host's bookkeeping); a subclass supplies the launch of one group (``_update``) and that bookkeeping.  One
 ``zsv_sgd_multi`` launch per parameter group (csrc/sgd.hip: 16 bytes per lane where a tensor's pointers allow it); clip record, scaler
 state and shadows are NULL-able arguments of that ONE entry point.  The state is torch's (``momentum_buffer``).  torch's first step
 copies the gradient into the new buffer; here the launch is told -- by the host, or under a scaler by the device-resident count of
@@ -65,7 +67,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._tables import CHUNK as _CHUNK, PinnedRing
+from ._tables import PinnedRing, pack_rows
 
 
 def _stream():
@@ -97,9 +99,10 @@ class LossScaler:
         return loss * self._scale.detach().reshape(())
 
     def step(self, optimizer) -> None:
-        """``scaler.step(optimizer)`` (main.py:200): unscale + non-finite check + (skipped-if-inf) Adam step."""
+        """``scaler.step(optimizer)`` (main.py:200): unscale + non-finite check + (skipped-if-inf) optimizer step."""
         if not isinstance(optimizer, _FusedOptimizer):
-            raise RuntimeError("LossScaler.step drives optim.FusedAdam (the check, unscale and skip run inside its kernels)")
+            raise RuntimeError("LossScaler.step drives optim.FusedAdam or optim.FusedSGD "
+                               "(the check, unscale and skip run inside their kernels)")
         optimizer.step(scaler=self)
 
     def unscale_(self, optimizer) -> None:
@@ -109,7 +112,7 @@ class LossScaler:
         ``scaler.unscale_(opt); torch.nn.utils.clip_grad_norm_(...); scaler.step(opt)``; ``FusedAdam(max_grad_norm=)``
         is the fused route, which needs no ``unscale_``."""
         if not isinstance(optimizer, _FusedOptimizer):
-            raise RuntimeError("LossScaler.unscale_ drives optim.FusedAdam")
+            raise RuntimeError("LossScaler.unscale_ drives optim.FusedAdam or optim.FusedSGD")
         if id(optimizer) in self._unscaled:
             raise RuntimeError("unscale_() has already been called on this optimizer since the last update().")
         optimizer._unscale(self)
@@ -160,8 +163,9 @@ class LossScaler:
 class _FusedOptimizer(torch.optim.Optimizer):
     """What ``FusedAdam`` and ``FusedSGD`` share: the descriptor tables {p, g, state, state, n, first_chunk} -- rebuilt per step and
     uploaded through a pinned ring, or built once per layout over the flat gradient buckets -- the ``LossScaler`` they are driven
-    by, ``LossScaler.unscale_``, the norm pass of ``max_grad_norm`` and the ``WeightAverage`` that rides in their launches.  A
-    subclass names its per-parameter state tensors (``_state_keys``), creates them (``_entry_state``) and launches its update."""
+    by, ``LossScaler.unscale_``, the norm pass of ``max_grad_norm``, the ``WeightAverage`` that rides in their launches, and
+    ``step()``.  A subclass names its per-parameter state tensors (``_state_keys``), creates them (``_entry_state``), launches the
+    update of one group (``_update``) and keeps its own count of steps (``_after_step``)."""
 
     def _init_fused(self, max_grad_norm, grad_buckets):
         self.max_grad_norm = max_grad_norm
@@ -218,7 +222,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     def _dynamic_table(self, group):
         keys = self._state_keys(group)
-        entries, first, keep, live = [], 0, [], []
+        rows, keep, live = [], [], []
         for p in group["params"]:
             if p.grad is None:
                 continue
@@ -226,18 +230,16 @@ class _FusedOptimizer(torch.optim.Optimizer):
             g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
             st = self._entry_state(p, group)
             ptrs = [st[k].data_ptr() for k in keys] + [0] * (2 - len(keys))
-            n = p.numel()
-            entries.append((p.data_ptr(), g.data_ptr(), ptrs[0], ptrs[1], n, first))
+            rows.append((p.data_ptr(), g.data_ptr(), ptrs[0], ptrs[1], p.numel()))
             keep.append(g)
             live.append(p)
-            first += (n + _CHUNK - 1) // _CHUNK
-        if not entries:
+        if not rows:
             return None
-        raw = bytearray(b"".join(struct.pack("<QQQQqq", *e) for e in entries))
+        raw, chunks = pack_rows(rows)
         if self._average is not None:
             raw += self._average._shadow_pointers(live)   # the shadow-pointer array rides behind the table (_avg_args)
         table = self._upload(raw, keep[0].device)
-        return table, len(entries), first, keep
+        return table, len(rows), chunks, keep
 
     def _static_table(self, group):
         """Table over the flat gradient buckets, built once per bucket layout; None when it does not apply this
@@ -248,13 +250,13 @@ class _FusedOptimizer(torch.optim.Optimizer):
         if self._static is None or self._static[0] != sync.layout_version:
             keys = self._state_keys(group)
             mine = {id(p) for p in group["params"]}
-            entries, first, expect, flats = [], 0, [], []
-            for flat, rows in sync.bucket_layout():
+            rows, expect, flats = [], [], []
+            for flat, slices in sync.bucket_layout():
                 if not flat.is_cuda:
                     return None
                 state_flats = tuple(torch.zeros_like(flat) for _ in keys)
                 flats.append(state_flats)
-                for p, off in rows:
+                for p, off in slices:
                     if id(p) not in mine:
                         raise RuntimeError(f"{type(self).__name__}: a bucketed parameter is not in this optimizer")
                     self._check_param(p)
@@ -263,15 +265,14 @@ class _FusedOptimizer(torch.optim.Optimizer):
                     self._rehome(self.state[p], keys, views)      # state from the discovery step(s) moves into the flat buffers
                     ptrs = [v.data_ptr() for v in views] + [0] * (2 - len(keys))
                     gptr = flat.data_ptr() + 4 * off
-                    entries.append((p.data_ptr(), gptr, ptrs[0], ptrs[1], n, first))
+                    rows.append((p.data_ptr(), gptr, ptrs[0], ptrs[1], n))
                     expect.append((p, gptr))
-                    first += (n + _CHUNK - 1) // _CHUNK
-            raw = bytearray(b"".join(struct.pack("<QQQQqq", *e) for e in entries))
+            raw, chunks = pack_rows(rows)
             if self._average is not None:
                 raw += self._average._shadow_pointers([p for p, _ in expect])       # once per layout, like the table
             dev = expect[0][0].device
             table = torch.frombuffer(raw, dtype=torch.uint8).to(dev)          # once per layout: a blocking copy is fine
-            self._static = (sync.layout_version, table, len(entries), first, expect, flats)
+            self._static = (sync.layout_version, table, len(rows), chunks, expect, flats)
         _, table, count, chunks, expect, _ = self._static
         bucketed = {id(p) for p, _ in expect}
         for p, gptr in expect:
@@ -354,6 +355,51 @@ class _FusedOptimizer(torch.optim.Optimizer):
                                "zsv_grad_check_multi")
         return clip_ptr
 
+    # -- step -------------------------------------------------------------------------------------
+    def _check_groups(self) -> None:
+        """Raise on a group option the update rule cannot take (the groups are editable between steps)."""
+
+    def _update(self, lib, scaler: Optional[LossScaler], unscaled: bool, clip_ptr):
+        """Decide once what this step's launches share and return ``launch(group, table, count, chunks)``, which launches the
+        update of one parameter group on the current stream."""
+        raise NotImplementedError
+
+    def _after_step(self, scaler: Optional[LossScaler]) -> None:
+        """Host bookkeeping after the launches of a step (under a scaler the host does not know whether it was taken)."""
+
+    @torch.no_grad()
+    def step(self, closure=None, scaler: Optional[LossScaler] = None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._adopt(scaler)
+        lib = _lib.load()
+        avg = self._average
+        if avg is not None:
+            avg._check_live()
+        self._check_groups()
+        work = self._tables()
+        if not work:
+            return loss
+        unscaled = scaler is not None and id(self) in scaler._unscaled      # LossScaler.unscale_ has run on these gradients
+        # GradScaler.step checks EVERY gradient before the optimizer touches anything (an inf in the last group must skip the first
+        # group's update too): the norm pass or the check, all groups first
+        clip_ptr = self._norm_pass(lib, work, scaler, unscaled)
+        launch = self._update(lib, scaler, unscaled, clip_ptr)
+        for group, (table, count, chunks, keep) in work:
+            with torch.cuda.device(table.device):
+                launch(group, table, count, chunks)
+            # keep the uploaded table and any contiguous gradient copies alive until the stream is past the launch
+            table.record_stream(torch.cuda.current_stream())
+            del keep
+        del work
+        if avg is not None:
+            avg._after_update(lib, scaler)         # BatchNorm statistics, then n_averaged += !found_inf (before scaler.update())
+        self._after_step(scaler)
+        _lib.note_raw_write()                      # parameters updated through raw pointers
+        return loss
+
 
 class FusedAdam(_FusedOptimizer):
     """``torch.optim.Adam`` / ``torch.optim.AdamW`` in one launch per parameter group (module docstring).
@@ -412,63 +458,38 @@ class FusedAdam(_FusedOptimizer):
             st[k] = v
 
     # -- step -------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def step(self, closure=None, scaler: Optional[LossScaler] = None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._adopt(scaler)
-        lib = _lib.load()
-        launched = False
-        avg = self._average
-        if avg is not None:
-            avg._check_live()
-        work = self._tables()
-        unscaled = scaler is not None and id(self) in scaler._unscaled      # LossScaler.unscale_ has run on these gradients
-        if self.max_grad_norm is not None or unscaled or any(g["weight_decay"] != 0 for g in self.param_groups):
-            launched = self._step_decay_clip(lib, work, scaler, unscaled)
-            work = []
-        elif scaler is not None:
-            # GradScaler.step checks EVERY gradient before the optimizer touches anything: an inf in the last group must
-            # skip the first group's update too
-            for _, (table, count, chunks, _keep) in work:
-                with torch.cuda.device(table.device):
-                    _lib.check(lib.zsv_grad_check_multi(table.data_ptr(), count, chunks, scaler.state_ptr, _stream()),
-                               "zsv_grad_check_multi")
-        for group, (table, count, chunks, keep) in work:
-            lr, (b1, b2), eps = float(group["lr"]), group["betas"], float(group["eps"])
-            with torch.cuda.device(table.device):
-                if avg is not None and scaler is not None:
-                    _lib.check(lib.zsv_adam_multi_scaled_avg(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps,
-                                                             scaler.state_ptr, *self._avg_args(table, count), _stream()),
-                               "zsv_adam_multi_scaled_avg")
-                elif avg is not None:
-                    _lib.check(lib.zsv_adam_multi_avg(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps,
-                                                      self._host_steps + 1, *self._avg_args(table, count), _stream()),
-                               "zsv_adam_multi_avg")
-                elif scaler is not None:
-                    _lib.check(lib.zsv_adam_multi_scaled(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps,
-                                                         scaler.state_ptr, _stream()), "zsv_adam_multi_scaled")
-                else:
-                    _lib.check(lib.zsv_adam_multi(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps,
-                                                  self._host_steps + 1, _stream()), "zsv_adam_multi")
-            # keep the uploaded table and any contiguous gradient copies alive until the stream is past the launch
-            table.record_stream(torch.cuda.current_stream())
-            del keep
-            launched = True
-        del work
-        if launched:
-            if avg is not None:
-                avg._after_update(lib, scaler)     # BatchNorm statistics, then n_averaged += !found_inf (before scaler.update())
-            if scaler is None:
-                self._host_steps += 1
-                for group in self.param_groups:
-                    for p in group["params"]:
-                        if p.grad is not None:
-                            self.state[p]["step"] += 1
-            _lib.note_raw_write()                  # parameters updated through raw pointers
-        return loss
+    def _update(self, lib, scaler, unscaled, clip_ptr):
+        """One of the eight ``zsv_adam[w]_multi[_scaled][_avg]`` entry points, picked once per step.  The ``adamw`` forms run when
+        anything needs them -- clipping, gradients ``unscale_`` has already rewritten, decay in any group -- and then for every
+        group, one with ``weight_decay == 0`` included."""
+        decay_clip = self.max_grad_norm is not None or unscaled or any(g["weight_decay"] != 0 for g in self.param_groups)
+        scaled, averaged = scaler is not None, self._average is not None
+        name = "zsv_adam" + ("w" if decay_clip else "") + "_multi" + ("_scaled" if scaled else "") + ("_avg" if averaged else "")
+        entry = getattr(lib, name)
+
+        def launch(group, table, count, chunks):
+            b1, b2 = group["betas"]
+            args = [table.data_ptr(), count, chunks, float(group["lr"]), float(b1), float(b2), float(group["eps"])]
+            if decay_clip:
+                wd = float(group["weight_decay"])
+                self._check_decay(wd)
+                args += [wd, int(bool(group["decoupled_weight_decay"])), clip_ptr]
+            if scaled:                                 # the step number is the scaler's device-resident count
+                args += [scaler.state_ptr, int(unscaled)] if decay_clip else [scaler.state_ptr]
+            else:
+                args += [self._host_steps + 1]
+            if averaged:
+                args += self._avg_args(table, count)
+            _lib.check(entry(*args, _stream()), name)
+        return launch
+
+    def _after_step(self, scaler):
+        if scaler is None:
+            self._host_steps += 1
+            for group in self.param_groups:
+                for p in group["params"]:
+                    if p.grad is not None:
+                        self.state[p]["step"] += 1
 
     def _on_adopt(self, scaler: LossScaler) -> None:
         if self._host_steps:
@@ -481,37 +502,6 @@ class FusedAdam(_FusedOptimizer):
                 scaler._seed_steps_done(self._host_steps)
             elif scaler.state()["steps_done"] != self._host_steps:
                 raise RuntimeError("FusedAdam: the loaded optimizer and scaler states disagree on the steps taken")
-
-    def _step_decay_clip(self, lib, work, scaler: Optional[LossScaler], unscaled: bool) -> bool:
-        """The step with weight decay and / or clipping: [norm pass per group, finalize,] one update launch per group."""
-        if not work:
-            return False
-        state_ptr = scaler.state_ptr if scaler is not None else None
-        clip_ptr = self._norm_pass(lib, work, scaler, unscaled)
-        for group, (table, count, chunks, keep) in work:
-            lr, (b1, b2), eps = float(group["lr"]), group["betas"], float(group["eps"])
-            wd, decoupled = float(group["weight_decay"]), int(bool(group["decoupled_weight_decay"]))
-            self._check_decay(wd)
-            with torch.cuda.device(table.device):
-                if self._average is not None and scaler is not None:
-                    _lib.check(lib.zsv_adamw_multi_scaled_avg(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps, wd,
-                                                              decoupled, clip_ptr, state_ptr, int(unscaled),
-                                                              *self._avg_args(table, count), _stream()),
-                               "zsv_adamw_multi_scaled_avg")
-                elif self._average is not None:
-                    _lib.check(lib.zsv_adamw_multi_avg(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps, wd,
-                                                       decoupled, clip_ptr, self._host_steps + 1,
-                                                       *self._avg_args(table, count), _stream()), "zsv_adamw_multi_avg")
-                elif scaler is not None:
-                    _lib.check(lib.zsv_adamw_multi_scaled(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps, wd,
-                                                          decoupled, clip_ptr, state_ptr, int(unscaled), _stream()),
-                               "zsv_adamw_multi_scaled")
-                else:
-                    _lib.check(lib.zsv_adamw_multi(table.data_ptr(), count, chunks, lr, float(b1), float(b2), eps, wd,
-                                                   decoupled, clip_ptr, self._host_steps + 1, _stream()), "zsv_adamw_multi")
-            table.record_stream(torch.cuda.current_stream())
-            del keep
-        return True
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -621,46 +611,27 @@ class FusedSGD(_FusedOptimizer):
             self._first_at = -1
 
     # -- step -------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def step(self, closure=None, scaler: Optional[LossScaler] = None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._adopt(scaler)
-        lib = _lib.load()
-        avg = self._average
-        if avg is not None:
-            avg._check_live()
+    def _check_groups(self):
         for group in self.param_groups:
             self._check_group(group)
-        work = self._tables()
-        if not work:
-            return loss
-        unscaled = scaler is not None and id(self) in scaler._unscaled      # LossScaler.unscale_ has run on these gradients
+
+    def _update(self, lib, scaler, unscaled, clip_ptr):
         state_ptr = scaler.state_ptr if scaler is not None else None
-        # GradScaler.step checks EVERY gradient before the optimizer touches anything: the norm pass or the check, all groups first
-        clip_ptr = self._norm_pass(lib, work, scaler, unscaled)
         if scaler is not None:
             first_step = self._first_at
         else:
             first_step = -1 if self._started else 0
-        for group, (table, count, chunks, keep) in work:
-            shadows, avg_state, ema_weight = self._avg_args(table, count) if avg is not None else (None, None, 0.0)
-            with torch.cuda.device(table.device):
-                _lib.check(lib.zsv_sgd_multi(table.data_ptr(), count, chunks, float(group["lr"]), float(group["momentum"]),
-                                             float(group["dampening"]), int(bool(group["nesterov"])), float(group["weight_decay"]),
-                                             int(bool(group["maximize"])), clip_ptr, state_ptr, int(unscaled), first_step,
-                                             shadows, avg_state, ema_weight, _stream()), "zsv_sgd_multi")
-            # keep the uploaded table and any contiguous gradient copies alive until the stream is past the launch
-            table.record_stream(torch.cuda.current_stream())
-            del keep
-        del work
-        if avg is not None:
-            avg._after_update(lib, scaler)         # BatchNorm statistics, then n_averaged += !found_inf (before scaler.update())
+
+        def launch(group, table, count, chunks):
+            shadows, avg_state, ema_weight = self._avg_args(table, count) if self._average is not None else (None, None, 0.0)
+            _lib.check(lib.zsv_sgd_multi(table.data_ptr(), count, chunks, float(group["lr"]), float(group["momentum"]),
+                                         float(group["dampening"]), int(bool(group["nesterov"])), float(group["weight_decay"]),
+                                         int(bool(group["maximize"])), clip_ptr, state_ptr, int(unscaled), first_step,
+                                         shadows, avg_state, ema_weight, _stream()), "zsv_sgd_multi")
+        return launch
+
+    def _after_step(self, scaler):
         self._started = True
-        _lib.note_raw_write()                      # parameters updated through raw pointers
-        return loss
 
     # -- state ------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict):
@@ -709,7 +680,8 @@ class WeightAverage:
 
     def __init__(self, optimizer, decay: Optional[float] = 0.999, model: Optional[torch.nn.Module] = None, buffers: bool = True):
         if not isinstance(optimizer, _FusedOptimizer):
-            raise TypeError("WeightAverage averages inside optim.FusedAdam's update launch; got " + type(optimizer).__name__)
+            raise TypeError("WeightAverage averages inside optim.FusedAdam's update launch; got " + type(optimizer).__name__
+                            + " (it takes an optim.FusedAdam or an optim.FusedSGD)")
         if decay is not None:
             if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not (0.0 <= decay < 1.0):
                 raise ValueError(f"decay must be None (equal-weight) or a number in [0, 1), not {decay!r}")
@@ -772,7 +744,7 @@ class WeightAverage:
         """``{key: averaged tensor}``: views of the flat buffer(s), keyed like ``state_dict()['shadows']``."""
         return {k: shadow for k, _, shadow in self._entries}
 
-    # -- what FusedAdam.step calls ------------------------------------------------------------------
+    # -- what the optimizer's step calls ----------------------------------------------------------------
     def _state_ptr(self, dev) -> int:
         return self._state[dev].data_ptr()
 
@@ -795,13 +767,11 @@ class WeightAverage:
         ptrs = tuple(t.data_ptr() for t, _ in rows)
         cached = self._pair_tables.get((dev, buffers_only))
         if cached is None or cached[0] != ptrs:
-            raw, first = bytearray(), 0
             for t, shadow in rows:
                 if t.device != shadow.device or t.numel() != shadow.numel() or not t.is_contiguous():
                     raise RuntimeError("WeightAverage: a shadowed tensor changed its device, size or layout")
-                raw += struct.pack("<QQqq", t.data_ptr(), shadow.data_ptr(), t.numel(), first)
-                first += (t.numel() + _CHUNK - 1) // _CHUNK
-            cached = (ptrs, torch.frombuffer(raw, dtype=torch.uint8).to(dev), len(rows), first)
+            raw, chunks = pack_rows([(t.data_ptr(), shadow.data_ptr(), t.numel()) for t, shadow in rows])
+            cached = (ptrs, torch.frombuffer(raw, dtype=torch.uint8).to(dev), len(rows), chunks)
             self._pair_tables[(dev, buffers_only)] = cached
         return cached[1:]
 
