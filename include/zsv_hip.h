@@ -300,6 +300,27 @@ int zsv_conv3d_bf16_pack(const zsv_conv_desc* d, const float* w, const float* sc
  * padding k-1-p -- and `w_fwd` is the FORWARD weight (forward Cout, forward Cin, kT, kH, kW) as the module holds it: channel
  * roles are swapped and the taps flipped while packing (aten::convolution_backward's input gradient, resnet.py:40-52). */
 int zsv_conv3d_bf16_pack_dgrad(const zsv_conv_desc* d, const float* w_fwd, void* blob, void* stream);
+/* Input gradient of a bf16 convolution (aten::convolution_backward's grad_input; resnet.py:40-52 the (2+1)D pairs, resnet.py:23-30
+ * 3x3x3, resnet.py:266-273 the strided 1x1x1 shortcut), ANY stride with sT*sH*sW <= 8, in ONE convolution launch.  `d` is the FORWARD
+ * descriptor.  dz is [N][To][Ho][Wo][pitch(Cout)], dx and `fanin` are [N][Ti][Hi][Wi][pitch(Cin)], channels-last bf16; pad channels
+ * of dx are written zero (fanin's are zero by its layout); no workspace, nothing allocates.
+ *   zsv_conv3d_bf16_dgrad_blob_bytes: bytes of the packed weights; 0 = unsupported geometry (the folded clip form Cin <= 4, more
+ *     than 8 residue classes, more than 32 taps in a class, padding > kernel - 1); for stride (1,1,1) it is
+ *     zsv_conv3d_bf16_blob_bytes of the stride-1 input-gradient problem and the blob is zsv_conv3d_bf16_pack_dgrad's.
+ *   zsv_conv3d_bf16_dgrad_pack: one launch; reads the FORWARD weight (Cout, Cin, kT, kH, kW) as the module holds it and writes, for
+ *     every residue class (rho_t, rho_h, rho_w) of the input positions i = s*j + rho, the sub-weight of the taps r + s*m,
+ *     r = (rho + p) mod s, channel roles swapped and taps flipped.
+ *   zsv_conv3d_bf16_dgrad: one launch whose grid is the column tiles of all classes; a class no tap reaches (7 of the 8 classes of the
+ *     1x1x1 stride-2 shortcut, the remainder rows / columns of odd extents) stores zero; every element of dx is written exactly
+ *     once.  `fanin` (may be NULL, may equal dx): dx = bf16( float(bf16(acc)) + float(fanin) ) -- the gradient is rounded to bf16
+ *     first and the fan-in added to that, exactly what an element-wise bf16 add of the two tensors gives (the residual joins of
+ *     resnet.py:110-111's backward); zsv_conv3d_bf16_fwd's `residual` adds BEFORE the rounding and is unchanged.  Stride (1,1,1)
+ *     runs zsv_conv3d_bf16_fwd's kernels on the stride-1 problem.
+ * ZSV_E_NULL for a NULL d / w_fwd / blob / dz / dx, ZSV_E_UNSUPPORTED where blob_bytes is 0 for a valid descriptor; all before
+ * any launch. */
+size_t zsv_conv3d_bf16_dgrad_blob_bytes(const zsv_conv_desc* d);
+int zsv_conv3d_bf16_dgrad_pack(const zsv_conv_desc* d, const float* w_fwd, void* blob, void* stream);
+int zsv_conv3d_bf16_dgrad(const zsv_conv_desc* d, const void* dz, const void* blob, const void* fanin, void* dx, void* stream);
 int zsv_conv3d_bf16_fwd(const zsv_conv_desc* d, const void* x, const void* blob, const void* residual,
                         int fuse_relu, void* y, void* stream);
 /* The same forward in front of a training-mode BatchNorm (no residual, no ReLU) with the BatchNorm's batch statistics taken in the

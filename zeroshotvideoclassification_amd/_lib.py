@@ -84,6 +84,9 @@ SIGNATURES = {
     "zsv_conv3d_bf16_blob_bytes": (c_size_t, [POINTER(ConvDesc)]),
     "zsv_conv3d_bf16_pack": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "zsv_conv3d_bf16_pack_dgrad": (c_int, [POINTER(ConvDesc), _P, _P, _P]),
+    "zsv_conv3d_bf16_dgrad_blob_bytes": (c_size_t, [POINTER(ConvDesc)]),
+    "zsv_conv3d_bf16_dgrad_pack": (c_int, [POINTER(ConvDesc), _P, _P, _P]),
+    "zsv_conv3d_bf16_dgrad": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "zsv_conv3d_bf16_fwd": (c_int, [POINTER(ConvDesc), _P, _P, _P, c_int, _P, _P]),
     "zsv_clip_to_bf16": (c_int, [_P] + [c_int32] * 9 + [_P, _P]),
     "zsv_maxpool3d_bf16": (c_int, [_P] + [c_int32] * 14 + [_P, _P]),

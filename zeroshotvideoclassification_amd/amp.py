@@ -378,12 +378,43 @@ class Bf16TrainPath:
         return conv_bf16(d2, dz, blob, None, False)
 
     @staticmethod
-    def _dgrad(r: _Record, dz: torch.Tensor) -> torch.Tensor:
-        """Input gradient of the unit's convolution on the FORWARD kernel: a stride-1 convolution of the output gradient with the
-        transposed, tap-flipped weights.  A strided convolution splits into one such problem per residue class of the input
-        positions (stride (1,2,2): four classes with 1 / 2 / 2 / 4 of the nine taps on the compact output grid -- exactly the
-        forward's multiply count, where a zero-interleaved output gradient would cost four times as much); the class results
-        are interleaved into the input gradient."""
+    def _dgrad(r: _Record, dz: torch.Tensor, fanin: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Input gradient of the unit's convolution, any stride: one weight-pack launch and one convolution launch
+        (``zsv_conv3d_bf16_dgrad``: the residue classes of a strided convolution are column tiles of one grid, each column stored
+        at its strided input coordinate; stride 1 runs the forward kernels on the stride-1 problem).  ``fanin`` (the other
+        gradient arriving at this tensor -- the residual branch's) is added in the epilogue to the bf16-ROUNDED gradient: the bits
+        of ``_dgrad(r, dz) + fanin``.  ``out`` (may be ``fanin`` itself: accumulate in place) receives the result.  A geometry
+        the entry point does not take (``zsv_conv3d_bf16_dgrad_blob_bytes`` == 0) goes through ``_dgrad_composed``."""
+        u, d = r.unit, r.desc
+        lib = _lib.load()
+        nbytes = 0 if u.folded else int(lib.zsv_conv3d_bf16_dgrad_blob_bytes(byref(d)))
+        if nbytes == 0:
+            dx = Bf16TrainPath._dgrad_composed(r, dz)
+            if fanin is None:
+                return dx
+            return torch.add(dx, fanin, out=out)
+        w = u.conv.weight.detach().contiguous()
+        blob = torch.empty(nbytes, dtype=torch.uint8, device=dz.device)
+        _lib.check(lib.zsv_conv3d_bf16_dgrad_pack(byref(d), w.data_ptr(), blob.data_ptr(), ops._stream()), "zsv_conv3d_bf16_dgrad_pack")
+        shape = (d.N, d.Ti, d.Hi, d.Wi, channel_pitch(u.cin))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.bfloat16, device=dz.device)
+        if tuple(out.shape) != shape or out.dtype != torch.bfloat16 or not out.is_contiguous():
+            raise RuntimeError(f"amp: the input gradient is a contiguous bf16 {shape} tensor")
+        if fanin is not None and (tuple(fanin.shape) != shape or fanin.dtype != torch.bfloat16 or not fanin.is_contiguous()):
+            raise RuntimeError(f"amp: the fan-in of an input gradient is a contiguous bf16 {shape} tensor")
+        _lib.check(lib.zsv_conv3d_bf16_dgrad(byref(d), dz.data_ptr(), blob.data_ptr(), ops._ptr(fanin), out.data_ptr(), ops._stream()),
+                   "zsv_conv3d_bf16_dgrad")
+        return out
+
+    @staticmethod
+    def _dgrad_composed(r: _Record, dz: torch.Tensor) -> torch.Tensor:
+        """The same input gradient composed from the FORWARD kernel per residue class (what ``_dgrad`` was before
+        ``zsv_conv3d_bf16_dgrad``; its fallback, and the comparison of tests/test_bf16_dgrad_gpu.py): a stride-1 convolution of
+        the output gradient with the transposed, tap-flipped weights.  A strided convolution splits into one such problem per
+        residue class of the input positions (stride (1,2,2): four classes with 1 / 2 / 2 / 4 of the nine taps on the compact
+        output grid -- exactly the forward's multiply count, where a zero-interleaved output gradient would cost four times as
+        much); the class results are interleaved into the input gradient with torch copies."""
         u, d = r.unit, r.desc
         w = u.conv.weight.detach()
         axes = [Bf16TrainPath._axis_classes(k, p, s, n_in, n_out) for k, p, s, n_in, n_out in
@@ -452,7 +483,9 @@ class Bf16TrainPath:
         grads = {}
         idx = len(tape) - 1
 
-        def unit_bwd(dy, want_g=False, need_dx=True):
+        def unit_bwd(dy, want_g=False, need_dx=True, fanin=None, defer=False):
+            """``fanin``: added to the input gradient in the convolution's epilogue.  ``defer``: (record, dz) is returned in
+            place of the input gradient, for a ``_dgrad`` that accumulates into a tensor not written yet."""
             nonlocal idx
             r = tape[idx]
             idx -= 1
@@ -469,20 +502,24 @@ class Bf16TrainPath:
                 grads[id(u.bn.bias)] = dbeta
             if need_weight_grads and u.conv.weight.requires_grad:
                 grads[id(u.conv.weight)] = self._wgrad(r, dz)
-            dx = self._dgrad(r, dz) if need_dx else None
+            if defer:
+                return (r, dz), g, r
+            dx = self._dgrad(r, dz, fanin) if need_dx else None
             return dx, g, r
 
         dx = dfeat
         for conv1, conv2, down in reversed(self.blocks):
             # tail unit: BatchNorm + residual + ReLU -- the masked gradient is also the residual branch's gradient
             dy, g, r_tail = unit_bwd(dx, want_g=True)
-            for _ in range(len(conv1) + len(conv2) - 1):
+            for _ in range(len(conv1) + len(conv2) - 2):
                 dy, _, _ = unit_bwd(dy)
+            # the block's first convolution: the two gradients of the block's input meet in its input gradient's epilogue
             if down is not None:
-                dxd, _, _ = unit_bwd(g)
-                dx = dy + dxd
+                (r_first, dz_first), _, _ = unit_bwd(dy, defer=True)
+                dx, _, _ = unit_bwd(g)                               # the shortcut's input gradient writes dx ...
+                dx = self._dgrad(r_first, dz_first, fanin=dx, out=dx)    # ... and the first convolution's accumulates into it
             else:
-                dx = dy + g
+                dx, _, _ = unit_bwd(dy, fanin=g)
         for i in range(len(self.stem) - 1, -1, -1):
             dx, _, _ = unit_bwd(dx, need_dx=(i > 0))
         assert idx == -1

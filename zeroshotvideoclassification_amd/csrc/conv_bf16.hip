@@ -56,6 +56,7 @@ struct Bf16Params {
     int P;                     // output voxels N*To*Ho*Wo
     int tiles_m, tiles_n;
     int relu;
+    int res_rounded;           // residual added AFTER the rounding to bf16 (the input gradient's fan-in), not before it
     int cc_outer;              // shared-image kernel: walk the K chunks outermost (image rows of one chunk stay in L2 across the kh groups)
     float* stat;               // != nullptr: per column tile the sums and sums of squares of the STORED (bf16-rounded) values, [tiles_n][2][CoutP]
 };
@@ -172,11 +173,14 @@ __device__ __forceinline__ void mfma_step(f32x4 (&acc)[TM][TN], unsigned sa, uns
 // the values as STORED (rounded to bf16 -- what the BatchNorm's own statistics pass would read back) go to
 // stat[tn][0 / 1][m0 + channel]: in-lane over the wave's column blocks, 16-lane DPP sums over a block's columns, the waves of a row
 // through `scratch` (the stage area of LDS, free after the K loop) in wave order -- fixed order, reproducible.
-template <int TM, int TN, int BM, int BN>
-__device__ __forceinline__ void epilogue(const Bf16Params& prm, f32x4 (&acc)[TM][TN], const float* sh,
-                                         const __bf16* __restrict__ R, __bf16* __restrict__ Y, int m0, int n0, int tm,
-                                         int wm, int wn, int tid, int hb_shift = 0, int frame_stride = 0, float* scratch = nullptr,
-                                         int tn = 0, int wgn = 4) {
+// prm.res_rounded (the input gradient's fan-in, zsv_conv3d_bf16_dgrad): the value is rounded to bf16 FIRST and the residual added
+// to that, y = bf16(float(bf16(acc + shift)) + residual) -- what an element-wise bf16 add of the stored result and the residual gives.
+// epilogue_at: `voxel(c)` = the output row of tile column c (>= prm.P: the column stores nothing); R may be Y (every element is
+// read and written by the same lane).
+template <int TM, int TN, int BM, int BN, class VoxelFn>
+__device__ __forceinline__ void epilogue_at(const Bf16Params& prm, f32x4 (&acc)[TM][TN], const float* sh,
+                                            const __bf16* __restrict__ R, __bf16* __restrict__ Y, int m0, const VoxelFn& voxel, int tm,
+                                            int wm, int wn, int tid, float* scratch, int tn, int wgn) {
     const int lane = tid & 63;
     const bool stats = prm.stat != nullptr;
     float ssum[TM][4], ssq[TM][4];
@@ -184,11 +188,11 @@ __device__ __forceinline__ void epilogue(const Bf16Params& prm, f32x4 (&acc)[TM]
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) ssum[i][e] = ssq[i][e] = 0.f;
-    auto voxel = [&](int c) { return hb_shift ? n0 + (c >> hb_shift) * frame_stride + (c & ((1 << hb_shift) - 1)) : n0 + c; };
     const float floor_ = prm.relu ? 0.f : -__builtin_inff();
     const int g = lane >> 4;
     const int ch_t = wm * TM * 16;                   // this wave's first channel inside the row tile
     constexpr int NPAIR = TM / 2;
+    const bool rounded = prm.res_rounded != 0;
     auto finish = [&](auto has_res) {
         constexpr bool HAS_RES = decltype(has_res)::value;
 #pragma unroll
@@ -214,7 +218,14 @@ __device__ __forceinline__ void epilogue(const Bf16Params& prm, f32x4 (&acc)[TM]
                 const int ch = ch_t + 32 * k + 8 * g;
                 f32x4 lo = acc[2 * k][j] + *(const f32x4*)(sh + ch);
                 f32x4 hi = acc[2 * k + 1][j] + *(const f32x4*)(sh + ch + 4);
-                if (HAS_RES) add_bf16x8(lo, hi, res[k]);
+                if (HAS_RES) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {      // (a select, not a branch: the two modes share one schedule)
+                        lo[e] = rounded ? (float)(__bf16)fmaxf(lo[e], floor_) : lo[e];
+                        hi[e] = rounded ? (float)(__bf16)fmaxf(hi[e], floor_) : hi[e];
+                    }
+                    add_bf16x8(lo, hi, res[k]);
+                }
                 bf16x8 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -235,6 +246,8 @@ __device__ __forceinline__ void epilogue(const Bf16Params& prm, f32x4 (&acc)[TM]
                 const int ch = ch_t + 16 * (TM - 1) + 4 * g;
                 f32x4 v = acc[TM - 1][j] + *(const f32x4*)(sh + ch);
                 if (HAS_RES) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = rounded ? (float)(__bf16)fmaxf(v[e], floor_) : v[e];
                     v[0] += __builtin_bit_cast(float, res_odd[0] << 16);
                     v[1] += __builtin_bit_cast(float, res_odd[0] & 0xffff0000u);
                     v[2] += __builtin_bit_cast(float, res_odd[1] << 16);
@@ -304,6 +317,15 @@ __device__ __forceinline__ void epilogue(const Bf16Params& prm, f32x4 (&acc)[TM]
             out[prm.CoutP] = 0.f;
         }
     }
+}
+
+template <int TM, int TN, int BM, int BN>
+__device__ __forceinline__ void epilogue(const Bf16Params& prm, f32x4 (&acc)[TM][TN], const float* sh,
+                                         const __bf16* __restrict__ R, __bf16* __restrict__ Y, int m0, int n0, int tm,
+                                         int wm, int wn, int tid, int hb_shift = 0, int frame_stride = 0, float* scratch = nullptr,
+                                         int tn = 0, int wgn = 4) {
+    auto voxel = [&](int c) { return hb_shift ? n0 + (c >> hb_shift) * frame_stride + (c & ((1 << hb_shift) - 1)) : n0 + c; };
+    epilogue_at<TM, TN, BM, BN>(prm, acc, sh, R, Y, m0, voxel, tm, wm, wn, tid, scratch, tn, wgn);
 }
 
 // Four floats -> four saturating e4m3 codes (byte e = value e).  v_cvt_pk_fp8_f32 rounds to nearest even; the caller clamps to
@@ -534,6 +556,196 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(Bf16Params prm, const
 
     if constexpr (IO::FP8_OUT) epilogue_fp8<TM, TN, BM, BN>(prm, acc, (const float*)(lds + SHIFT_AT), shift + prm.Mp, R, Y, m0, n0, tm, wm, wn, tid);
     else epilogue<TM, TN, BM, BN>(prm, acc, (const float*)(lds + SHIFT_AT), R, Y, m0, n0, tm, wm, wn, tid, 0, 0, (float*)lds, tn, WGN);
+#endif
+}
+
+// Input gradient of a STRIDED convolution, every residue class in one launch (zsv_conv3d_bf16_dgrad).  Input position
+// i = s*j + rho of an axis receives  sum_m w[r + s*m] * dz[j + c - m],  r = (rho + p) mod s, c = (rho + p - r) / s: per class
+// (rho_t, rho_h, rho_w) a stride-1 correlation of dz with the taps of that residue, flipped.  Rows = the forward's input channels,
+// K = class taps x the forward's output channels in chunks of 32, columns = the input positions of ONE class; the grid is the
+// column tiles of all classes one after the other, and a tile finds its class in the table below (kernel argument, at most
+// 8 classes).  The K loop is conv_bf16_kernel's (tap validity mask, zero line for taps outside dz), in the same (tap, chunk) order
+// as that kernel run per class, so the fp32 sums are the same numbers.  A class no tap reaches has no K chunks: its tiles stream
+// zero (or the fan-in) into their rows and leave.  Column -> dx row at the strided coordinate; every dx element is stored once.
+struct DgradClass {
+    short nT, nH, nW;          // taps of this class per axis; all three 0: no tap reaches the class
+    short oT, oH, oW;          // tap a of column j reads dz position j + o + a  (o = c - taps + 1)
+    short rT, rH, rW;          // rho: the column's input position is s*j + rho
+    short wT, wH, wW;          // r: tap a is forward tap r + s*(taps - 1 - a)  (the pack kernel)
+    int cT, cH, cW;            // input positions of the class per axis
+    int cols;                  // N * cT * cH * cW
+    int q0;                    // first K chunk of the class in the blob
+    int tile0;                 // first column tile of the class
+};
+struct DgradTable { DgradClass c[8]; };              // unused entries: q0 = tile0 = INT_MAX
+
+template <int TM, int TN, int WGM, int WGN>
+__global__ __launch_bounds__(256, 2) void conv_bf16_dgrad_kernel(Bf16Params prm, DgradTable tab, const __bf16* __restrict__ X,
+                                                                 const __bf16* __restrict__ Wp, const float* __restrict__ shift,
+                                                                 const __bf16* R, __bf16* Y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __bf16 In;
+    constexpr int CH = 32, EPS = 8;
+    static_assert(WGM * WGN == 4, "4 waves");
+    static_assert(WGM == 1 || (TM % 2) == 0, "row-block pairs must not straddle waves");
+    constexpr int BM = 16 * TM * WGM, BN = 16 * TN * WGN;
+    constexpr int NA_P = BM / 16, NB_P = BN / 16;
+    static_assert(NA_P >= 4 && NB_P % 4 == 0, "piece distribution");
+    constexpr int NAW = (NA_P + 3) / 4, NBW = NB_P / 4;
+    constexpr int NPW = NAW + NBW;
+    constexpr int STAGE = (BM + BN) * 64;
+    constexpr int SHIFT_AT = 3 * STAGE;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave % WGM, wn = wave / WGM;
+    const int tile = xcd_tile(gridDim.x, blockIdx.x);
+    const int tm = tile % prm.tiles_m, tn = tile / prm.tiles_m;
+    DgradClass cls = tab.c[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k)
+        if (tn >= tab.c[k].tile0) cls = tab.c[k];
+    const int m0 = tm * BM, n0 = (tn - cls.tile0) * BN;        // n0: first column of the tile INSIDE its class
+    const int cHW = cls.cH * cls.cW, cTHW = cls.cT * cHW;
+    const int nq = cls.nT * cls.nH * cls.nW * prm.nchunk;
+
+    // column c of the tile -> dx row ((n*Ti + sT*jt + rho_t)*Hi + sH*jh + rho_h)*Wi + sW*jw + rho_w  (prm.ToHoWo / HoWo / Wo hold
+    // dx's extents here, prm.P its rows)
+    auto voxel = [&](int c) {
+        const int p = n0 + c;
+        if (p >= cls.cols) return prm.P;
+        const int n = p / cTHW;
+        int rem = p - n * cTHW;
+        const int jt = rem / cHW;
+        rem -= jt * cHW;
+        const int jh = rem / cls.cW, jw = rem - jh * cls.cW;
+        return n * prm.ToHoWo + (prm.strT * jt + cls.rT) * prm.HoWo + (prm.strH * jh + cls.rH) * prm.Wo + prm.strW * jw + cls.rW;
+    };
+    if (nq == 0) {
+        // a class no tap reaches (uniform over the workgroup): its dx rows are zero, or bf16(0 + fan-in); no LDS, no barrier -- the
+        // tile's channels of every row as consecutive 16-byte pieces (the last row tile owns the channels up to the pitch)
+        const int ch_end = tm == prm.tiles_m - 1 ? prm.CoutP : min(m0 + BM, prm.CoutP);
+        const int ppc = (ch_end - m0) >> 3;
+        for (int idx = tid; idx < BN * ppc; idx += 256) {
+            const int c = idx / ppc, k = idx - c * ppc;
+            const int col = voxel(c);
+            if (col < prm.P) {
+                const size_t off = (size_t)col * prm.CoutP + m0 + 8 * k;
+                f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
+                if (R != nullptr) add_bf16x8(lo, hi, *(const u32x4*)(R + off));
+                bf16x8 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    o[e] = (__bf16)lo[e];
+                    o[4 + e] = (__bf16)hi[e];
+                }
+                *(bf16x8*)(Y + off) = o;
+            }
+        }
+        return;
+    }
+
+    const int srcslot = ((lane & 3) ^ swz(lane >> 2)) * EPS;
+    int a_off[NAW], a_dst[NAW];
+#pragma unroll
+    for (int k = 0; k < NAW; ++k) {
+        int pa = wave + 4 * k;
+        if (pa >= NA_P) pa -= 4;
+        a_off[k] = (pa * 16 + (lane >> 2)) * CH + srcslot;
+        a_dst[k] = pa * 1024;
+    }
+    int b_base[NBW], b_dst[NBW];
+    unsigned b_mask[NBW];                            // bit tap = the tap lies inside dz
+#pragma unroll
+    for (int k = 0; k < NBW; ++k) {
+        const int pb = wave + 4 * k;
+        const int p = n0 + pb * 16 + (lane >> 2);
+        b_dst[k] = BM * 64 + pb * 1024;
+        b_mask[k] = 0;
+        b_base[k] = 0;
+        if (p < cls.cols) {
+            const int n = p / cTHW;
+            int rem = p - n * cTHW;
+            const int jt = rem / cHW;
+            rem -= jt * cHW;
+            const int jh = rem / cls.cW, jw = rem - jh * cls.cW;
+            const int t0 = jt + cls.oT, h0 = jh + cls.oH, w0 = jw + cls.oW;
+            b_base[k] = (int)(n * prm.sN) + t0 * prm.sT + h0 * prm.sH + w0 * prm.sW + srcslot;
+            unsigned m = 0;
+            int tap = 0;
+            for (int a = 0; a < cls.nT; ++a)
+                for (int b = 0; b < cls.nH; ++b)
+                    for (int c = 0; c < cls.nW; ++c, ++tap)
+                        m |= (unsigned)((unsigned)(t0 + a) < (unsigned)prm.Ti && (unsigned)(h0 + b) < (unsigned)prm.Hi &&
+                                        (unsigned)(w0 + c) < (unsigned)prm.Wi) << tap;
+            b_mask[k] = m;
+        }
+    }
+    const In* wq = Wp + ((size_t)cls.q0 * prm.Mp + m0) * CH;    // chunk q of the class lives at + q*Mp*CH
+    const size_t wq_step = (size_t)prm.Mp * CH;
+    const In* zero = (const In*)zsv_zero_line;
+
+    int kt = 0, kh = 0, kw = 0, cc = 0, tap_i = 0;
+    auto issue = [&](int buf) {
+        unsigned char* base = lds + buf * STAGE;
+        const int tapoff = kt * prm.sT + kh * prm.sH + kw * prm.sW + cc * CH;
+#pragma unroll
+        for (int k = 0; k < NAW; ++k)
+            __builtin_amdgcn_global_load_lds(wq + a_off[k], (lds_ptr_t)(base + a_dst[k]), 16, 0, 0);
+#pragma unroll
+        for (int k = 0; k < NBW; ++k) {
+            const In* src = ((b_mask[k] >> tap_i) & 1u) ? X + (b_base[k] + tapoff) : zero;
+            __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(base + b_dst[k]), 16, 0, 0);
+        }
+        wq += wq_step;
+        if (++cc == prm.nchunk) {
+            cc = 0;
+            ++tap_i;
+            if (++kw == cls.nW) {
+                kw = 0;
+                if (++kh == cls.nH) { kh = 0; ++kt; }
+            }
+        }
+    };
+
+    f32x4 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
+    const int frag_off = (lane & 15) * 64 + (((lane >> 4) ^ swz(lane & 15)) << 4);
+    const int a_frag = wm * TM * 16 * 64 + frag_off;
+    const int b_frag = BM * 64 + wn * TN * 16 * 64 + frag_off;
+
+    if (wave == 0) {                                  // the blob's shifts (zeros): the shared epilogue reads them from LDS
+        const int l4 = lane < BM / 4 ? lane : BM / 4 - 1;
+        __builtin_amdgcn_global_load_lds(shift + m0 + 4 * l4, (lds_ptr_t)(lds + SHIFT_AT), 16, 0, 0);
+    }
+    issue(0);
+    if (nq > 1) {
+        issue(1);
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPW) : "memory");
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();
+    int cur = 0, nxt2 = 2;
+    for (int q = 0; q < nq; ++q) {
+        const bool ahead = q + 2 < nq;
+        if (ahead) issue(nxt2);
+        const unsigned no_mask[TN] = {};
+        mfma_step<TM, TN, false>(acc, lds_base + cur * STAGE + a_frag, lds_base + cur * STAGE + b_frag, no_mask);
+        if (ahead) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPW) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        cur = cur == 2 ? 0 : cur + 1;
+        nxt2 = nxt2 == 2 ? 0 : nxt2 + 1;
+    }
+
+    epilogue_at<TM, TN, BM, BN>(prm, acc, (const float*)(lds + SHIFT_AT), R, Y, m0, voxel, tm, wm, wn, tid, (float*)lds, tn, WGN);
 #endif
 }
 
@@ -1058,6 +1270,33 @@ __global__ void pack_bf16_kernel(const float* __restrict__ w, const float* __res
     wp[idx] = (__bf16)v;
 }
 
+// The blob of conv_bf16_dgrad_kernel in one launch: per class Wp[q][Mp][32], q = class tap * nchunk + chunk, the classes one after
+// the other (DgradClass::q0), then Mp zero shifts.  `w` is the FORWARD weight (K, M, kT, kH, kW) as the module holds it: channel roles
+// swapped, and tap (a_t, a_h, a_w) of a class is forward tap r + s*(taps - 1 - a) per axis (selected and flipped).
+__global__ void pack_bf16_dgrad_kernel(const float* __restrict__ w, __bf16* __restrict__ wp, float* __restrict__ shift_out,
+                                       DgradTable tab, int M, int Mp, int bm, int K, int nchunk, int kH, int kW, int sT, int sH,
+                                       int sW, int taps, long total) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < Mp) shift_out[idx] = 0.f;
+    if (idx >= total) return;
+    const int k = (int)(idx & 31);
+    const long rq = idx >> 5;
+    const int prow = (int)(rq % Mp);
+    const int row = prow / bm * bm + tile_channel(prow % bm, bm);
+    const int q = (int)(rq / Mp);
+    DgradClass cls = tab.c[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i)
+        if (q >= tab.c[i].q0) cls = tab.c[i];         // (a class without taps shares its q0 with the next one: the last match holds q)
+    const int ql = q - cls.q0;
+    const int tap = ql / nchunk, ci = (ql - tap * nchunk) * 32 + k;
+    const int aw = tap % cls.nW, ah = tap / cls.nW % cls.nH, at = tap / (cls.nW * cls.nH);
+    const int ft = cls.wT + sT * (cls.nT - 1 - at), fh = cls.wH + sH * (cls.nH - 1 - ah), fw = cls.wW + sW * (cls.nW - 1 - aw);
+    float v = 0.f;
+    if (row < M && ci < K) v = w[((long)ci * M + row) * taps + (ft * kH + fh) * kW + fw];
+    wp[idx] = (__bf16)v;
+}
+
 // (N,3,T,H,W) fp32 -> [N][T][Hp][Wp][4] bf16 with a zero border of (padH, padW) (and zero 4th channel)
 __global__ void clip_to_bf16_kernel(const float* __restrict__ x, int C, int T, int H, int W, int padH, int padW, int Hp,
                                     int Wpix, long total, __bf16* __restrict__ out) {
@@ -1395,7 +1634,7 @@ int zsv_conv3d_bf16_pack_dgrad(const zsv_conv_desc* d, const float* w_fwd, void*
 }
 
 static int bf16_fwd_impl(const zsv_conv_desc* d, const void* x, const void* blob, const void* residual, int fuse_relu, void* y,
-                         float* stat, int32_t stat_rows_capacity, int32_t* stat_rows, void* stream);
+                         float* stat, int32_t stat_rows_capacity, int32_t* stat_rows, void* stream, int res_rounded = 0);
 
 int zsv_conv3d_bf16_fwd(const zsv_conv_desc* d, const void* x, const void* blob, const void* residual, int fuse_relu,
                         void* y, void* stream) {
@@ -1416,7 +1655,7 @@ int zsv_conv3d_bf16_fwd_stats(const zsv_conv_desc* d, const void* x, const void*
 }
 
 static int bf16_fwd_impl(const zsv_conv_desc* d, const void* x, const void* blob, const void* residual, int fuse_relu, void* y,
-                         float* stat, int32_t stat_rows_capacity, int32_t* stat_rows, void* stream) {
+                         float* stat, int32_t stat_rows_capacity, int32_t* stat_rows, void* stream, int res_rounded) {
     if (d == nullptr) return ZSV_E_NULL;
     const int st = bf16_check(d);
     if (st != ZSV_OK) return st;
@@ -1439,6 +1678,7 @@ static int bf16_fwd_impl(const zsv_conv_desc* d, const void* x, const void* blob
     p.pT = d->pT; p.pH = d->pH; p.pW = d->pW;
     p.P = d->N * p.ToHoWo;
     p.relu = fuse_relu ? 1 : 0;
+    p.res_rounded = res_rounded;
     p.stat = stat;
     if (stat != nullptr) {
         // one row per column tile of the kernel chosen below (256 voxels, 128 in the small-problem form)
@@ -1483,6 +1723,160 @@ static int bf16_fwd_impl(const zsv_conv_desc* d, const void* x, const void* blob
     if (bm == 144) return bf16_launch<9, 4, 1, 4>(p, s, xb, wp, shift, rb, yb);
     if (small) return bf16_launch<4, 4, 2, 2>(p, s, xb, wp, shift, rb, yb);
     return bf16_launch<8, 4, 1, 4>(p, s, xb, wp, shift, rb, yb);
+}
+
+}  // extern "C"
+
+// ---- input gradient, any stride, one launch -----------------------------------------
+namespace {
+struct DgradPlan {
+    bool stride1;
+    zsv_conv_desc d1;          // stride 1: the input-gradient problem as a forward convolution (bf16_fwd_impl's selection runs it)
+    Bf16Params p;              // strided: conv_bf16_dgrad_kernel's parameters ...
+    DgradTable tab;            // ... and its class table
+    int bm, cfg;               // row tile; cfg: 0 = 64 x 256, 1 = 144 x 256, 2 = 128 x 128 (small problem), 3 = 128 x 256
+    long total_q;              // K chunks of all classes
+};
+
+struct AxisClass { int rho, r, taps, o, count; };
+int axis_classes(int k, int p, int s, int n_in, AxisClass* out) {
+    int n = 0;
+    for (int rho = 0; rho < s; ++rho) {
+        const int count = (n_in - rho + s - 1) / s;
+        if (count <= 0) continue;
+        const int r = (rho + p) % s;
+        const int taps = k > r ? (k - r + s - 1) / s : 0;
+        const int c = (rho + p - r) / s;
+        out[n++] = AxisClass{rho, r, taps, c - taps + 1, count};
+    }
+    return n;
+}
+
+int dgrad_plan(const zsv_conv_desc* d, DgradPlan* pl) {
+    if (d == nullptr) return ZSV_E_NULL;
+    const int st = conv_check(d);
+    if (st != ZSV_OK) return st;
+    if (bf16_folded(d)) return ZSV_E_UNSUPPORTED;                       // the clip's gradient: nobody needs it
+    if (d->pT > d->kT - 1 || d->pH > d->kH - 1 || d->pW > d->kW - 1) return ZSV_E_UNSUPPORTED;
+    if (d->sT > 8 || d->sH > 8 || d->sW > 8 || d->sT * d->sH * d->sW > 8) return ZSV_E_UNSUPPORTED;
+    pl->stride1 = d->sT == 1 && d->sH == 1 && d->sW == 1;
+    if (pl->stride1) {
+        pl->d1 = zsv_conv_desc{d->N, d->Cout, d->To, d->Ho, d->Wo, d->Cin, d->Ti, d->Hi, d->Wi, d->kT, d->kH, d->kW, 1, 1, 1,
+                               d->kT - 1 - d->pT, d->kH - 1 - d->pH, d->kW - 1 - d->pW};
+        return bf16_check(&pl->d1);
+    }
+    const int cp = round_up(d->Cout, 32), dxp = round_up(d->Cin, 32);   // channel pitches of dz and dx
+    const long dz_elems = (long)d->N * d->To * d->Ho * d->Wo * cp, dx_elems = (long)d->N * d->Ti * d->Hi * d->Wi * dxp;
+    if (dz_elems >= (1L << 31) || dx_elems >= (1L << 31)) return ZSV_E_TOO_LARGE;
+    Bf16Params& p = pl->p;
+    const int bm = pl->bm = bf16_bm(d->Cin);
+    p.M = d->Cin;
+    p.Mp = round_up(d->Cin, bm);
+    p.CoutP = dxp;
+    p.nchunk = cp / 32;
+    p.kT = d->kT; p.kH = d->kH; p.kW = d->kW;
+    p.sW = cp; p.sH = d->Wo * cp; p.sT = d->Ho * d->Wo * cp;
+    p.sN = (long)d->To * d->Ho * d->Wo * cp;
+    p.Ti = d->To; p.Hi = d->Ho; p.Wi = d->Wo;                           // dz's extents: validity of a tap
+    p.Wo = d->Wi; p.HoWo = d->Hi * d->Wi; p.ToHoWo = d->Ti * d->Hi * d->Wi;   // dx's extents: where a column is stored
+    p.strT = d->sT; p.strH = d->sH; p.strW = d->sW;
+    p.pT = d->pT; p.pH = d->pH; p.pW = d->pW;
+    p.P = d->N * p.ToHoWo;
+    p.relu = 0;
+    p.res_rounded = 1;
+    p.cc_outer = 0;
+    p.stat = nullptr;
+    const bool small = (long)(p.Mp / 128) * ((p.P + 255) / 256) < 384;  // bf16_fwd_impl's tile shapes for the per-tap kernel
+    pl->cfg = bm == 64 ? 0 : bm == 144 ? 1 : small ? 2 : 3;
+    const int bn = pl->cfg == 2 ? 128 : 256;
+    AxisClass at[8], ah[8], aw[8];
+    const int nt = axis_classes(d->kT, d->pT, d->sT, d->Ti, at), nh = axis_classes(d->kH, d->pH, d->sH, d->Hi, ah),
+              nw = axis_classes(d->kW, d->pW, d->sW, d->Wi, aw);
+    int n = 0, tiles = 0;
+    long q = 0;
+    for (int i = 0; i < 8; ++i) {
+        pl->tab.c[i] = DgradClass{};
+        pl->tab.c[i].q0 = pl->tab.c[i].tile0 = 0x7fffffff;
+    }
+    for (int a = 0; a < nt; ++a)
+        for (int b = 0; b < nh; ++b)
+            for (int c = 0; c < nw; ++c) {
+                DgradClass& k = pl->tab.c[n++];
+                const bool reached = at[a].taps > 0 && ah[b].taps > 0 && aw[c].taps > 0;
+                const int taps = reached ? at[a].taps * ah[b].taps * aw[c].taps : 0;
+                if (taps > 32) return ZSV_E_UNSUPPORTED;                // tap validity mask
+                k.nT = reached ? at[a].taps : 0; k.nH = reached ? ah[b].taps : 0; k.nW = reached ? aw[c].taps : 0;
+                k.oT = at[a].o; k.oH = ah[b].o; k.oW = aw[c].o;
+                k.rT = at[a].rho; k.rH = ah[b].rho; k.rW = aw[c].rho;
+                k.wT = at[a].r; k.wH = ah[b].r; k.wW = aw[c].r;
+                k.cT = at[a].count; k.cH = ah[b].count; k.cW = aw[c].count;
+                k.cols = d->N * k.cT * k.cH * k.cW;
+                k.q0 = (int)q;
+                k.tile0 = tiles;
+                q += (long)taps * p.nchunk;
+                tiles += (k.cols + bn - 1) / bn;
+            }
+    pl->total_q = q;
+    p.nq = (int)q;
+    p.tiles_m = p.Mp / bm;
+    p.tiles_n = tiles;
+    return ZSV_OK;
+}
+
+template <int TM, int TN, int WGM, int WGN>
+int bf16_dgrad_launch(const DgradPlan& pl, hipStream_t stream, const __bf16* dz, const __bf16* wp, const float* shift,
+                      const __bf16* fanin, __bf16* dx) {
+    constexpr int BM = 16 * TM * WGM, BN = 16 * TN * WGN;
+    constexpr int LDS_BYTES = 3 * (BM + BN) * 64 + 1024;
+    static const hipError_t attr = hipFuncSetAttribute((const void*)conv_bf16_dgrad_kernel<TM, TN, WGM, WGN>,
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    if (attr != hipSuccess) return ZSV_E_LAUNCH;
+    hipLaunchKernelGGL((conv_bf16_dgrad_kernel<TM, TN, WGM, WGN>), dim3(pl.p.tiles_m * pl.p.tiles_n), dim3(256), LDS_BYTES, stream,
+                       pl.p, pl.tab, dz, wp, shift, fanin, dx);
+    return launch_status();
+}
+}  // namespace
+
+extern "C" {
+
+size_t zsv_conv3d_bf16_dgrad_blob_bytes(const zsv_conv_desc* d) {
+    DgradPlan pl;
+    if (dgrad_plan(d, &pl) != ZSV_OK) return 0;
+    if (pl.stride1) return zsv_conv3d_bf16_blob_bytes(&pl.d1);
+    return (size_t)pl.total_q * pl.p.Mp * 32 * 2 + (size_t)pl.p.Mp * 4;
+}
+
+int zsv_conv3d_bf16_dgrad_pack(const zsv_conv_desc* d, const float* w_fwd, void* blob, void* stream) {
+    DgradPlan pl;
+    const int st = dgrad_plan(d, &pl);
+    if (st != ZSV_OK) return st;
+    if (w_fwd == nullptr || blob == nullptr) return ZSV_E_NULL;
+    if (pl.stride1) return zsv_conv3d_bf16_pack_dgrad(&pl.d1, w_fwd, blob, stream);
+    const long total = pl.total_q * pl.p.Mp * 32;
+    const long threads = total > pl.p.Mp ? total : pl.p.Mp;            // (a geometry no tap reaches anywhere still gets its shifts)
+    hipLaunchKernelGGL(pack_bf16_dgrad_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_fwd,
+                       (__bf16*)blob, (float*)((char*)blob + total * 2), pl.tab, d->Cin, pl.p.Mp, pl.bm, d->Cout, pl.p.nchunk, d->kH,
+                       d->kW, d->sT, d->sH, d->sW, d->kT * d->kH * d->kW, total);
+    return launch_status();
+}
+
+int zsv_conv3d_bf16_dgrad(const zsv_conv_desc* d, const void* dz, const void* blob, const void* fanin, void* dx, void* stream) {
+    DgradPlan pl;
+    const int st = dgrad_plan(d, &pl);
+    if (st != ZSV_OK) return st;
+    if (dz == nullptr || blob == nullptr || dx == nullptr) return ZSV_E_NULL;
+    if (pl.stride1) return bf16_fwd_impl(&pl.d1, dz, blob, fanin, 0, dx, nullptr, 0, nullptr, stream, 1);
+    const __bf16* wp = (const __bf16*)blob;
+    const float* shift = (const float*)((const char*)blob + (size_t)pl.total_q * pl.p.Mp * 32 * 2);
+    const __bf16 *zb = (const __bf16*)dz, *fb = (const __bf16*)fanin;
+    __bf16* xb = (__bf16*)dx;
+    hipStream_t s = (hipStream_t)stream;
+    switch (pl.cfg) {
+        case 0: return bf16_dgrad_launch<4, 4, 1, 4>(pl, s, zb, wp, shift, fb, xb);
+        case 1: return bf16_dgrad_launch<9, 4, 1, 4>(pl, s, zb, wp, shift, fb, xb);
+        case 2: return bf16_dgrad_launch<4, 4, 2, 2>(pl, s, zb, wp, shift, fb, xb);
+        default: return bf16_dgrad_launch<8, 4, 1, 4>(pl, s, zb, wp, shift, fb, xb);
+    }
 }
 
 int zsv_clip_to_bf16(const float* x, int32_t N, int32_t C, int32_t T, int32_t H, int32_t W, int32_t padH, int32_t padW,
@@ -1572,6 +1966,7 @@ int zsv_conv3d_fp8_fwd(const zsv_conv_desc* d, const void* x, const void* blob, 
     p.pT = d->pT; p.pH = d->pH; p.pW = d->pW;
     p.P = d->N * p.ToHoWo;
     p.relu = fuse_relu ? 1 : 0;
+    p.res_rounded = 0;
     p.stat = nullptr;
     p.cc_outer = (p.nchunk >= 3 && ZSV_KNOB(BF16_GROUP_OUTER) == nullptr) ? 1 : 0;     // (>= 192 bytes per image row, as bf16)
     const float* shift = (const float*)((const char*)blob + fp8_weight_bytes(d, p.Mp));    // then the Mp factors
