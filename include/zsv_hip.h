@@ -11,6 +11,34 @@
  *     S = T*H*W; pointers are device pointers owned by the caller;
  *   - kernels never allocate: workspaces are passed in (query the size first);
  *   - no byte outside the stated extent of an input may influence a result, and no input (const pointer) is written;
+ *   - alignment of pointer arguments:
+ *       fp32 tensors and vectors -- x, w, bias, y, dy, dx, dw, residual, add, sub, the BatchNorm vectors (gamma, beta, save_*,
+ *         running_*, dgamma, dbeta), bn_partials / conv_partials, the linear operands, the cosine_topk / split_accuracy
+ *         embeddings, out_dist (8 bytes: a double), zsv_clip_to_bf16's input, the clip-transform outputs -- need only their
+ *         element's alignment (4 bytes), each on its own: a contiguous view that starts at an odd element offset of a larger
+ *         buffer (a parameter inside one flat buffer, a bucket slice) is a legal operand.  int32 / int64 tables, labels, argmax
+ *         and index outputs keep their natural alignment (4 / 8 bytes).  uint8 frames and images: any address;
+ *       workspaces, weight panels, blobs, mask tables and the coefficient rows (pre_coef / coef of zsv_bn_fwd_train_coeffs,
+ *         zsv_bn_eval_coeffs) are 16-byte aligned, and a size query covers every route a call with any legal alignment of
+ *         its tensors can take;
+ *       channels-last bf16 / e4m3 tensors (activations, residuals, fanin, dz, dx, the folded clip of zsv_clip_to_bf16) are
+ *         16-byte aligned: their rows are 64-byte (clip: 8-byte) units moved as 16-byte pieces.  An entry point handed one
+ *         off a 16-byte boundary returns ZSV_E_UNSUPPORTED before any launch and writes nothing.  zsv_absmax_bf16 is the
+ *         exception: it takes any 2-byte aligned address;
+ *     results do not depend on the alignment of the fp32 operands: a call gives the same bits as on 16-byte aligned ones
+ *     wherever it runs the same kernel.  Some entry points choose the kernel by `pointer & 15`; where the other kernel sums
+ *     in another order the result is that kernel's (as deterministic, within the same tolerance of the exact value).  These
+ *     are: the weight gradients zsv_conv3d_wgrad and zsv_conv3d_wgrad_masked, whose LDS-DMA,
+ *     temporal-ring, Winograd-form and stem-row kernels are given only x and dy on 16-byte boundaries -- otherwise the
+ *     register-staged / generic kernels run, the ones ZSV_NO_WGRAD_DMA, ZSV_NO_WGRAD_TRING, ZSV_NO_WGRAD_WINO and
+ *     ZSV_NO_STEM_WGRAD select (zsv_conv3d_wgrad_pre has one kernel and gives the same bits at any alignment);
+ *     zsv_conv3d_fwd_stat_tiles(d, y), which answers for the y it is given: the tap kernel's statistics epilogue needs y on a
+ *     16-byte boundary, 0 means "call the plain form for this y" (y itself has the same bits either way; statistic tiles asked
+ *     for one y and passed with another are refused, ZSV_E_UNSUPPORTED, by zsv_conv3d_fwd_stats / _full / _pre); and
+ *     zsv_relu_bwd_bias, whose db is summed in another order when S % 4 != 0 or one of dy, y, dx is off a 16-byte boundary
+ *     (dx is the same bits).  Everywhere else -- the float4 forms of the element-wise, pool, BatchNorm, split-K reduce and
+ *     generic-convolution kernels, the 16-byte image pieces of the Winograd and stride-2 input-gradient kernels -- alignment
+ *     selects only the width of the loads and stores;
  *   - `stream` is a hipStream_t passed as void*; launches are asynchronous on it;
  *   - return value: 0 = OK, otherwise a ZSV_E_* code (zsv_status_string() names it);
  *     nothing throws across this boundary;
@@ -58,7 +86,8 @@ int32_t zsv_reload_knobs(void);
 /* ---- convolution (aten::conv3d and its autograd formulas) ------------------- */
 /* y = conv3d(x, w) (+ bias[c]) (relu optional, for network.py:147-162 `relu(conv(x))`).
  * `workspace` holds the weights re-packed tap-major for the fast kernel (query the size;
- * 0 means the call needs none).  It must be 16-byte aligned. */
+ * 0 means the call needs none).  It must be 16-byte aligned; x, w, bias, residual, y (and dy, dx, dw, add, sub, bn_partials
+ * below) need 4 bytes each (Conventions: alignment). */
 size_t zsv_conv3d_fwd_workspace_bytes(const zsv_conv_desc* d);
 /* Same, and the epilogue also emits BatchNorm partial statistics of y: bn_partials[0..Cout*tiles)
  * = per (channel, column tile) sums, then Cout*tiles sums of squares, tiles =
@@ -152,7 +181,8 @@ int zsv_channel_sum(const float* dy, int32_t N, int32_t C, int32_t S, float* db,
  *   mean/var over (N, S) per channel (biased var for normalising),
  *   running_mean/var updated in place with `momentum` (unbiased var), like torch;
  *   y = relu?((x - mean) * invstd * gamma + beta + residual?)
- * save_mean / save_invstd (C floats each) are kept for backward. */
+ * save_mean / save_invstd (C floats each) are kept for backward.  Every tensor and vector of this family needs 4-byte
+ * alignment only (the float4 routes are taken on S % 4 == 0 and work at any such address); the workspace 16. */
 size_t zsv_bn_workspace_bytes(int32_t N, int32_t C, int32_t S);
 int zsv_bn_fwd_train(const float* x, int32_t N, int32_t C, int32_t S, const float* gamma,
                      const float* beta, const float* residual, int fuse_relu, float* y,
@@ -290,7 +320,8 @@ int zsv_adam_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, i
  * conv desc carries the padded Hi/Wi and pH = pW = 0, and needs (Wo-1)*sW + 8 <= Wi.
  * `blob` = the packed bf16 weights followed by the fp32 shifts (zsv_conv3d_bf16_blob_bytes), built
  * once per layer by zsv_conv3d_bf16_pack (scale / shift may be NULL = 1 / 0: plain conv or bias).
- * `residual` (may be NULL) and y have the output's layout. */
+ * `residual` (may be NULL) and y have the output's layout.  x, residual, y (dz, fanin, dx of the input gradient; the clip) and
+ * the blob are 16-byte aligned -- ZSV_E_UNSUPPORTED otherwise, before any launch; w, scale, shift need 4 bytes. */
 int32_t zsv_bf16_channel_pitch(int32_t channels);
 size_t zsv_conv3d_bf16_blob_bytes(const zsv_conv_desc* d);
 int zsv_conv3d_bf16_pack(const zsv_conv_desc* d, const float* w, const float* scale, const float* shift,
@@ -353,7 +384,8 @@ int zsv_meanpool_bf16(const void* x, int32_t N, int32_t S, int32_t C, float* out
  * pad channels are written as zero).  A clip (Cin <= 4) stays in the bf16 folded form of zsv_clip_to_bf16 (same descriptor
  * rules as zsv_conv3d_bf16_fwd, bf16 operands) and only its output is e4m3.  `blob` = the packed weights (e4m3, or bf16 for a
  * clip) followed by Mp fp32 shifts and Mp fp32 wscale factors (zsv_conv3d_fp8_blob_bytes), built once per layer by
- * zsv_conv3d_fp8_pack (scale / shift may be NULL = 1 / 0).  `residual` (may be NULL) and y have the output's layout, e4m3. */
+ * zsv_conv3d_fp8_pack (scale / shift may be NULL = 1 / 0).  `residual` (may be NULL) and y have the output's layout, e4m3.
+ * Alignment as in the bf16 path: 16 bytes for x, residual, y and the blob (ZSV_E_UNSUPPORTED otherwise), 4 for w, scale, shift. */
 int32_t zsv_fp8_channel_pitch(int32_t channels);
 size_t zsv_conv3d_fp8_blob_bytes(const zsv_conv_desc* d);
 int zsv_conv3d_fp8_pack(const zsv_conv_desc* d, const float* w, const float* scale, const float* shift, void* blob, void* stream);
@@ -387,7 +419,9 @@ int zsv_absmax_bf16(const void* x, int64_t count, float* amax, void* stream);
  *   save_coef (may be NULL): 2 * Cp floats, the forward's scale a and shift b per (padded) channel.  Passed back as `fwd_coef`
  *   with y == NULL (no residual in the forward) the backward recomputes the ReLU mask as fma(z, a, b) > 0 -- exactly what the
  *   forward rounded to y -- and does not read the saved output at all (4 of its 14 bytes per element).
- * workspace: zsv_bn_cl_workspace_bytes(R, C) bytes (0 = unsupported shape). */
+ * workspace: zsv_bn_cl_workspace_bytes(R, C) bytes (0 = unsupported shape).  Every channels-last operand of this family (z, residual,
+ * y, dy, dz, g_out, x / dx of the pools and converters) is 16-byte aligned, ZSV_E_UNSUPPORTED otherwise; the fp32 vectors,
+ * coefficient rows and fp32 tensors (dw, dpooled, the NCS side of the converters) need 4 bytes. */
 size_t zsv_bn_cl_workspace_bytes(int64_t R, int32_t C);
 int zsv_bn_cl_fwd_train(const void* z, const void* residual, int64_t R, int32_t C, const float* gamma, const float* beta,
                         float* running_mean, float* running_var, float momentum, float eps, int fuse_relu, void* y,
@@ -448,7 +482,8 @@ int zsv_meanpool_bf16_bwd(const float* dpooled, int32_t N, int32_t S, int32_t C,
  * crop_flip_params_device: N x {top, left, flip} int32 on the device; out: (N, 3, T, crop, crop)
  * fp32.  Hres/Wres = floor(Hin*scale), floor(Win*scale); inv_scale = (float)(1/scale).
  * Rounding: the source coordinate is fma(inv_scale, dst + 0.5, -0.5) and each of the three blends is
- * fma(l, b, (1 - l) * a), nothing else fused.  Builds before zsv_clip_transform_batch existed left the fusing to the
+ * fma(l, b, (1 - l) * a), nothing else fused.  The uint8 frames and images of this family may start at any address, the int32 /
+ * int64 tables at their natural alignment, out at 4 bytes.  Builds before zsv_clip_transform_batch existed left the fusing to the
  * compiler, and which product of a blend was fused depended on the loop version a pixel went through: against those
  * builds an output can differ in its last bit (within the 2e-6 of the reference's chain either way). */
 int zsv_clip_transform(const uint8_t* frames_u8, int32_t N, int32_t T, int32_t Hin, int32_t Win,

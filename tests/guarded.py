@@ -9,6 +9,9 @@ The same layout pins what a kernel READS: an input's bytes are the payload of a 
 the value reach its result computes something else when the band byte changes (``BAND_BYTES``); the fetch itself stays inside
 the test's own allocation.
 
+``run_contract`` is the sequence of runs built on this -- two prefills, a shifted workspace, two poisoned bands and the
+element-aligned run, in which every fp32 / uint8 operand sits 4, 8 or 12 (1, 2 or 3) bytes past its boundary.
+
 Plain module: no fixtures, works on CPU tensors as well (tests/test_guarded_host.py).
 """
 import torch
@@ -100,6 +103,137 @@ def guarded_copy(tensor, device, guard_byte=GUARD_BYTE, align=256, shift=0):
     if b.nbytes:
         b.payload.copy_(src.reshape(-1).view(torch.uint8))
     return b
+
+
+# ---- the element-aligned run ----------------------------------------------------------------------------------------------
+# include/zsv_hip.h: fp32 tensors and vectors need only 4-byte alignment, each on its own, uint8 frames none at all.  Every such
+# operand of a call, inputs and outputs alike, starts e * (1 + i mod 3) bytes past a 256-byte boundary -- e its element size,
+# i its position among them -- so fp32 operands sit at +4, +8, +12 and neighbours differ from each other: a kernel that rounds
+# a base down to 16 bytes, or takes "x and y are misaligned alike" for granted, writes a band, leaves an element unwritten or
+# computes other bytes.  Everything else (workspaces, panels, blobs, mask tables, coefficient rows, channels-last bf16 / e4m3
+# tensors, integer tables) keeps its alignment.
+ELEMENT_ALIGNED_DTYPES = (torch.float32, torch.uint8)
+
+
+def element_shift(dtype, position):
+    """Bytes past the 256-byte boundary of the ``position``-th element-aligned operand of a call."""
+    return torch.empty((), dtype=dtype).element_size() * (1 + int(position) % 3)
+
+
+def contract_runs(shifted, element_aligned=True):
+    """(payload prefill, workspace shift, band byte, element-aligned?) of every run of ``run_contract``."""
+    return [(0x00, 0, GUARD_BYTE, False), (0xFF, 0, GUARD_BYTE, False)] + ([(0xFF, 16, GUARD_BYTE, False)] if shifted else []) + \
+        [(0x00, 0, band, False) for band in BAND_BYTES] + ([(0xFF, 0, GUARD_BYTE, True)] if element_aligned else [])
+
+
+def _raw(t):
+    return t.contiguous().view(-1).view(torch.uint8)
+
+
+def run_contract(entry, launch, outs, works=None, shifted=False, defined=None, ins=None, aligned=(), device="cpu", synchronize=None,
+                 status_string=str, other_route=None, element_aligned=True):
+    """Run ``launch`` once per entry of ``contract_runs`` on fresh guarded buffers and assert, after ``synchronize()``: status 0,
+    every band intact, every input unchanged, no output element of a 0xFF run left at the prefill, and the outputs of every run
+    equal to the first run's as raw bytes.
+
+    outs:  name -> (dtype, shape) or (dtype, shape, initial tensor) -- the latter for in / out arguments;
+    works: name -> bytes: workspaces, blobs, panels, mask tables (prefilled, guarded, not compared); ``shifted`` (True, or a set
+           of their names): one more run has them 16 bytes past a 256-byte boundary;
+    ins:   name -> tensor of EXACTLY the extent the callee may read (None: an operand left out, the launch gets None), or
+           (tensor, shift): the copy starts ``shift`` bytes past a 256-byte boundary in every run;
+    aligned: names of fp32 / uint8 operands that keep their 16-byte alignment in the element-aligned run (coefficient rows,
+           e4m3 tensors held as uint8);
+    launch(p): p[name] = address, p["table"](tensor) = the address of a guarded copy of a table the launch itself builds;
+           returns the status, or a list of them;
+    defined(name, tensor) -> the part of an output the operation defines (default: all of it);
+    other_route: None, or -- for a call whose kernel family depends on the operands' alignment -- a function of the
+           element-aligned run's outputs that makes the comparison (against a reference of its own) in place of the byte
+           comparison with the first run.
+    Returns (the first run's outputs (copies), {"element_operands": how many operands the element-aligned run moved (0: that run
+    was left out, nothing to move), "element_equal": whether its outputs equalled the first run's bytes (None without it)})."""
+    works, ins = works or {}, ins or {}
+    for name in ins:
+        assert name not in outs and name not in works, f"{entry}: {name} is named twice"
+    moved = [name for name, t in ins.items() if t is not None and not isinstance(t, tuple) and t.dtype in ELEMENT_ALIGNED_DTYPES] + \
+        [name for name, spec in outs.items() if spec[0] in ELEMENT_ALIGNED_DTYPES]
+    moved = [name for name in moved if name not in aligned]
+    runs = contract_runs(shifted, element_aligned and bool(moved))
+    results = []
+    for fill, shift, band, elem in runs:
+        bufs, views, sources = {}, {}, {}
+        at = {name: element_shift(ins[name].dtype if name in ins else outs[name][0], i) for i, name in enumerate(moved)} if elem else {}
+        for name, t in ins.items():
+            if t is None:
+                continue
+            t, in_shift = t if isinstance(t, tuple) else (t, at.get(name, 0))
+            bufs[name] = sources[name] = guarded_copy(t, device, band, 256, in_shift)
+        for name, spec in outs.items():
+            b = guarded_like(spec[0], spec[1], device, fill, 256, at.get(name, 0), guard_byte=band)
+            views[name] = b.view(spec[0], spec[1])
+            if len(spec) > 2:
+                views[name].copy_(spec[2])
+            bufs[name] = b
+        for name, nbytes in works.items():
+            bufs[name] = guarded(nbytes, device, fill, 256, shift if (shifted is True or (shifted and name in shifted)) else 0, guard_byte=band)
+        before = {name: b.bytes() for name, b in sources.items()}
+        p = {name: b.ptr for name, b in bufs.items()}
+        p.update({name: None for name, t in ins.items() if t is None})
+
+        def table(tensor, name="table"):
+            """For a launch that builds a table of addresses of this run's buffers: the table as one more guarded input."""
+            name = f"{name} #{len(bufs)}"
+            bufs[name] = sources[name] = guarded_copy(tensor, device, band)
+            before[name] = sources[name].bytes()
+            return sources[name].ptr
+
+        p["table"] = table
+        status = launch(p)
+        if synchronize:
+            synchronize()
+        what = f"{entry}, prefill 0x{fill:02X}" + (", workspace at 256 k + 16" if shift else "") + \
+            (f", bands 0x{band:02X}" if band != GUARD_BYTE else "") + \
+            (", element-aligned operands (" + ", ".join(f"{n} +{s}" for n, s in at.items()) + ")" if elem else "")
+        for s in (status if isinstance(status, (list, tuple)) else [status]):
+            assert s == 0, f"{what}: {status_string(int(s))} (status {s})"
+        for name, b in bufs.items():
+            b.check(f"{what}: {name}")
+        for name, b in sources.items():
+            assert torch.equal(b.payload, before[name]), f"{what}: the input {name} was written (inputs are const)"
+        got = {}
+        for name, v in views.items():
+            part = defined(name, v) if defined else v
+            if fill == 0xFF:
+                assert_all_written(part, f"{what}: {name}")
+            got[name] = part.clone()
+        results.append(got)
+    info = {"element_operands": len(moved) if runs[-1][3] else 0, "element_equal": None}
+    for (fill, shift, band, elem), got in zip(runs[1:], results[1:]):
+        same = all(v.shape == results[0][name].shape and torch.equal(_raw(v), _raw(results[0][name])) for name, v in got.items())
+        if elem:
+            info["element_equal"] = same
+            if other_route is not None:
+                other_route(got)
+                continue
+        for name, v in got.items():
+            first = results[0][name]
+            if elem and v.shape != first.shape:
+                raise AssertionError(f"{entry}: what the call defines of {name} depends on the ALIGNMENT of the operands: {tuple(v.shape)} with the "
+                                     f"fp32 / uint8 tensors off their 16-byte boundaries, {tuple(first.shape)} on them")
+            assert v.shape == first.shape, f"{entry}: {name}: {tuple(v.shape)} vs {tuple(first.shape)}"
+            a, b = _raw(v), _raw(first)
+            if torch.equal(a, b):
+                continue
+            index = int(torch.nonzero(a != b).flatten()[0]) // v.element_size()
+            where = f"{int((a != b).sum())} byte(s) differ from the ordinary run, first at flat index {index} of {v.numel()}"
+            if elem:
+                raise AssertionError(f"{entry}: {name} depends on the ALIGNMENT of the operands: with the fp32 / uint8 tensors 4, 8 and 12 (1, 2, 3) "
+                                     f"bytes past a 16-byte boundary {where}")
+            if band == GUARD_BYTE:
+                raise AssertionError(f"{entry}: {name} depends on what the buffers held before the call (prefill 0x00 vs 0x{fill:02X}, "
+                                     f"shift {shift})")
+            raise AssertionError(f"{entry}: {name} depends on bytes OUTSIDE the inputs or the workspace: with bands of 0x{band:02X} "
+                                 f"around every buffer {where}")
+    return results[0], info
 
 
 def unwritten(t):

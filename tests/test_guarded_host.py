@@ -207,3 +207,76 @@ def test_two_band_bytes_because_a_nan_band_alone_misses_a_max_type_over_read(kin
         differs = _run_kernel(kind, band, over=1) != first
         assert differs == caught_by[band], f"{kind} reading one element past its input, band 0x{band:02X}: caught = {differs}"
     assert any(caught_by.values())
+
+
+# ---- the element-aligned run of guarded.run_contract ------------------------------------------------------------------------------
+def test_element_shifts_differ_between_neighbouring_operands():
+    assert [G.element_shift(torch.float32, i) for i in range(5)] == [4, 8, 12, 4, 8]
+    assert [G.element_shift(torch.uint8, i) for i in range(4)] == [1, 2, 3, 1]
+    runs = G.contract_runs(shifted=True)
+    assert runs[-1] == (0xFF, 0, G.GUARD_BYTE, True) and [r[3] for r in runs[:-1]] == [False] * 5       # prefill 0xFF, ordinary bands
+    assert G.contract_runs(shifted=False, element_aligned=False) == G.contract_runs(shifted=False)[:-1]
+
+
+@pytest.mark.parametrize("shift", [4, 8, 12])
+def test_a_shifted_output_buffer_is_placed_where_asked_and_guarded_from_its_first_byte(shift):
+    b = G.guarded_like(torch.float32, (3, 5), "cpu", 0xFF, shift=shift)
+    v = b.view(torch.float32, (3, 5))
+    assert b.ptr % 256 == shift and v.data_ptr() == b.ptr and b.nbytes == 60
+    v.fill_(1.0)
+    b.check()                                              # all of the payload, nothing else
+    b.buf[b.start - 4:b.start] = 0                         # one element in front of the shifted payload: where an aligned-down store lands
+    with pytest.raises(AssertionError) as e:
+        b.check("y")
+    assert "4 byte(s) written BEFORE the payload: first at payload_start-4, last at payload_start-1" in str(e.value)
+
+
+def _numpy_scale(base_of):
+    """y = 2 * x on raw addresses, as a kernel sees them; ``base_of(x_address, y_address)`` = where it actually reads and writes."""
+    import ctypes
+    import numpy as np
+
+    def launch(p, n=24):
+        xa, ya = base_of(p["x"], p["y"])
+        x = np.ctypeslib.as_array((ctypes.c_float * n).from_address(xa))
+        y = np.ctypeslib.as_array((ctypes.c_float * n).from_address(ya))
+        y[:] = 2 * x
+        return 0
+    return launch
+
+
+@pytest.mark.parametrize("kind", ["honest", "rounds_its_bases_down", "takes_x_and_y_for_misaligned_alike"])
+def test_a_kernel_that_assumes_16_byte_alignment_fails_the_element_aligned_run_only(kind):
+    base_of = {"honest": lambda x, y: (x, y),
+               "rounds_its_bases_down": lambda x, y: (x & ~15, y & ~15),             # "the first float4"
+               "takes_x_and_y_for_misaligned_alike": lambda x, y: (x, (y & ~15) + (x & 15))}[kind]
+    x = torch.arange(24.) - 7
+    args = ("scale", _numpy_scale(base_of), {"y": (torch.float32, (24,))})
+    first, info = G.run_contract(*args, ins={"x": x}, element_aligned=False)           # the runs there were before: every kernel passes
+    assert torch.equal(first["y"], 2 * x) and info == {"element_operands": 0, "element_equal": None}
+    if kind == "honest":
+        first, info = G.run_contract(*args, ins={"x": x})
+        assert torch.equal(first["y"], 2 * x) and info == {"element_operands": 2, "element_equal": True}
+        return
+    with pytest.raises(AssertionError) as e:
+        G.run_contract(*args, ins={"x": x})
+    assert "element-aligned operands (x +4, y +8)" in str(e.value) and "BEFORE the payload" in str(e.value), str(e.value)
+
+
+def test_operands_that_keep_their_alignment_and_the_other_route_hook():
+    """bf16 / integer operands and the names in ``aligned`` stay on their boundary; ``other_route`` replaces the byte comparison of
+    the element-aligned run, and the caller learns whether the bytes were equal after all."""
+    seen = []
+
+    def launch(p):
+        seen.append({k: v % 256 for k, v in p.items() if isinstance(v, int)})
+        return 0
+
+    outs = {"y": (torch.float32, (4,), torch.zeros(4)), "coef": (torch.float32, (4,), torch.zeros(4)), "z": (torch.bfloat16, (8,), torch.zeros(8)),
+            "index": (torch.int32, (4,), torch.zeros(4, dtype=torch.int32))}
+    ins = {"x": torch.ones(4), "frames": torch.ones(5, dtype=torch.uint8), "w": (torch.ones(4), 16)}
+    hooked = []
+    _, info = G.run_contract("placement", launch, outs, {"ws": 64}, shifted=True, ins=ins, aligned={"coef"}, other_route=hooked.append)
+    assert info == {"element_operands": 3, "element_equal": True} and len(hooked) == 1 and set(hooked[0]) == set(outs)
+    assert seen[-1] == {"x": 4, "frames": 2, "w": 16, "y": 12, "coef": 0, "z": 0, "index": 0, "ws": 0}
+    assert seen[2]["ws"] == 16 and all(s["x"] == 0 and s["y"] == 0 for s in seen[:-1])

@@ -1,7 +1,7 @@
 """The C ABI's memory contract (include/zsv_hip.h: "kernels never allocate: workspaces are passed in (query the size first)",
 the caller owns every output), entry point by entry point, with guard bands (tests/guarded.py).
 
-Every (entry point, case) is called through ctypes four or five times.  Each run gets a workspace / blob / panel / mask table /
+Every (entry point, case) is called through ctypes five to seven times.  Each run gets a workspace / blob / panel / mask table /
 partials buffer of EXACTLY the queried size and every output in a buffer of exactly its shape, each between two 1 MiB guard
 bands in an allocation of its own; the payloads are prefilled with 0x00 in the first run and 0xFF (NaN / -1 / the e4m3 NaN
 code) in the second; the convolution and weight-gradient cases run a third time with the workspace 16 bytes past a 256-byte
@@ -11,7 +11,10 @@ header states, so the launch sees no tensor of the caching allocator.  Two more 
 buffer of the run -- inputs, workspaces, blobs, panels, mask tables, outputs -- with 0xFF and then 0x7F (guarded.BAND_BYTES: a
 NaN that survives every sum and product, then a huge finite value that wins every max and passes every ``> 0``).  Many kernels
 fetch past the logical data on purpose (16-byte pieces, halo voxels, clamped loads) and rely on a mask, a clamp or a buffer
-descriptor's range to keep the value out of the result: these runs pin that.  Asserted after one synchronize:
+descriptor's range to keep the value out of the result: these runs pin that.  A last run (prefill 0xFF, ordinary bands) has every
+fp32 / uint8 tensor operand, inputs and outputs alike, 4, 8 or 12 (1, 2 or 3) bytes past a 256-byte boundary -- the header asks
+only for the element's alignment, each operand on its own -- while workspaces, panels, blobs, mask tables, coefficient rows and the
+channels-last bf16 / e4m3 tensors keep theirs (guarded.element_shift).  Asserted after one synchronize:
 
 (a) the call returns ZSV_OK;
 (b) no guard band changed (nothing written before or past a buffer);
@@ -24,12 +27,15 @@ descriptor's range to keep the value out of the result: these runs pin that.  As
     comparison is the one the existing test of that entry point makes, with its tolerance;
 (f) the outputs of the two poisoned runs equal the first run's as raw bytes: no byte outside the stated extent of an input (or
     of a workspace) may influence a result;
-(g) no input's band changed and every input's payload holds the bytes it held before the call: inputs are const.
+(g) no input's band changed and every input's payload holds the bytes it held before the call: inputs are const;
+(h) the element-aligned run returns ZSV_OK, keeps (b), (d) and (g), fits workspaces of exactly the queried size (the queries see no
+    pointer: they must cover the route an unaligned call falls back to) and gives the first run's bytes -- except for the calls
+    ROUTE_CHANGES lists, whose kernel family follows the alignment: those are held to the fp64 reference of the row's own test.
 
 A case is left out for an entry point only where that entry point's own ``*_supported`` / size query says it cannot run the
 geometry.  The case tables are the ones of the other suites (rows with N = 22 or more than about 2 M output elements left out:
-GPU_ROW_LIMIT).  The last test of the file asserts that every entry point ran, and on every row of its table, and prints the
-counts: run the file as a whole.
+GPU_ROW_LIMIT).  The last test of the file asserts that every entry point ran, and on every row of its table, that each had its
+element-aligned run, and that ROUTE_CHANGES is exact, and prints the counts: run the file as a whole.
 """
 import collections
 import ctypes
@@ -79,85 +85,82 @@ def numel(shape):
     return int(np.prod(shape)) if len(shape) else 1
 
 
-def contract(entry, launch, outs, works=None, shifted=False, defined=None, count=True, ins=None):
-    """Run ``launch`` once per payload fill (and once more with the buffers named in ``shifted`` 16 bytes past a 256-byte
-    boundary), then once per poisoned band byte, on fresh guarded buffers and assert (a) - (d), (f), (g).
+# ---- (h): the only exceptions to bit equality under the element-aligned run ----------------------------------------------------------
+# The calls whose KERNEL FAMILY follows the alignment of an fp32 operand (include/zsv_hip.h names the entry points): (entry point,
+# "table/row") -- every switch combination of the row -- or (entry point, "table/row SWITCH=1"), mapped to the dispatch that sends the
+# call elsewhere; None: the exception to a row's entry, a switch under which the aligned call already runs the kernel the unaligned
+# one falls back to.  For a listed call the element-aligned run is held to the fp64 reference and the tolerance of the row's own test
+# in test_ops_gpu.py, never to the first run.  The last test of the file fails for an entry no call matched and for a listed call
+# whose bytes equalled the first run's after all: the list cannot grow slack.
+TRING = "conv_wgrad_tring.hip:524 (wgrad_tring_applicable: x | dy)"
+WINO = "conv_wgrad_wino.hip:551 (wgrad_wino_applicable: x | dy)"
+DMA = "conv_wgrad_dma.hip:306 (wgrad_dma_applicable: x | dy; asked at conv_wgrad.hip:612, sized at :526)"
+STEM = "conv_wgrad_generic.hip:433 (the stem row kernel: x | dy)"
+STATS = "conv_tap.hip:560 (tap_lds_epilogue_ok: y -- zsv_conv3d_fwd_stat_tiles(d, y) answers 0, the plain form runs, no statistics)"
+BIAS = "elementwise_pool.hip:384 (zsv_relu_bwd_bias: the float4 route sums db in another order; dx is the same bits)"
+ROUTE_CHANGES = {}
 
-    outs:  name -> (dtype, shape) or (dtype, shape, initial tensor) -- the latter for in / out arguments (running statistics);
-    works: name -> bytes: workspaces, blobs, panels, mask tables (prefilled, guarded, not compared);
-    ins:   name -> device tensor of EXACTLY the extent the header states for that argument (None: an operand left out, the
-           launch gets None), or (tensor, shift): the copy starts ``shift`` bytes past a 256-byte boundary;
-    launch(p): p[name] = device address, p["table"](tensor) = the address of a guarded copy of a table the launch itself builds
-           (job and pointer tables hold addresses of this run's buffers); returns the status, or a list of them;
-    defined(name, tensor) -> the part of an output the operation defines (default: all of it).
+
+def _listed(entries, line, rows, unless=()):
+    for entry in entries:
+        for row in rows:
+            ROUTE_CHANGES[(entry, row)] = line
+        for route in unless:
+            ROUTE_CHANGES[(entry, route)] = None
+
+
+_WGRAD = ("zsv_conv3d_wgrad", "zsv_conv3d_wgrad_masked")                    # one dispatch: wgrad_dispatch, conv_wgrad.hip:588
+_listed(_WGRAD, TRING, [f"WGRAD_TRING_CASES/{r}" for r in ("t1_like", "cin230_cout128", "ragged_both", "many_clips")])      # (switched off: the LDS-DMA kernel, DMA)
+_listed(_WGRAD, WINO, [f"WGRAD_WINO_CASES/{r}" for r in ("w_10_odd_chunks", "r3d_layer1_like_64_rows", "m56_ragged_columns", "partial_chunk_aligned_w",
+                                                         "unaligned_w_whole_chunks", "two_144_row_tiles", "m200_ragged_second_tile")],
+        unless=[f"WGRAD_WINO_CASES/{r} ZSV_NO_WGRAD_WINO=1" for r in ("w_10_odd_chunks", "partial_chunk_aligned_w", "unaligned_w_whole_chunks")])
+_listed(_WGRAD, DMA, [f"WGRAD_DMA_CASES/{r}" for r in ("s1_like", "t1_like", "cout_230", "full_333", "wide_w", "many_slices")] + ["CONV_CASES/spatial_144"],
+        unless=[f"WGRAD_DMA_CASES/{r} ZSV_NO_WGRAD_DMA=1" for r in ("s1_like", "t1_like", "cout_230", "full_333", "wide_w", "many_slices")])
+_listed(_WGRAD, f"{WINO}, or {DMA}", ["VW_CASES/r3d_layer3_333"])
+_listed(_WGRAD, STEM, [f"stem_rows/{r}" for r in ("n2_t4_56x56_c45", "n3_t2_112x112_c45", "n2_t3_24x40_c20", "n2_t2_30x128_c48")],
+        unless=[f"stem_rows/{r} ZSV_NO_STEM_WGRAD=1" for r in ("n2_t4_56x56_c45", "n3_t2_112x112_c45", "n2_t3_24x40_c20", "n2_t2_30x128_c48")])
+# every row whose forward runs the tap kernel with the statistics epilogue (the Winograd kernels' epilogue does not look at y)
+_listed(("zsv_conv3d_fwd_full (statistics)",), STATS,
+        ["CONV_CASES/temporal_s2", "CONV_CASES/pointwise_s2", "S2_DGRAD_CASES/temporal_ragged_16_byte_pieces", "two_frame_dense/n2_45_70", "two_frame_dense/n3_64_48",
+         "VW_CASES/w30 ZSV_WINO_NO_VW=1"] +
+        [f"WGRAD_DMA_CASES/{r}" for r in ("t1_like", "cin_45", "cout_230", "full_333", "one_chunk", "wide_w", "pointwise", "many_slices")] +
+        [f"WGRAD_WINO_CASES/{r}" for r in ("w_10_odd_chunks", "m56_ragged_columns", "partial_chunk_aligned_w", "unaligned_w_whole_chunks", "two_144_row_tiles")] +
+        [f"WGRAD_TRING_CASES/{r}" for r in ("t1_like", "ragged_both", "many_clips")])
+_listed(("zsv_conv3d_fwd_pre",), STATS, [f"WGRAD_TRING_CASES/{r}" for r in ("t1_like", "ragged_both", "many_clips")])
+_listed(("zsv_relu_bwd_bias",), BIAS, ["2x5x3x4x4", "2x64x4x8x8"])            # the shapes with S % 4 == 0
+
+ROUTE_SEEN = collections.defaultdict(list)     # key of ROUTE_CHANGES -> per matching call: the element-aligned run's bytes equalled the first run's
+ALIGN_RUNS = collections.Counter()             # entry point -> element-aligned runs (of the combinations COUNTS counts)
+# entry points with no fp32 / uint8 tensor operand at all: nothing to move, no element-aligned run
+NO_ELEMENT_OPERANDS = {"zsv_maxpool3d_bf16", "zsv_maxpool3d_bf16_bwd", "zsv_maxpool3d_fp8"}
+
+
+def _route_key(entry, route):
+    """The ROUTE_CHANGES key a call falls under: its own (with its switches) before its row's."""
+    if route is None:
+        return None
+    for key in ((entry, route), (entry, route.split(" ")[0])):
+        if key in ROUTE_CHANGES:
+            return key
+    return None
+
+
+def contract(entry, launch, outs, works=None, shifted=False, defined=None, count=True, ins=None, aligned=(), route=None, reference=None):
+    """guarded.run_contract on the device: (a) - (d), (f), (g), (h).  ``aligned``: fp32 / uint8 operands that keep their 16-byte
+    alignment in the element-aligned run; ``route``: "table/row" + switches, what ROUTE_CHANGES is looked up with; ``reference``:
+    the comparison (a function of the run's outputs) the element-aligned run gets where ROUTE_CHANGES lists the call.
     Returns name -> the first run's output (a copy)."""
-    works, ins = works or {}, ins or {}
-    for name in ins:
-        assert name not in outs and name not in works, f"{entry}: {name} is named twice"
-    runs = [(0x00, 0, G.GUARD_BYTE), (0xFF, 0, G.GUARD_BYTE)] + ([(0xFF, 16, G.GUARD_BYTE)] if shifted else []) + \
-        [(0x00, 0, band) for band in G.BAND_BYTES]
-    results = []
-    for fill, shift, band in runs:
-        bufs, views, sources = {}, {}, {}
-        for name, spec in outs.items():
-            b = G.guarded_like(spec[0], spec[1], DEV, fill, guard_byte=band)
-            views[name] = b.view(spec[0], spec[1])
-            if len(spec) > 2:
-                views[name].copy_(spec[2])
-            bufs[name] = b
-        for name, nbytes in works.items():
-            bufs[name] = G.guarded(nbytes, DEV, fill, 256, shift if (shifted is True or (shifted and name in shifted)) else 0, guard_byte=band)
-        for name, t in ins.items():
-            if t is None:
-                continue
-            t, in_shift = t if isinstance(t, tuple) else (t, 0)
-            bufs[name] = sources[name] = G.guarded_copy(t, DEV, band, 256, in_shift)
-        before = {name: b.bytes() for name, b in sources.items()}
-        p = {name: b.ptr for name, b in bufs.items()}
-        p.update({name: None for name, t in ins.items() if t is None})
-
-        def table(tensor, name="table"):
-            """For a launch that builds a device table of addresses of this run's buffers: the table as one more guarded input."""
-            name = f"{name} #{len(bufs)}"
-            bufs[name] = sources[name] = G.guarded_copy(tensor, DEV, band)
-            before[name] = sources[name].bytes()
-            return sources[name].ptr
-
-        p["table"] = table
-        status = launch(p)
-        torch.cuda.synchronize()
-        what = f"{entry}, prefill 0x{fill:02X}" + (", workspace at 256 k + 16" if shift else "") + \
-            (f", bands 0x{band:02X}" if band != G.GUARD_BYTE else "")
-        for s in (status if isinstance(status, (list, tuple)) else [status]):
-            assert s == 0, f"{what}: {lib().zsv_status_string(int(s)).decode()} (status {s})"                    # (a)
-        for name, b in bufs.items():
-            b.check(f"{what}: {name}")                                                                         # (b), (g)
-        for name, b in sources.items():
-            assert torch.equal(b.payload, before[name]), f"{what}: the input {name} was written (inputs are const)"   # (g)
-        got = {}
-        for name, v in views.items():
-            part = defined(name, v) if defined else v
-            if fill == 0xFF:
-                G.assert_all_written(part, f"{what}: {name}")                                                  # (d)
-            got[name] = part.clone()
-        results.append(got)
-    for (fill, shift, band), got in zip(runs[1:], results[1:]):
-        for name, v in got.items():
-            first = results[0][name]
-            assert v.shape == first.shape, f"{entry}: {name}: {tuple(v.shape)} vs {tuple(first.shape)}"
-            a, b = v.contiguous().view(-1).view(U8), first.contiguous().view(-1).view(U8)
-            if torch.equal(a, b):
-                continue
-            if band == G.GUARD_BYTE:
-                raise AssertionError(f"{entry}: {name} depends on what the buffers held before the call (prefill 0x00 vs 0x{fill:02X}, "
-                                     f"shift {shift})")                                                        # (c)
-            index = int(torch.nonzero(a != b).flatten()[0]) // v.element_size()
-            raise AssertionError(f"{entry}: {name} depends on bytes OUTSIDE the inputs or the workspace: with bands of 0x{band:02X} "
-                                 f"around every buffer {int((a != b).sum())} byte(s) differ from the ordinary run, first at flat index "
-                                 f"{index} of {v.numel()}")                                                     # (f)
+    key = _route_key(entry, route)
+    listed = key is not None and ROUTE_CHANGES[key] is not None
+    assert not listed or reference is not None, f"{key}: listed in ROUTE_CHANGES, but the call site gives no reference"
+    first, info = G.run_contract(entry, launch, outs, works, shifted, defined, ins, aligned, DEV, torch.cuda.synchronize,
+                                 lambda s: lib().zsv_status_string(s).decode(), reference if listed else None)
+    if key is not None:
+        ROUTE_SEEN[key].append(bool(info["element_equal"]))
     if count:
         COUNTS[entry] += 1
-    return results[0]
+        ALIGN_RUNS[entry] += 1 if info["element_operands"] else 0
+    return first
 
 
 def pick(o, *names, **renamed):
@@ -252,6 +255,30 @@ def _conv_operands(row):
     return d, ys, {k_: v.to(DEV) for k_, v in o.items()}, g
 
 
+_REFERENCE = {}
+
+
+def _conv_reference(row, o, want):
+    """The fp64 references of the row's own test in test_ops_gpu.py (F.conv3d and its weight gradient on the CPU), computed when a
+    ROUTE_CHANGES row asks and kept for the row's other calls and switches: "y", "dw", and "y_pre" / "dw_pre" with x read through
+    relu(x * scale[c] + shift[c])."""
+    key = (row.table, row.name)
+    if _REFERENCE.get("key") != key:
+        _REFERENCE.clear()
+        _REFERENCE["key"] = key
+    if want not in _REFERENCE:
+        x, w, dy = (o[k].double().cpu() for k in ("x", "w", "dy"))
+        if want.endswith("_pre"):
+            cin = row.xs[1]
+            a, b = (o["coef"][i, :cin].double().cpu().view(1, cin, 1, 1, 1) for i in (0, 1))
+            x = F.relu(x * a + b)
+        if want.startswith("y"):
+            _REFERENCE[want] = F.conv3d(x, w, None, row.stride, row.pad)
+        else:
+            _REFERENCE[want] = torch.nn.grad.conv3d_weight(x, row.ws, dy, stride=row.stride, padding=row.pad)
+    return _REFERENCE[want]
+
+
 def _conv_entry_points(row, tag):
     """Every fp32 convolution entry point on one row under the switches in force."""
     L = lib()
@@ -274,15 +301,30 @@ def _conv_entry_points(row, tag):
     def fwd(b, r, relu, stats, tiles):
         return lambda p: L.zsv_conv3d_fwd_full(dp, p["x"], p["w"], p.get(b), p.get(r), p["y"], relu, p.get(stats), tiles, p["ws"], nf, None)
 
-    y = contract("zsv_conv3d_fwd_full", fwd(None, None, 0, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True, ins=pick(o, "x", "w"))["y"]
+    # zsv_conv3d_fwd_stat_tiles(d, y) answers for the y it is given: every run asks for its own y, and where the answer is 0 it
+    # calls the plain form and gets no statistics, as the wrapper does
+    asked = {}
+
+    def tiles_for(p):
+        asked["tiles"] = int(L.zsv_conv3d_fwd_stat_tiles(dp, p["y"]))
+        assert asked["tiles"] in (0, tiles), f"{what}: zsv_conv3d_fwd_stat_tiles says {asked['tiles']} for this y and {tiles} for an aligned one"
+        return asked["tiles"]
+
+    def partials_written(name, v):
+        return v if name != "bn_partials" or asked["tiles"] else v[:, :, :0]
+
+    def y_reference(want):
+        return lambda got: T.close(got["y"], _conv_reference(row, o, want), what=f"{what}: forward on element-aligned operands, against fp64")
+
+    y = contract("zsv_conv3d_fwd_full", fwd(None, None, 0, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True, ins=pick(o, "x", "w"), route=what)["y"]
     same_bytes(y, yw.detach(), f"{what}: forward")
     ROWS_RUN[(row.table, "fwd")].add(row.name)
     yb = contract("zsv_conv3d_fwd_full (bias + ReLU)", fwd("bias", None, 1, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True,
-                  ins=pick(o, "x", "w", "bias"))["y"]
+                  ins=pick(o, "x", "w", "bias"), route=what)["y"]
     same_bytes(yb, yw_relu, f"{what}: forward + bias + ReLU")
     if L.zsv_conv3d_fwd_add_supported(dp):
         yr = contract("zsv_conv3d_fwd_full (residual)", fwd("bias", "res", 1, None, 0), {"y": (F32, ys)}, {"ws": nf}, shifted=True,
-                      ins=pick(o, "x", "w", "bias", "res"))["y"]
+                      ins=pick(o, "x", "w", "bias", "res"), route=what)["y"]
         conv = torch.nn.Conv3d(d.Cin, d.Cout, row.ws[2:], row.stride, row.pad, bias=True).to(DEV)
         with torch.no_grad():
             conv.weight.copy_(o["w"])
@@ -292,40 +334,47 @@ def _conv_entry_points(row, tag):
     tiles = int(L.zsv_conv3d_fwd_stat_tiles(dp, probe.ptr))
     assert (tiles > 0) == (stats_w is not None), f"{what}: the statistics query disagrees with the wrapper's"
     if tiles > 0:
-        out = contract("zsv_conv3d_fwd_full (statistics)", fwd(None, None, 0, "bn_partials", tiles),
-                       {"y": (F32, ys), "bn_partials": (F32, (2, d.Cout, tiles))}, {"ws": nf}, shifted=True, ins=pick(o, "x", "w"))
+        out = contract("zsv_conv3d_fwd_full (statistics)",
+                       lambda p: fwd(None, None, 0, "bn_partials", tiles)(p) if tiles_for(p) else fwd(None, None, 0, None, 0)(p),
+                       {"y": (F32, ys), "bn_partials": (F32, (2, d.Cout, tiles))}, {"ws": nf}, shifted=True, ins=pick(o, "x", "w"),
+                       defined=partials_written, route=what, reference=y_reference("y"))
         same_bytes(out["y"], yw_stats, f"{what}: forward with the statistics epilogue")
         same_bytes(out["bn_partials"], stats_w, f"{what}: statistics")
 
     # ---- input gradient ----
     dx = contract("zsv_conv3d_dgrad", lambda p: L.zsv_conv3d_dgrad(dp, p["dy"], p["w"], p["dx"], p["ws"], nd, None),
-                  {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True, ins=pick(o, "dy", "w"))["dx"]
+                  {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True, ins=pick(o, "dy", "w"), route=what)["dx"]
     same_bytes(dx, xg.grad, f"{what}: dgrad")
     ROWS_RUN[(row.table, "dgrad")].add(row.name)
     if L.zsv_conv3d_dgrad_add_supported(dp):
         dxa = contract("zsv_conv3d_dgrad_add", lambda p: L.zsv_conv3d_dgrad_add(dp, p["dy"], p["w"], p["add"], p["dx"], p["ws"], nd, None),
-                       {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True, ins=pick(o, "dy", "w", "add"))["dx"]
+                       {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True, ins=pick(o, "dy", "w", "add"), route=what)["dx"]
         T.close(dxa, dx.double() + o["add"].double(), rtol=1e-6, what=f"{what}: dgrad + shortcut gradient")
     for st in (1, 2):
         if L.zsv_conv3d_dgrad_add_strided_supported(dp, st, 2, 2):
             sub = torch.randn((d.N, d.Cin, -(-d.Ti // st), d.Hi // 2, d.Wi // 2), generator=g).to(DEV)
             dxs = contract("zsv_conv3d_dgrad_add_strided",
                            lambda p: L.zsv_conv3d_dgrad_add_strided(dp, p["dy"], p["w"], p["sub"], st, 2, 2, p["dx"], p["ws"], nd, None),
-                           {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True, ins=dict(pick(o, "dy", "w"), sub=sub))["dx"]
+                           {"dx": (F32, row.xs)}, {"ws": nd}, shifted=True, ins=dict(pick(o, "dy", "w"), sub=sub), route=what)["dx"]
             ref = dx.double()
             ref[:, :, ::st, :2 * (d.Hi // 2):2, :2 * (d.Wi // 2):2] += sub.double()
             T.close(dxs, ref, rtol=1e-6, what=f"{what}: dgrad + strided shortcut gradient (st = {st})")
 
     # ---- weight gradient ----
+    def dw_reference(want, rtol):
+        return lambda got: T.close(got["dw"], _conv_reference(row, o, want), rtol=rtol, what=f"{what}: wgrad on element-aligned operands, against fp64")
+
+    rtol = 5e-5 if row.table == "stem_rows" else 2e-5              # (test_stem_weight_gradient_row_kernel; the other tables' tests)
     dw = contract("zsv_conv3d_wgrad", lambda p: L.zsv_conv3d_wgrad(dp, p["x"], p["dy"], p["dw"], p["ws"], nw, None),
-                  {"dw": (F32, row.ws)}, {"ws": nw}, shifted=True, ins=pick(o, "x", "dy"))["dw"]
+                  {"dw": (F32, row.ws)}, {"ws": nw}, shifted=True, ins=pick(o, "x", "dy"), route=what, reference=dw_reference("dw", rtol))["dw"]
     same_bytes(dw, wg.grad, f"{what}: wgrad")
     ROWS_RUN[(row.table, "wgrad")].add(row.name)
     nm = int(L.zsv_conv3d_wgrad_mask_bytes(dp))
     dwm = contract("zsv_conv3d_wgrad_masked",
                    lambda p: [L.zsv_conv3d_wgrad_mask(dp, p["mask"], None) if nm else 0,
                               L.zsv_conv3d_wgrad_masked(dp, p["x"], p["dy"], p["dw"], p["ws"], nw, p["mask"] if nm else None, None)],
-                   {"dw": (F32, row.ws)}, {"ws": nw, "mask": nm}, shifted={"ws"}, ins=pick(o, "x", "dy"))["dw"]
+                   {"dw": (F32, row.ws)}, {"ws": nw, "mask": nm}, shifted={"ws"}, ins=pick(o, "x", "dy"), route=what,
+                   reference=dw_reference("dw", rtol))["dw"]
     same_bytes(dwm, dw, f"{what}: wgrad with a kept tap-validity table")
 
     # ---- the BatchNorm + ReLU folded into the convolution ----
@@ -340,13 +389,16 @@ def _conv_entry_points(row, tag):
         if tiles > 0:
             outs["bn_partials"] = (F32, (2, d.Cout, tiles))
         out = contract("zsv_conv3d_fwd_pre",
-                       lambda p: L.zsv_conv3d_fwd_pre(dp, p["x"], p["coef"], pitch, p["w"], p["y"], p.get("bn_partials"), tiles, p["ws"], nf, None),
-                       outs, {"ws": nf}, shifted=True, ins=pick(o, "x", "coef", "w"))
+                       lambda p: L.zsv_conv3d_fwd_pre(dp, p["x"], p["coef"], pitch, p["w"], p["y"], *((p["bn_partials"], tiles) if tiles and tiles_for(p)
+                                                                                                   else (None, 0)), p["ws"], nf, None),
+                       outs, {"ws": nf}, shifted=True, ins=pick(o, "x", "coef", "w"), aligned={"coef"}, defined=partials_written, route=what,
+                       reference=y_reference("y_pre"))
         same_bytes(out["y"], yp.detach(), f"{what}: forward through BatchNorm + ReLU")
         if tiles > 0:
             same_bytes(out["bn_partials"], sp, f"{what}: statistics of the forward through BatchNorm + ReLU")
         dwp = contract("zsv_conv3d_wgrad_pre", lambda p: L.zsv_conv3d_wgrad_pre(dp, p["x"], p["coef"], pitch, p["dy"], p["dw"], p["ws"], nw, None),
-                       {"dw": (F32, row.ws)}, {"ws": nw}, shifted=True, ins=pick(o, "x", "coef", "dy"))["dw"]
+                       {"dw": (F32, row.ws)}, {"ws": nw}, shifted=True, ins=pick(o, "x", "coef", "dy"), aligned={"coef"}, route=what,
+                       reference=dw_reference("dw_pre", 5e-5))["dw"]       # (test_batchnorm_relu_folded_into_the_temporal_convolution)
         same_bytes(dwp, wp.grad, f"{what}: wgrad through BatchNorm + ReLU")
 
 
@@ -415,7 +467,7 @@ def test_weight_panels(case):
                      lambda p: [pack(p, 0, 0, panel_bytes(0, 0)),
                                 L.zsv_conv3d_fwd_pre_panel(dp, p["x"], p["coef"], pitch, p["w"], p["y"], None, 0, p["ws"], nf, None, p["panel"],
                                                            panel_bytes(0, 0))],
-                     {"y": (F32, ys)}, {"ws": nf, "panel": panel_bytes(0, 0)}, shifted={"ws"}, ins=pick(o, "x", "coef", "w"))["y"]
+                     {"y": (F32, ys)}, {"ws": nf, "panel": panel_bytes(0, 0)}, shifted={"ws"}, ins=pick(o, "x", "coef", "w"), aligned={"coef"})["y"]
         with torch.no_grad():
             same_bytes(y, ops.conv3d_pre(o["x"], o["coef"], o["w"], stride, pad), f"{name}: forward through BatchNorm + ReLU")
     for st in (1, 2):
@@ -456,11 +508,16 @@ def test_channel_sum_and_relu_bwd_bias(shape):
     db = contract("zsv_channel_sum", lambda p: L.zsv_channel_sum(p["dy"], n, c, s, p["db"], p["ws"], nb, None), {"db": (F32, (c,))}, {"ws": nb},
                   ins=pick(o, "dy"))["db"]
     same_bytes(db, ops.channel_sum(o["dy"]), "channel_sum")
-    out = contract("zsv_relu_bwd_bias", lambda p: L.zsv_relu_bwd_bias(p["dy"], p["y"], p["dx"], n, c, s, p["db"], p["ws"], nb, None),
-                   {"dx": (F32, shape), "db": (F32, (c,))}, {"ws": nb}, ins=pick(o, "dy", y="x"))
     ref = torch.where(o["x"] > 0, o["dy"], torch.zeros_like(o["dy"]))
-    assert torch.equal(out["dx"], ref)
-    T.close(out["db"], ref.double().sum(dim=(0, 2, 3, 4)), what="bias gradient")        # (test_relu_bwd_bias_on_misaligned_views)
+
+    def masked_and_summed(got, what="bias gradient"):                                     # (test_relu_bwd_bias_on_misaligned_views)
+        assert torch.equal(got["dx"], ref)
+        T.close(got["db"], ref.double().sum(dim=(0, 2, 3, 4)), what=what)
+
+    out = contract("zsv_relu_bwd_bias", lambda p: L.zsv_relu_bwd_bias(p["dy"], p["y"], p["dx"], n, c, s, p["db"], p["ws"], nb, None),
+                   {"dx": (F32, shape), "db": (F32, (c,))}, {"ws": nb}, ins=pick(o, "dy", y="x"), route="x".join(map(str, shape)),
+                   reference=lambda got: masked_and_summed(got, "bias gradient on element-aligned operands"))
+    masked_and_summed(out)
     ROWS_RUN[("BN_CASES", "channel_sum")].add(shape)
 
 
@@ -520,7 +577,7 @@ def test_batchnorm_entry_points(shape, use_res, relu):
         out = contract("zsv_bn_fwd_train_coeffs",
                        lambda p: L.zsv_bn_fwd_train_coeffs(p["x"], n, c, s, p["gamma"], p["beta"], p["save_mean"], p["save_invstd"], p["running_mean"],
                                                            p["running_var"], 0.1, 1e-5, None, 0, p["coef"], pitch, p["ws"], nb, None),
-                       dict(stat_outs, coef=(F32, (2, pitch))), {"ws": nb}, ins=pick(o, "x", "gamma", "beta"))
+                       dict(stat_outs, coef=(F32, (2, pitch))), {"ws": nb}, ins=pick(o, "x", "gamma", "beta"), aligned={"coef"})
         assert int(torch.count_nonzero(out["coef"][:, c:])) == 0, "coef entries C .. coef_pitch-1 must be zero"
         rm, rv = o["rm"].clone(), o["rv"].clone()
         _, coef_w = ops._BatchNormDeferred.apply(o["x"], o["gamma"], o["beta"], rm, rv, 0.1, 1e-5, None)
@@ -896,7 +953,7 @@ def test_fp8_blob_and_forward(case):
     y = contract("zsv_conv3d_fp8_pack + zsv_conv3d_fp8_fwd",
                  lambda q: [L.zsv_conv3d_fp8_pack(byref(d), q["w"], None, q["shift"], q["blob"], None),
                             L.zsv_conv3d_fp8_fwd(byref(d), q["x"], q["blob"], q["residual"], 1 if relu else 0, q["y"], None)],
-                 {"y": (U8, ys)}, {"blob": nb}, ins=dict(w=wgt, shift=shift, x=xb, residual=rb))["y"]
+                 {"y": (U8, ys)}, {"blob": nb}, ins=dict(w=wgt, shift=shift, x=xb, residual=rb), aligned={"y"})["y"]
     want = inference.conv_fp8(d, xb, inference.pack_conv_fp8(d, wgt, None, shift), rb, relu)
     same_bytes(y, want.view(U8), "conv_fp8: y")
     assert int(torch.count_nonzero(y[..., cout:])) == 0, "pad channels must be written as zero"
@@ -998,7 +1055,7 @@ def test_channels_last_pools(shape, kernel, pad):
     codes = torch.full((n, t, h, w, cp8), 0x55, dtype=U8)
     codes[..., :c] = (torch.randn((n, t, h, w, c), generator=g) * 40.0).clamp(-448.0, 448.0).to(F8.FP8).view(U8)
     x8 = codes.to(DEV).view(F8.FP8)
-    y8 = contract("zsv_maxpool3d_fp8", lambda q: L.zsv_maxpool3d_fp8(q["x"], *geom, q["y"], None), {"y": (U8, (n, to, ho, wo, cp8))}, ins=dict(x=x8))["y"]
+    y8 = contract("zsv_maxpool3d_fp8", lambda q: L.zsv_maxpool3d_fp8(q["x"], *geom, q["y"], None), {"y": (U8, (n, to, ho, wo, cp8))}, ins=dict(x=x8), aligned={"y"})["y"]
     same_bytes(y8, inference.maxpool3d_fp8(x8, c, kernel, pad).view(U8), "maxpool3d_fp8")
     m8 = contract("zsv_meanpool_fp8", lambda q: L.zsv_meanpool_fp8(q["x"], n, s, c, q["out"], None), {"out": (F32, (n, c))}, ins=dict(x=x8))["out"]
     same_bytes(m8, inference.meanpool_fp8(x8, c), "meanpool_fp8")
@@ -1068,7 +1125,7 @@ def test_bn_eval_coeffs(c):
     o = _bn_operands((2, c, 1, 1, 1))
     pitch = (c + 15) // 16 * 16
     coef = contract("zsv_bn_eval_coeffs", lambda p: L.zsv_bn_eval_coeffs(c, p["gamma"], p["beta"], p["rm"], p["rv"], 1e-5, p["coef"], pitch, None),
-                    {"coef": (F32, (2, pitch))}, ins=pick(o, "gamma", "beta", "rm", "rv"))["coef"]
+                    {"coef": (F32, (2, pitch))}, ins=pick(o, "gamma", "beta", "rm", "rv"), aligned={"coef"})["coef"]
     _, coef_w = ops._BatchNormFrozenDeferred.apply(o["x"], o["gamma"], o["beta"], o["rm"], o["rv"], 1e-5)
     same_bytes(coef, coef_w, "bn_eval_coeffs")
     assert int(torch.count_nonzero(coef[:, c:])) == 0, "coef entries C .. coef_pitch-1 must be zero"
@@ -1196,9 +1253,21 @@ def test_every_entry_point_ran_and_on_every_row(capsys):
         print("\nworkspace / output contract: (entry point, case x switch combinations run)")
         for name in sorted(COUNTS):
             print(f"  {name:68s} {COUNTS[name]:5d}")
+        print("element-aligned runs (fp32 / uint8 tensors 4, 8, 12 / 1, 2, 3 bytes past a 256-byte boundary) per entry point")
+        for name in sorted(COUNTS):
+            print(f"  {name:68s} {ALIGN_RUNS[name]:5d}")
+        changed = sum(len(v) for k, v in ROUTE_SEEN.items() if ROUTE_CHANGES[k] is not None)
+        print(f"ROUTE_CHANGES: {sum(1 for v in ROUTE_CHANGES.values() if v is not None)} rows whose kernel family follows the alignment, {changed} calls under them")
     assert COUNTS, "nothing was recorded: this test reads what the other tests of the file record -- run the file as a whole, in order"
     missing = [e for e in ENTRY_POINTS if COUNTS[e] == 0]
     assert not missing, f"entry points that ran on no case (was the whole file run?): {missing}"
+    # (h): an element-aligned run for every entry point on every combination the other runs cover
+    short = {e: (ALIGN_RUNS[e], COUNTS[e]) for e in ENTRY_POINTS if ALIGN_RUNS[e] != (0 if e in NO_ELEMENT_OPERANDS else COUNTS[e])}
+    assert not short, f"element-aligned runs vs combinations run: {short}"
+    never = sorted(k for k in ROUTE_CHANGES if k not in ROUTE_SEEN)
+    assert not never, f"ROUTE_CHANGES lists calls that never ran: {never}"
+    slack = sorted(k for k, equal in ROUTE_SEEN.items() if ROUTE_CHANGES[k] is not None and any(equal))
+    assert not slack, f"ROUTE_CHANGES lists calls whose element-aligned run gave the first run's bits (take them out): {slack}"
     for table in CONV_TABLES:
         names = {r.name for r in CONV_ROWS if r.table == table}
         assert len(names) >= (1 if table == "slab_sum_rows" else 2), f"{table}: GPU_ROW_LIMIT left {len(names)} row(s)"

@@ -1660,6 +1660,7 @@ static int bf16_fwd_impl(const zsv_conv_desc* d, const void* x, const void* blob
     const int st = bf16_check(d);
     if (st != ZSV_OK) return st;
     if (x == nullptr || blob == nullptr || y == nullptr) return ZSV_E_NULL;
+    if (!aligned16(x, blob, residual, y)) return ZSV_E_UNSUPPORTED;
     const bool folded = bf16_folded(d);
     Bf16Params p;
     const int bm = bf16_bm(d->Cout);
@@ -1865,6 +1866,7 @@ int zsv_conv3d_bf16_dgrad(const zsv_conv_desc* d, const void* dz, const void* bl
     const int st = dgrad_plan(d, &pl);
     if (st != ZSV_OK) return st;
     if (dz == nullptr || blob == nullptr || dx == nullptr) return ZSV_E_NULL;
+    if (!aligned16(dz, blob, fanin, dx)) return ZSV_E_UNSUPPORTED;
     if (pl.stride1) return bf16_fwd_impl(&pl.d1, dz, blob, fanin, 0, dx, nullptr, 0, nullptr, stream, 1);
     const __bf16* wp = (const __bf16*)blob;
     const float* shift = (const float*)((const char*)blob + (size_t)pl.total_q * pl.p.Mp * 32 * 2);
@@ -1884,6 +1886,7 @@ int zsv_clip_to_bf16(const float* x, int32_t N, int32_t C, int32_t T, int32_t H,
     if (N <= 0 || C <= 0 || C > 4 || T <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0 || Hp < H + padH || Wp < W + padW)
         return ZSV_E_BAD_SHAPE;
     if (x == nullptr || out == nullptr) return ZSV_E_NULL;
+    if (!aligned16(out)) return ZSV_E_UNSUPPORTED;
     const long total = (long)N * T * Hp * Wp;
     if (total * 4 >= (1L << 31)) return ZSV_E_TOO_LARGE;
     hipLaunchKernelGGL(clip_to_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, C, T,
@@ -1900,6 +1903,7 @@ int zsv_maxpool3d_bf16(const void* x, int32_t N, int32_t C, int32_t Ti, int32_t 
         Ho <= 0 || Wo <= 0)
         return ZSV_E_BAD_SHAPE;
     if (x == nullptr || y == nullptr) return ZSV_E_NULL;
+    if (!aligned16(x, y)) return ZSV_E_UNSUPPORTED;
     const int G = round_up(C, 32) / 8;
     const long total = (long)N * To * Ho * Wo * G;
     if ((long)N * Ti * Hi * Wi * G >= (1L << 31)) return ZSV_E_TOO_LARGE;
@@ -1948,6 +1952,7 @@ int zsv_conv3d_fp8_fwd(const zsv_conv_desc* d, const void* x, const void* blob, 
     const int st = fp8_check(d);
     if (st != ZSV_OK) return st;
     if (x == nullptr || blob == nullptr || y == nullptr) return ZSV_E_NULL;
+    if (!aligned16(x, blob, residual, y)) return ZSV_E_UNSUPPORTED;
     const bool folded = bf16_folded(d);
     Bf16Params p;
     const int bm = bf16_bm(d->Cout);
@@ -2010,6 +2015,7 @@ int zsv_conv3d_fp8_fwd(const zsv_conv_desc* d, const void* x, const void* blob, 
 int zsv_meanpool_fp8(const void* x, int32_t N, int32_t S, int32_t C, float* out, void* stream) {
     if (N <= 0 || S <= 0 || C <= 4) return ZSV_E_BAD_SHAPE;
     if (x == nullptr || out == nullptr) return ZSV_E_NULL;
+    if (!aligned16(x)) return ZSV_E_UNSUPPORTED;
     hipLaunchKernelGGL(meanpool_fp8_kernel, dim3((C + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)x, S,
                        round_up(C, 64), C, out);
     return launch_status();
@@ -2018,6 +2024,7 @@ int zsv_meanpool_fp8(const void* x, int32_t N, int32_t S, int32_t C, float* out,
 int zsv_meanpool_bf16(const void* x, int32_t N, int32_t S, int32_t C, float* out, void* stream) {
     if (N <= 0 || S <= 0 || C <= 4) return ZSV_E_BAD_SHAPE;
     if (x == nullptr || out == nullptr) return ZSV_E_NULL;
+    if (!aligned16(x)) return ZSV_E_UNSUPPORTED;
     hipLaunchKernelGGL(meanpool_bf16_kernel, dim3((C + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, S,
                        round_up(C, 32), C, out);
     return launch_status();

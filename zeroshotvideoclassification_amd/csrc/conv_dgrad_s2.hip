@@ -61,7 +61,9 @@ __global__ __launch_bounds__(256) void dgrad_s2_pack_kernel(const float* __restr
 }
 
 // X4: dy clips are whole 16-byte pieces (S % 4 == 0; temporal form: frames too): one 16-byte DMA instruction per image row
-template <int BN, int KIND, bool X4>
+// PAIR (spatial form): dx is 8-byte aligned, the classes (rh, 0) and (rh, 1) of a voxel go out as one 8-byte store; a dx that is only
+// 4-byte aligned (include/zsv_hip.h: every fp32 tensor may be) gets the same values from two 4-byte stores.
+template <int BN, int KIND, bool X4, bool PAIR = true>
 __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_kernel(DgradS2Params prm, const float* __restrict__ Wp,
                                                                const float* __restrict__ DY, float* __restrict__ DX) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -242,8 +244,15 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_kernel(DgradS2Params prm
                 float* o = base + (size_t)m * prm.oS;
                 if constexpr (KIND == KIND_HW) {
                     if (sub != nullptr) acc[0][i][j][r4] += sub[(size_t)m * sub_pitch];
-                    *reinterpret_cast<float2*>(o) = float2{acc[0][i][j][r4], acc[1][i][j][r4]};
-                    *reinterpret_cast<float2*>(o + prm.oW) = float2{acc[2][i][j][r4], acc[3][i][j][r4]};
+                    if constexpr (PAIR) {
+                        *reinterpret_cast<float2*>(o) = float2{acc[0][i][j][r4], acc[1][i][j][r4]};
+                        *reinterpret_cast<float2*>(o + prm.oW) = float2{acc[2][i][j][r4], acc[3][i][j][r4]};
+                    } else {
+                        o[0] = acc[0][i][j][r4];
+                        o[1] = acc[1][i][j][r4];
+                        o[prm.oW] = acc[2][i][j][r4];
+                        o[prm.oW + 1] = acc[3][i][j][r4];
+                    }
                 } else {
                     o[0] = acc[0][i][j][r4];
                     o[prm.oHW] = acc[1][i][j][r4];
@@ -315,15 +324,15 @@ size_t dgrad_s2_workspace_bytes(const zsv_conv_desc* d) {
     return s2_panel_bytes(d, pl) + (pl.ks > 1 ? (size_t)pl.ks * out_bytes : 0);
 }
 
-template <int BN, int KIND, bool X4>
+template <int BN, int KIND, bool X4, bool PAIR = true>
 static int s2_launch(const DgradS2Params& p, const float* wp, const float* dy, float* out, hipStream_t stream) {
     constexpr int NTAP = S2Kind<KIND>::NTAP;
     constexpr int MAXSEG = KIND == KIND_T ? 2 * BN / 64 : (BN == 128 ? 4 : 3);
     constexpr int LDS_BYTES = 2 * (NTAP * 8 * 64 + 8 * (X4 ? 272 : 64 * MAXSEG + 16)) * 4;          // as in the kernel
-    static const hipError_t attr = hipFuncSetAttribute((const void*)conv_dgrad_s2_kernel<BN, KIND, X4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    static const hipError_t attr = hipFuncSetAttribute((const void*)conv_dgrad_s2_kernel<BN, KIND, X4, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     if (attr != hipSuccess) return ZSV_E_LAUNCH;
     const long blocks = (long)p.tiles_m * ((p.P + BN - 1) / BN) * p.ksplit;
-    hipLaunchKernelGGL((conv_dgrad_s2_kernel<BN, KIND, X4>), dim3((unsigned)blocks), dim3(256), LDS_BYTES, stream, p, wp, dy, out);
+    hipLaunchKernelGGL((conv_dgrad_s2_kernel<BN, KIND, X4, PAIR>), dim3((unsigned)blocks), dim3(256), LDS_BYTES, stream, p, wp, dy, out);
     return launch_status();
 }
 template <int BN, int KIND>
@@ -343,7 +352,6 @@ int dgrad_s2(const zsv_conv_desc* d, const float* dy, const float* w, const floa
     if (!s2_plan(d, pl)) return ZSV_E_UNSUPPORTED;
     if (sub != nullptr && !dgrad_s2_sub_supported(d, sub_st, 2, 2)) return ZSV_E_UNSUPPORTED;
     if (!workspace || workspace_bytes < dgrad_s2_workspace_bytes(d) || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ZSV_E_WORKSPACE;
-    if ((reinterpret_cast<uintptr_t>(dx) & 7) != 0) return ZSV_E_UNSUPPORTED;
     const int ntap = pl.kind == KIND_HW ? 9 : 3;
     DgradS2Params p;
     p.M = d->Cin; p.tiles_m = pl.tiles_m; p.Mp = pl.tiles_m * 64;
@@ -377,7 +385,11 @@ int dgrad_s2(const zsv_conv_desc* d, const float* dy, const float* w, const floa
     }
     float* out = pl.ks > 1 ? slabs : dx;
     int st;
-    if (pl.kind == KIND_HW) st = pl.bn == 128 ? s2_launch_x<128, KIND_HW>(x4, p, wp, dy, out, stream) : s2_launch_x<64, KIND_HW>(x4, p, wp, dy, out, stream);
+    // the spatial form stores pairs: a dx off an 8-byte boundary takes the 4-byte stores (and the 4-byte image DMAs: one more
+    // instantiation per tile width, the same arithmetic); the temporal form and the slabs of a K-part run never store pairs
+    if (pl.kind == KIND_HW && (reinterpret_cast<uintptr_t>(out) & 7) != 0)
+        st = pl.bn == 128 ? s2_launch<128, KIND_HW, false, false>(p, wp, dy, out, stream) : s2_launch<64, KIND_HW, false, false>(p, wp, dy, out, stream);
+    else if (pl.kind == KIND_HW) st = pl.bn == 128 ? s2_launch_x<128, KIND_HW>(x4, p, wp, dy, out, stream) : s2_launch_x<64, KIND_HW>(x4, p, wp, dy, out, stream);
     else st = pl.bn == 128 ? s2_launch_x<128, KIND_T>(x4, p, wp, dy, out, stream) : s2_launch_x<64, KIND_T>(x4, p, wp, dy, out, stream);
     if (st || pl.ks == 1) return st;
     return splitk_reduce(slabs, pl.ks, p.slab_elems, d->Cin, p.oS, nullptr, 0, dx, stream);

@@ -23,7 +23,6 @@ static inline unsigned ew_blocks(long work_items) {
     if (b < 1) b = 1;
     return (unsigned)b;
 }
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int OP>   // 0 relu fwd (a), 1 relu bwd (a = dy, b = y), 2 add_relu (a + b)
 __global__ __launch_bounds__(256) void ew_kernel(const float* __restrict__ a, const float* __restrict__ b,

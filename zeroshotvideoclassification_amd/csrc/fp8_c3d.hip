@@ -107,6 +107,7 @@ int zsv_maxpool3d_fp8(const void* x, int32_t N, int32_t C, int32_t Ti, int32_t H
         Ho <= 0 || Wo <= 0)
         return ZSV_E_BAD_SHAPE;
     if (x == nullptr || y == nullptr) return ZSV_E_NULL;
+    if (!aligned16(x, y)) return ZSV_E_UNSUPPORTED;
     const int G = zsv_fp8_channel_pitch(C) / 16;
     const long total = (long)N * To * Ho * Wo * G;
     if ((long)N * Ti * Hi * Wi * G >= (1L << 31)) return ZSV_E_TOO_LARGE;

@@ -558,6 +558,7 @@ static int bn_cl_fwd_train_impl(const void* z, const void* residual, int64_t R, 
     const int st = cl_shape(R, C, &sh, &nb);
     if (st != ZSV_OK) return st;
     if (!z || !y || !save_mean || !save_invstd || !workspace) return ZSV_E_NULL;
+    if (!aligned16(z, residual, y)) return ZSV_E_UNSUPPORTED;
     if (workspace_bytes < cl_workspace_bytes(sh, nb)) return ZSV_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float* partial = (float*)workspace;
@@ -593,6 +594,7 @@ int zsv_bn_cl_bwd(const void* dy, const void* y, const void* z, int64_t R, int32
     if (st != ZSV_OK) return st;
     if (!dy || !z || !dz || !save_mean || !save_invstd || !workspace) return ZSV_E_NULL;
     if (relu_mask && !y && !fwd_coef) return ZSV_E_NULL;
+    if (!aligned16(dy, y, z, dz, g_out)) return ZSV_E_UNSUPPORTED;
     if (workspace_bytes < cl_workspace_bytes(sh, nb)) return ZSV_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float* partial = (float*)workspace;
@@ -622,6 +624,7 @@ int zsv_bn_cl_fwd_eval(const void* z, const void* residual, int64_t R, int32_t C
     const int st = cl_shape(R, C, &sh, &nb);
     if (st != ZSV_OK) return st;
     if (!z || !y || !running_mean || !running_var || !coef) return ZSV_E_NULL;
+    if (!aligned16(z, residual, y)) return ZSV_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(bn_cl_eval_coef_kernel, dim3((sh.Cp + 127) / 128), dim3(128), 0, s, C, sh.Cp, gamma, beta, running_mean,
                        running_var, eps, coef);
@@ -648,6 +651,7 @@ int zsv_bn_cl_bwd_eval(const void* dy, const void* y, const void* z, int64_t R, 
     if (!dy || !dz || !coef) return ZSV_E_NULL;
     const int mask = !relu_mask ? 0 : (y ? 1 : 2);          // 1: the saved output, 2: recomputed from z and the forward's coefficients
     if ((sums || mask == 2) && !z) return ZSV_E_NULL;
+    if (!aligned16(dy, y, z, dz, g_out)) return ZSV_E_UNSUPPORTED;
     if (sums && (!workspace || workspace_bytes < cl_workspace_bytes(sh, nb))) return ZSV_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float* partial = (float*)workspace;
@@ -679,6 +683,7 @@ int zsv_maxpool3d_bf16_bwd(const void* dy, const void* x, int32_t N, int32_t C, 
         Ho <= 0 || Wo <= 0)
         return ZSV_E_BAD_SHAPE;
     if (!dy || !x || !dx) return ZSV_E_NULL;
+    if (!aligned16(dy, x, dx)) return ZSV_E_UNSUPPORTED;
     const int G = (C + 31) / 32 * 32 / 8;
     if ((long)N * Ti * Hi * Wi * G >= (1L << 31)) return ZSV_E_TOO_LARGE;
     hipStream_t s = (hipStream_t)stream;
@@ -699,6 +704,7 @@ int zsv_relu_bias_bwd_cl(const void* dy, const void* y, int64_t R, int32_t C, vo
     const int st = cl_shape(R, C, &sh, &nb);
     if (st != ZSV_OK) return st;
     if (!dy || !y || !g_out || !workspace) return ZSV_E_NULL;
+    if (!aligned16(dy, y, g_out)) return ZSV_E_UNSUPPORTED;
     if (workspace_bytes < cl_workspace_bytes(sh, nb)) return ZSV_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float* partial = (float*)workspace;
@@ -711,6 +717,7 @@ int zsv_relu_bias_bwd_cl(const void* dy, const void* y, int64_t R, int32_t C, vo
 int zsv_cl_bf16_to_ncs_f32(const void* x, int32_t N, int32_t S, int32_t C, float* out, void* stream) {
     if (N <= 0 || S <= 0 || C <= 4) return ZSV_E_BAD_SHAPE;
     if (!x || !out) return ZSV_E_NULL;
+    if (!aligned16(x)) return ZSV_E_UNSUPPORTED;
     const int Cp = (C + 31) / 32 * 32;
     hipLaunchKernelGGL(cl_bf16_to_ncs_f32_kernel, dim3((S + 63) / 64, Cp / 32, N), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)x, S, C, Cp, out);
@@ -720,6 +727,7 @@ int zsv_cl_bf16_to_ncs_f32(const void* x, int32_t N, int32_t S, int32_t C, float
 int zsv_ncs_f32_to_cl_bf16(const float* x, int32_t N, int32_t S, int32_t C, void* out, void* stream) {
     if (N <= 0 || S <= 0 || C <= 4) return ZSV_E_BAD_SHAPE;
     if (!x || !out) return ZSV_E_NULL;
+    if (!aligned16(out)) return ZSV_E_UNSUPPORTED;
     const int Cp = (C + 31) / 32 * 32;
     hipLaunchKernelGGL(ncs_f32_to_cl_bf16_kernel, dim3((S + 63) / 64, Cp / 32, N), dim3(256), 0, (hipStream_t)stream, x, S, C, Cp,
                        (unsigned short*)out);
@@ -729,6 +737,7 @@ int zsv_ncs_f32_to_cl_bf16(const float* x, int32_t N, int32_t S, int32_t C, void
 int zsv_meanpool_bf16_bwd(const float* dpooled, int32_t N, int32_t S, int32_t C, void* dx, void* stream) {
     if (N <= 0 || S <= 0 || C <= 4) return ZSV_E_BAD_SHAPE;
     if (!dpooled || !dx) return ZSV_E_NULL;
+    if (!aligned16(dx)) return ZSV_E_UNSUPPORTED;
     const int Cp = (C + 31) / 32 * 32;
     const long total = (long)N * S * Cp;
     hipLaunchKernelGGL(meanpool_cl_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dpooled, S, C,

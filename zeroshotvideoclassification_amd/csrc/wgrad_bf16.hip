@@ -438,6 +438,7 @@ int zsv_conv3d_bf16_wgrad(const zsv_conv_desc* d, const void* x, const void* dz,
     const WgradClPlan pl = wgrad_cl_plan(d);
     if (!pl.ok) return ZSV_E_UNSUPPORTED;
     if (!x || !dz || !dw || !workspace) return ZSV_E_NULL;
+    if (!aligned16(x, dz)) return ZSV_E_UNSUPPORTED;
     if (workspace_bytes < (size_t)pl.slices * pl.taps * pl.Ptot * pl.Qpad * sizeof(float)) return ZSV_E_WORKSPACE;
     WgradClParams p;
     const bool gather = pl.mode >= 2;

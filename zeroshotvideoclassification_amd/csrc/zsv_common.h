@@ -42,6 +42,13 @@ static inline Magic make_magic(unsigned d) {
 }
 __device__ __forceinline__ unsigned mdiv(unsigned p, Magic m) { return (__umulhi(p, m.mul) + p) >> m.shift; }
 
+// The alignment rule of the channels-last bf16 / e4m3 tensors (include/zsv_hip.h, Conventions): their rows are moved as 16-byte
+// pieces, so an entry point refuses (ZSV_E_UNSUPPORTED, before any launch) a tensor that starts off a 16-byte boundary.  The fp32
+// kernels use the same test to choose between a float4 route and an element-wise one.  A null (optional) operand counts as aligned.
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+template <typename... Rest>
+static inline bool aligned16(const void* p, Rest... rest) { return aligned16(p) && aligned16(rest...); }
+
 static inline int launch_status() { return hipGetLastError() == hipSuccess ? 0 : 5; }
 
 }  // namespace zsv
