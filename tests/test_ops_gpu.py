@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import panel_cases  # noqa: E402
 from zeroshotvideoclassification_amd import ops  # noqa: E402
 
 DEV = "cuda"
@@ -1302,6 +1303,9 @@ def test_conv3d_winograd_virtual_width(case, monkeypatch):
     assert not torch.equal(y, y2) and not torch.equal(dx, dx2), "the two paths should not be the same kernel"
 
 
+# At default switches every one of these sizes takes the direct kernel (job kind 0; the two strided input gradients kind 3): they
+# lie below the Winograd kernels' tile thresholds whatever their names say.  panel_cases.SWITCHED_CASES are the rows that lower
+# the thresholds and reach the Winograd pack sites.
 PANEL_CASES = [
     # name, x shape, w shape, stride, padding
     ("winograd_f43", (3, 64, 4, 24, 24), (144, 64, 1, 3, 3), 1, (0, 1, 1)),
@@ -1313,16 +1317,20 @@ PANEL_CASES = [
     ("pointwise", (4, 64, 4, 14, 14), (128, 64, 1, 1, 1), 1, (0, 0, 0)),
     ("full_333", (2, 32, 6, 12, 16), (48, 32, 3, 3, 3), 1, (1, 1, 1)),
 ]
+PANEL_TEST_ROWS = panel_cases.rows(PANEL_CASES)
 
 
-@pytest.mark.parametrize("case", PANEL_CASES, ids=[c[0] for c in PANEL_CASES])
-def test_weight_panels_packed_ahead_of_the_call(case):
+@pytest.mark.parametrize("case", PANEL_TEST_ROWS, ids=[c.name for c in PANEL_TEST_ROWS])
+def test_weight_panels_packed_ahead_of_the_call(case, monkeypatch):
     """C ABI: zsv_conv3d_panel_query / _panel_job / zsv_pack_multi / zsv_conv3d_*_panel.  The panel packed by the multi-job launch
     from the call's own job, fed to the *_panel entry point, gives the bits of the ordinary entry point (which packs per call):
-    forward (plain and with a bias + ReLU) and input gradient; several jobs share one table / one launch."""
+    forward (plain, with a bias + ReLU, and behind a folded BatchNorm + ReLU where the geometry has that form) and input gradient;
+    several jobs share one table / one launch.  Every row names the pack kernel (job kind) it must reach under its switches."""
     import ctypes
     from zeroshotvideoclassification_amd import _lib
-    name, xs, ws_, stride, pad = case
+    for k, v in case.switches.items():
+        monkeypatch.setenv(k, v)
+    name, xs, ws_, stride, pad = case[:5]
     lib = _lib.load()
     g = torch.Generator().manual_seed(len(name))
     x = torch.randn(*xs, generator=g).to(DEV)
@@ -1331,9 +1339,8 @@ def test_weight_panels_packed_ahead_of_the_call(case):
     d = ops.conv_desc(xs, ws_, stride, pad)
     y_shape = (d.N, d.Cout, d.To, d.Ho, d.Wo)
     dy = torch.randn(*y_shape, generator=g).to(DEV)
-    variants = [(0, 0), (0, 1), (1, 0)]                       # (direction, extras)
     jobs, panels = [], {}
-    for direction, extras in variants:
+    for (direction, extras), kind in zip(panel_cases.VARIANTS, case.kinds):
         nb = ctypes.c_size_t(0)
         _lib.check(lib.zsv_conv3d_panel_query(ctypes.byref(d), direction, extras, ctypes.byref(nb)), "query")
         assert nb.value > 0, (name, direction, extras)
@@ -1341,6 +1348,7 @@ def test_weight_panels_packed_ahead_of_the_call(case):
         job = _lib.PackJob()
         _lib.check(lib.zsv_conv3d_panel_job(ctypes.byref(d), direction, extras, w.data_ptr(), panel.data_ptr(), nb.value, ctypes.byref(job)), "job")
         assert job.total * 4 <= nb.value and job.w == w.data_ptr() and job.out == panel.data_ptr()
+        assert job.kind == kind, (name, direction, extras)
         jobs.append(job)
         panels[(direction, extras)] = panel
     first, raw = 0, bytearray()
@@ -1370,13 +1378,43 @@ def test_weight_panels_packed_ahead_of_the_call(case):
     assert torch.equal(dx, dx_ref), (name, "dgrad")
     ref = F.conv3d(x.double().cpu(), w.double().cpu(), stride=stride, padding=pad)
     close(y, F.relu(ref + bias.double().cpu().view(1, -1, 1, 1, 1)), what="forward + bias + relu")
+    pre = bool(lib.zsv_conv3d_pre_supported(ctypes.byref(d)))
+    assert pre or name not in panel_cases.PRE_SUPPORTED
+    if pre:
+        # the forward that reads its input through a folded BatchNorm + ReLU: coefficient rows (scale, shift) of pitch ceil(Cin/16)*16
+        pitch = (d.Cin + 15) // 16 * 16
+        coef = torch.zeros(2, pitch)
+        coef[0, :d.Cin] = torch.rand(d.Cin, generator=g) + 0.5
+        coef[1, :d.Cin] = torch.randn(d.Cin, generator=g)
+        coef = coef.to(DEV)
+        assert coef.data_ptr() % 16 == 0
+        y_ref, y = torch.empty(y_shape, device=DEV), torch.empty(y_shape, device=DEV)
+        _lib.check(lib.zsv_conv3d_fwd_pre(ctypes.byref(d), x.data_ptr(), coef.data_ptr(), pitch, w.data_ptr(), y_ref.data_ptr(), None, 0, ws.data_ptr(), nf,
+                                          None), "fwd pre")
+        p = panels[(0, 0)]
+        _lib.check(lib.zsv_conv3d_fwd_pre_panel(ctypes.byref(d), x.data_ptr(), coef.data_ptr(), pitch, w.data_ptr(), y.data_ptr(), None, 0, ws.data_ptr(), nf,
+                                                None, p.data_ptr(), p.numel()), "fwd pre panel")
+        torch.cuda.synchronize()
+        assert torch.equal(y, y_ref), (name, "forward behind BatchNorm + ReLU")
+        act = F.relu(x.double().cpu() * coef[0, :d.Cin].double().cpu().view(1, -1, 1, 1, 1) + coef[1, :d.Cin].double().cpu().view(1, -1, 1, 1, 1))
+        close(y, F.conv3d(act, w.double().cpu(), stride=stride, padding=pad), what="forward behind BatchNorm + ReLU")
     # a too-small panel is refused, a stem has no panel
     assert lib.zsv_conv3d_fwd_full_panel(ctypes.byref(d), x.data_ptr(), w.data_ptr(), None, None, y.data_ptr(), 0, None, 0, ws.data_ptr(), nf, None,
                                          panels[(0, 0)].data_ptr(), 16) != 0
-    ds = ops.conv_desc((2, 3, 4, 32, 32), (45, 3, 1, 7, 7), (1, 2, 2), (0, 3, 3))
+    sx, sw_, sstride, spad = panel_cases.STEM
+    ds = ops.conv_desc(sx, sw_, sstride, spad)
     nb = ctypes.c_size_t(1)
     _lib.check(lib.zsv_conv3d_panel_query(ctypes.byref(ds), 0, 0, ctypes.byref(nb)), "query stem")
     assert nb.value == 0
+    # ... and its *_panel form refuses before it launches anything
+    x3, w3 = torch.randn(*sx, generator=g).to(DEV), torch.randn(*sw_, generator=g).to(DEV)
+    y3 = torch.full((4 * ds.N * ds.Cout * ds.To * ds.Ho * ds.Wo,), 0xFF, dtype=torch.uint8, device=DEV)
+    n3 = lib.zsv_conv3d_fwd_workspace_bytes(ctypes.byref(ds))
+    ws3 = torch.empty(max(int(n3), 16), dtype=torch.uint8, device=DEV)
+    assert lib.zsv_conv3d_fwd_full_panel(ctypes.byref(ds), x3.data_ptr(), w3.data_ptr(), None, None, y3.data_ptr(), 0, None, 0, ws3.data_ptr(), n3,
+                                         None, panels[(0, 0)].data_ptr(), panels[(0, 0)].numel()) == 6          # ZSV_E_UNSUPPORTED
+    torch.cuda.synchronize()
+    assert bool((y3 == 0xFF).all()), "the refused stem call wrote its output"
 
 
 @pytest.mark.parametrize("xs,cout,k", [((4, 64, 8, 28, 28), 144, (1, 3, 3)), ((2, 64, 4, 14, 14), 64, (3, 3, 3)),

@@ -144,9 +144,25 @@ extern "C" int zsv_conv3d_fwd_add(const zsv_conv_desc* d, const float* x, const 
     return zsv_conv3d_fwd_full(d, x, w, bias, residual, y, fuse_relu, nullptr, 0, workspace, workspace_bytes, stream);
 }
 
-extern "C" int zsv_conv3d_fwd_full(const zsv_conv_desc* d, const float* x, const float* w, const float* bias,
-                                   const float* residual, float* y, int fuse_relu, float* bn_partials,
-                                   int32_t stat_tiles, void* workspace, size_t workspace_bytes, void* stream) {
+// The forward on the direct kernel: the panel at the head of the workspace (`need` bytes in all, sized by the caller's descriptor),
+// the K parts' slabs behind it, summed in order with the bias / ReLU of `p` afterwards.  Probing calls stop after the pack site.
+static int tap_fwd(IgemmParams& p, size_t need, const float* w, int w_m_stride, int w_c_stride, const float* x, const float* bias,
+                   float* y, void* workspace, size_t workspace_bytes, hipStream_t stream, PanelCtx& pc) {
+    if (workspace_bytes < need || !workspace) return ZSV_E_WORKSPACE;
+    const int ks = igemm_tap_ksplit(p);
+    const size_t wbytes = align256(igemm_tap_workspace_bytes(p));
+    const long out_elems = (long)p.M * p.P;
+    float* slabs = ks > 1 ? (float*)((char*)workspace + wbytes) : nullptr;
+    p.ksplit = ks;
+    p.slab_elems = (int)out_elems;
+    const int st = igemm_tap(p, w, w_m_stride, w_c_stride, x, bias, y, workspace, wbytes, slabs, stream, pc);
+    if (st || ks <= 1 || pc.probing()) return st;
+    return splitk_reduce(slabs, ks, out_elems, p.M, p.oS, bias, p.relu, y, stream);
+}
+
+static int fwd_full(const zsv_conv_desc* d, const float* x, const float* w, const float* bias, const float* residual, float* y,
+                    int fuse_relu, float* bn_partials, int32_t stat_tiles, void* workspace, size_t workspace_bytes, hipStream_t stream,
+                    PanelCtx& pc) {
     int st = conv_check(d);
     if (st) return st;
     if (!x || !w || !y) return ZSV_E_NULL;
@@ -154,27 +170,14 @@ extern "C" int zsv_conv3d_fwd_full(const zsv_conv_desc* d, const float* x, const
     if (wino_fwd_applicable(d)) {
         if (bn_partials && (bias || fuse_relu || stat_tiles != wino_fwd_stat_tiles(d))) return ZSV_E_UNSUPPORTED;
         return wino_fwd(d, x, w, bias, residual, fuse_relu ? 1 : 0, bn_partials,
-                        bn_partials ? bn_partials + (size_t)d->Cout * stat_tiles : nullptr, y, workspace, workspace_bytes,
-                        (hipStream_t)stream);
+                        bn_partials ? bn_partials + (size_t)d->Cout * stat_tiles : nullptr, y, workspace, workspace_bytes, stream, pc);
     }
     if (t2_dense(d) && !bias && !fuse_relu && !residual && !bn_partials) {
         const zsv_conv_desc d2 = t2_dense_desc(d);
         IgemmParams p;
         fwd_params(p, &d2, 0);
         p.t2_cin = d->Cin;
-        if (igemm_tap_applicable(p)) {
-            const size_t need = tap_fwd_workspace(&d2);
-            if (workspace_bytes < need || !workspace) return ZSV_E_WORKSPACE;
-            const int ks = igemm_tap_ksplit(p);
-            const size_t wbytes = align256(igemm_tap_workspace_bytes(p));
-            const long out_elems = (long)d->N * d->Cout * d->To * d->Ho * d->Wo;
-            float* slabs = ks > 1 ? (float*)((char*)workspace + wbytes) : nullptr;
-            p.ksplit = ks;
-            p.slab_elems = (int)out_elems;
-            st = igemm_tap(p, w, 0, 0, x, nullptr, y, workspace, wbytes, slabs, (hipStream_t)stream);
-            if (st || ks <= 1 || panel_stop()) return st;
-            return splitk_reduce(slabs, ks, out_elems, d2.Cout, p.oS, nullptr, 0, y, (hipStream_t)stream);
-        }
+        if (igemm_tap_applicable(p)) return tap_fwd(p, tap_fwd_workspace(&d2), w, 0, 0, x, nullptr, y, workspace, workspace_bytes, stream, pc);
     }
     IgemmParams p;
     fwd_params(p, d, fuse_relu);
@@ -187,21 +190,18 @@ extern "C" int zsv_conv3d_fwd_full(const zsv_conv_desc* d, const float* x, const
         p.stat_sq = bn_partials + (size_t)d->Cout * stat_tiles;
         p.tiles_n = stat_tiles;
     }
-    if (igemm_tap_applicable(p)) {
-        if (workspace_bytes < zsv_conv3d_fwd_workspace_bytes(d) || !workspace) return ZSV_E_WORKSPACE;
-        const int ks = igemm_tap_ksplit(p);
-        const size_t wbytes = align256(igemm_tap_workspace_bytes(p));
-        const long out_elems = (long)d->N * d->Cout * d->To * d->Ho * d->Wo;
-        float* slabs = ks > 1 ? (float*)((char*)workspace + wbytes) : nullptr;
-        p.ksplit = ks;
-        p.slab_elems = (int)out_elems;
-        st = igemm_tap(p, w, p.a_m_stride, p.a_c_stride, x, bias, y, workspace, wbytes, slabs, (hipStream_t)stream);
-        if (st || ks <= 1 || panel_stop()) return st;
-        return splitk_reduce(slabs, ks, out_elems, d->Cout, p.oS, bias, fuse_relu ? 1 : 0, y, (hipStream_t)stream);
-    }
-    if (g_panel.mode != PANEL_NONE) return panel_stop() ? ZSV_OK : ZSV_E_UNSUPPORTED;      // (no weight panel on this path: jobs stays 0)
+    if (igemm_tap_applicable(p))
+        return tap_fwd(p, zsv_conv3d_fwd_workspace_bytes(d), w, p.a_m_stride, p.a_c_stride, x, bias, y, workspace, workspace_bytes, stream, pc);
+    if (pc.mode != PANEL_NONE) return pc.probing() ? ZSV_OK : ZSV_E_UNSUPPORTED;      // (no weight panel on this path: jobs stays 0)
     const bool avec = (p.K % 4 == 0) && ((reinterpret_cast<uintptr_t>(w) & 15) == 0);
-    return igemm_generic(p, avec, w, x, bias, y, (hipStream_t)stream);
+    return igemm_generic(p, avec, w, x, bias, y, stream);
+}
+
+extern "C" int zsv_conv3d_fwd_full(const zsv_conv_desc* d, const float* x, const float* w, const float* bias,
+                                   const float* residual, float* y, int fuse_relu, float* bn_partials,
+                                   int32_t stat_tiles, void* workspace, size_t workspace_bytes, void* stream) {
+    PanelCtx pc = {PANEL_NONE};
+    return fwd_full(d, x, w, bias, residual, y, fuse_relu, bn_partials, stat_tiles, workspace, workspace_bytes, (hipStream_t)stream, pc);
 }
 
 // ---- convolution of a BatchNorm + ReLU output that is never materialised -----------------------------------------
@@ -215,9 +215,8 @@ extern "C" int32_t zsv_conv3d_pre_supported(const zsv_conv_desc* d) {
     return igemm_tap_applicable(p) ? 1 : 0;
 }
 
-extern "C" int zsv_conv3d_fwd_pre(const zsv_conv_desc* d, const float* x, const float* pre_coef, int32_t coef_pitch,
-                                  const float* w, float* y, float* bn_partials, int32_t stat_tiles, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+static int fwd_pre(const zsv_conv_desc* d, const float* x, const float* pre_coef, int32_t coef_pitch, const float* w, float* y,
+                   float* bn_partials, int32_t stat_tiles, void* workspace, size_t workspace_bytes, hipStream_t stream, PanelCtx& pc) {
     int st = conv_check(d);
     if (st) return st;
     if (!x || !w || !y || !pre_coef) return ZSV_E_NULL;
@@ -227,7 +226,7 @@ extern "C" int zsv_conv3d_fwd_pre(const zsv_conv_desc* d, const float* x, const 
     if (wino_fwd_applicable(d)) {
         if (bn_partials && stat_tiles != zsv_conv3d_fwd_stat_tiles(d, y)) return ZSV_E_UNSUPPORTED;
         return wino_fwd_pre(d, x, pre_coef, coef_pitch, w, bn_partials, bn_partials ? bn_partials + (size_t)d->Cout * stat_tiles : nullptr,
-                            y, workspace, workspace_bytes, (hipStream_t)stream);
+                            y, workspace, workspace_bytes, stream, pc);
     }
     IgemmParams p;
     fwd_params(p, d, 0);
@@ -239,16 +238,14 @@ extern "C" int zsv_conv3d_fwd_pre(const zsv_conv_desc* d, const float* x, const 
         p.stat_sq = bn_partials + (size_t)d->Cout * stat_tiles;
         p.tiles_n = stat_tiles;
     }
-    if (workspace_bytes < zsv_conv3d_fwd_workspace_bytes(d) || !workspace) return ZSV_E_WORKSPACE;
-    const int ks = igemm_tap_ksplit(p);
-    const size_t wbytes = align256(igemm_tap_workspace_bytes(p));
-    const long out_elems = (long)d->N * d->Cout * d->To * d->Ho * d->Wo;
-    float* slabs = ks > 1 ? (float*)((char*)workspace + wbytes) : nullptr;
-    p.ksplit = ks;
-    p.slab_elems = (int)out_elems;
-    st = igemm_tap(p, w, p.a_m_stride, p.a_c_stride, x, nullptr, y, workspace, wbytes, slabs, (hipStream_t)stream);
-    if (st || ks <= 1 || panel_stop()) return st;
-    return splitk_reduce(slabs, ks, out_elems, d->Cout, p.oS, nullptr, 0, y, (hipStream_t)stream);
+    return tap_fwd(p, zsv_conv3d_fwd_workspace_bytes(d), w, p.a_m_stride, p.a_c_stride, x, nullptr, y, workspace, workspace_bytes, stream, pc);
+}
+
+extern "C" int zsv_conv3d_fwd_pre(const zsv_conv_desc* d, const float* x, const float* pre_coef, int32_t coef_pitch,
+                                  const float* w, float* y, float* bn_partials, int32_t stat_tiles, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    PanelCtx pc = {PANEL_NONE};
+    return fwd_pre(d, x, pre_coef, coef_pitch, w, y, bn_partials, stat_tiles, workspace, workspace_bytes, (hipStream_t)stream, pc);
 }
 
 // one split factor for every residue class of a dgrad call (they share the slabs)
@@ -300,14 +297,14 @@ extern "C" int zsv_conv3d_dgrad(const zsv_conv_desc* d, const float* dy, const f
     return zsv_conv3d_dgrad_add(d, dy, w, nullptr, dx, workspace, workspace_bytes, stream);
 }
 
-extern "C" int zsv_conv3d_dgrad_add(const zsv_conv_desc* d, const float* dy, const float* w, const float* add,
-                                    float* dx, void* workspace, size_t workspace_bytes, void* stream) {
+static int dgrad_add(const zsv_conv_desc* d, const float* dy, const float* w, const float* add, float* dx, void* workspace,
+                     size_t workspace_bytes, hipStream_t stream, PanelCtx& pc) {
     int st = conv_check(d);
     if (st) return st;
     if (!dy || !w || !dx) return ZSV_E_NULL;
     if (add != nullptr && !zsv_conv3d_dgrad_add_supported(d)) return ZSV_E_UNSUPPORTED;
-    if (wino_dgrad_applicable(d)) return wino_dgrad(d, dy, w, add, dx, workspace, workspace_bytes, (hipStream_t)stream);
-    if (dgrad_s2_applicable(d)) return dgrad_s2(d, dy, w, nullptr, 1, dx, workspace, workspace_bytes, (hipStream_t)stream);     // (stride 2: no `add`)
+    if (wino_dgrad_applicable(d)) return wino_dgrad(d, dy, w, add, dx, workspace, workspace_bytes, stream, pc);
+    if (dgrad_s2_applicable(d)) return dgrad_s2(d, dy, w, nullptr, 1, dx, workspace, workspace_bytes, stream, pc);     // (stride 2: no `add`)
     zsv_conv_desc d2;
     int t2_cin = 0;
     if (t2_dense(d)) { t2_cin = d->Cin; d2 = t2_dense_desc(d); d = &d2; }
@@ -318,9 +315,9 @@ extern "C" int zsv_conv3d_dgrad_add(const zsv_conv_desc* d, const float* dy, con
     if (need > 0 && (!workspace || workspace_bytes < need)) return ZSV_E_WORKSPACE;
     float* slabs = ks > 1 ? (float*)((char*)workspace + wbytes) : nullptr;
     IgemmParams p;
-    if (g_panel.mode != PANEL_NONE && (d->sT != 1 || d->sH != 1 || d->sW != 1)) {
+    if (pc.mode != PANEL_NONE && (d->sT != 1 || d->sH != 1 || d->sW != 1)) {
         // class-by-class launches pack one panel per residue class into the same workspace: no single panel to keep
-        if (g_panel.mode == PANEL_QUERY) { g_panel.jobs = 2; return ZSV_OK; }
+        if (pc.mode == PANEL_QUERY) { pc.jobs = 2; return ZSV_OK; }
         return ZSV_E_UNSUPPORTED;
     }
     // residue classes that see no tap (e.g. 7 of the 8 classes of a 1x1x1 stride-2 shortcut) are
@@ -330,7 +327,7 @@ extern "C" int zsv_conv3d_dgrad_add(const zsv_conv_desc* d, const float* dy, con
         for (int rh = 0; rh < d->sH; ++rh)
             for (int rw = 0; rw < d->sW; ++rw)
                 if (dgrad_class_params(p, d, rt, rh, rw) && p.K == 0) any_empty = true;
-    if (any_empty && hipMemsetAsync(dx, 0, (size_t)out_elems * sizeof(float), (hipStream_t)stream) != hipSuccess)
+    if (any_empty && hipMemsetAsync(dx, 0, (size_t)out_elems * sizeof(float), stream) != hipSuccess)
         return ZSV_E_LAUNCH;
     // one launch per residue class; the classes reuse the (stream-ordered) weight workspace
     for (int rt = 0; rt < d->sT; ++rt)
@@ -343,16 +340,21 @@ extern "C" int zsv_conv3d_dgrad_add(const zsv_conv_desc* d, const float* dy, con
                     p.slab_elems = (int)out_elems;
                     p.acc_src = add;
                     p.t2_cin = t2_cin;
-                    st = igemm_tap(p, w, p.a_m_stride, p.a_c_stride, dy, nullptr, dx, workspace, wbytes, slabs,
-                                   (hipStream_t)stream);
+                    st = igemm_tap(p, w, p.a_m_stride, p.a_c_stride, dy, nullptr, dx, workspace, wbytes, slabs, stream, pc);
                 } else {
-                    if (g_panel.mode != PANEL_NONE) return panel_stop() ? ZSV_OK : ZSV_E_UNSUPPORTED;
-                    st = igemm_generic(p, false, w, dy, nullptr, dx, (hipStream_t)stream);
+                    if (pc.mode != PANEL_NONE) return pc.probing() ? ZSV_OK : ZSV_E_UNSUPPORTED;
+                    st = igemm_generic(p, false, w, dy, nullptr, dx, stream);
                 }
                 if (st) return st;
             }
-    if (ks > 1 && !panel_stop()) return splitk_reduce(slabs, ks, out_elems, d->Cin, p.oS, nullptr, 0, dx, (hipStream_t)stream);
+    if (ks > 1 && !pc.probing()) return splitk_reduce(slabs, ks, out_elems, d->Cin, p.oS, nullptr, 0, dx, stream);
     return ZSV_OK;
+}
+
+extern "C" int zsv_conv3d_dgrad_add(const zsv_conv_desc* d, const float* dy, const float* w, const float* add,
+                                    float* dx, void* workspace, size_t workspace_bytes, void* stream) {
+    PanelCtx pc = {PANEL_NONE};
+    return dgrad_add(d, dy, w, add, dx, workspace, workspace_bytes, (hipStream_t)stream, pc);
 }
 
 // ---- dx = dgrad + the gradient of the block's strided 1x1x1 shortcut convolution (resnet.py:240-246: `downsample`), which reads the
@@ -363,13 +365,19 @@ extern "C" int32_t zsv_conv3d_dgrad_add_strided_supported(const zsv_conv_desc* d
     return dgrad_s2_sub_supported(d, st, sh, sw) ? 1 : 0;
 }
 
-extern "C" int zsv_conv3d_dgrad_add_strided(const zsv_conv_desc* d, const float* dy, const float* w, const float* sub, int32_t st,
-                                            int32_t sh, int32_t sw, float* dx, void* workspace, size_t workspace_bytes, void* stream) {
+static int dgrad_add_strided(const zsv_conv_desc* d, const float* dy, const float* w, const float* sub, int32_t st, int32_t sh, int32_t sw,
+                             float* dx, void* workspace, size_t workspace_bytes, hipStream_t stream, PanelCtx& pc) {
     int rc = conv_check(d);
     if (rc) return rc;
     if (!dy || !w || !dx || !sub) return ZSV_E_NULL;
     if (!zsv_conv3d_dgrad_add_strided_supported(d, st, sh, sw)) return ZSV_E_UNSUPPORTED;
-    return dgrad_s2(d, dy, w, sub, st, dx, workspace, workspace_bytes, (hipStream_t)stream);
+    return dgrad_s2(d, dy, w, sub, st, dx, workspace, workspace_bytes, stream, pc);
+}
+
+extern "C" int zsv_conv3d_dgrad_add_strided(const zsv_conv_desc* d, const float* dy, const float* w, const float* sub, int32_t st,
+                                            int32_t sh, int32_t sw, float* dx, void* workspace, size_t workspace_bytes, void* stream) {
+    PanelCtx pc = {PANEL_NONE};
+    return dgrad_add_strided(d, dy, w, sub, st, sh, sw, dx, workspace, workspace_bytes, (hipStream_t)stream, pc);
 }
 
 extern "C" size_t zsv_linear_fwd_workspace_bytes(int32_t rows, int32_t in_features, int32_t out_features) {
@@ -397,18 +405,15 @@ extern "C" int zsv_linear_dgrad(const float* dy, const float* w, float* dx, int3
 
 
 // ---- weight panels kept by the caller (zsv_hip.h) ------------------------------------------------------------------------------
-// query / job run the ordinary entry point with the thread-local panel context set (conv_params.h): the path that would pack a
-// panel reports its size / writes the pack launch down and returns before anything is launched; x / y / workspace are never touched.
+// query / job run the entry point's own body with a PanelCtx that asks for the size / the job (conv_params.h): the path that would
+// pack a panel reports its size / writes the pack launch down and returns before anything is launched; x / y / workspace are never
+// touched.  The *_panel forms run it with the caller's panel, which the pack site takes instead of packing.
 namespace {
-struct PanelScope {
-    PanelScope(int mode, void* ptr, size_t bytes) { g_panel = PanelCtx{mode, ptr, bytes, 0, 0, {}}; }
-    ~PanelScope() { g_panel.mode = PANEL_NONE; g_panel.ptr = nullptr; }
-};
 float* const kDummy = reinterpret_cast<float*>(0x1000);      // non-null, 16-byte aligned, never dereferenced in query / record mode
-int panel_probe(const zsv_conv_desc* d, int32_t direction, int32_t extras, const float* w) {
+int panel_probe(const zsv_conv_desc* d, int32_t direction, int32_t extras, const float* w, PanelCtx& pc) {
     if (direction == 0)
-        return zsv_conv3d_fwd_full(d, kDummy, w, extras ? kDummy : nullptr, nullptr, kDummy, 0, nullptr, 0, kDummy, ~(size_t)0 >> 1, nullptr);
-    return zsv_conv3d_dgrad_add(d, kDummy, w, nullptr, kDummy, kDummy, ~(size_t)0 >> 1, nullptr);
+        return fwd_full(d, kDummy, w, extras ? kDummy : nullptr, nullptr, kDummy, 0, nullptr, 0, kDummy, ~(size_t)0 >> 1, nullptr, pc);
+    return dgrad_add(d, kDummy, w, nullptr, kDummy, kDummy, ~(size_t)0 >> 1, nullptr, pc);
 }
 }  // namespace
 
@@ -418,10 +423,10 @@ extern "C" int zsv_conv3d_panel_query(const zsv_conv_desc* d, int32_t direction,
     int st = conv_check(d);
     if (st) return st;
     if (direction != 0 && direction != 1) return ZSV_E_BAD_SHAPE;
-    PanelScope scope(PANEL_QUERY, nullptr, 0);
-    st = panel_probe(d, direction, extras, kDummy);
+    PanelCtx pc = {PANEL_QUERY};
+    st = panel_probe(d, direction, extras, kDummy, pc);
     if (st) return st;
-    *panel_bytes = g_panel.jobs == 1 ? g_panel.need : 0;
+    *panel_bytes = pc.jobs == 1 ? pc.need : 0;
     return ZSV_OK;
 }
 
@@ -431,41 +436,39 @@ extern "C" int zsv_conv3d_panel_job(const zsv_conv_desc* d, int32_t direction, i
     int st = conv_check(d);
     if (st) return st;
     if (direction != 0 && direction != 1) return ZSV_E_BAD_SHAPE;
-    PanelScope scope(PANEL_RECORD, panel, panel_bytes);
-    st = panel_probe(d, direction, extras, w);
+    PanelCtx pc = {PANEL_RECORD, panel, panel_bytes};
+    st = panel_probe(d, direction, extras, w, pc);
     if (st) return st;
-    if (g_panel.jobs != 1) return ZSV_E_UNSUPPORTED;
-    *job = g_panel.job;
+    if (pc.jobs != 1) return ZSV_E_UNSUPPORTED;
+    *job = pc.job;
     return ZSV_OK;
 }
 
 extern "C" int zsv_conv3d_fwd_full_panel(const zsv_conv_desc* d, const float* x, const float* w, const float* bias,
                                          const float* residual, float* y, int fuse_relu, float* bn_partials, int32_t stat_tiles,
                                          void* workspace, size_t workspace_bytes, void* stream, const void* panel, size_t panel_bytes) {
-    if (!panel) return ZSV_E_NULL;
-    PanelScope scope(PANEL_LAUNCH_ONLY, const_cast<void*>(panel), panel_bytes);
-    return zsv_conv3d_fwd_full(d, x, w, bias, residual, y, fuse_relu, bn_partials, stat_tiles, workspace, workspace_bytes, stream);
+    PanelCtx pc = {PANEL_LAUNCH_ONLY, const_cast<void*>(panel), panel_bytes};
+    return !panel ? ZSV_E_NULL
+                  : fwd_full(d, x, w, bias, residual, y, fuse_relu, bn_partials, stat_tiles, workspace, workspace_bytes, (hipStream_t)stream, pc);
 }
 
 extern "C" int zsv_conv3d_fwd_pre_panel(const zsv_conv_desc* d, const float* x, const float* pre_coef, int32_t coef_pitch,
                                         const float* w, float* y, float* bn_partials, int32_t stat_tiles, void* workspace,
                                         size_t workspace_bytes, void* stream, const void* panel, size_t panel_bytes) {
-    if (!panel) return ZSV_E_NULL;
-    PanelScope scope(PANEL_LAUNCH_ONLY, const_cast<void*>(panel), panel_bytes);
-    return zsv_conv3d_fwd_pre(d, x, pre_coef, coef_pitch, w, y, bn_partials, stat_tiles, workspace, workspace_bytes, stream);
+    PanelCtx pc = {PANEL_LAUNCH_ONLY, const_cast<void*>(panel), panel_bytes};
+    return !panel ? ZSV_E_NULL
+                  : fwd_pre(d, x, pre_coef, coef_pitch, w, y, bn_partials, stat_tiles, workspace, workspace_bytes, (hipStream_t)stream, pc);
 }
 
 extern "C" int zsv_conv3d_dgrad_add_panel(const zsv_conv_desc* d, const float* dy, const float* w, const float* add, float* dx,
                                           void* workspace, size_t workspace_bytes, void* stream, const void* panel, size_t panel_bytes) {
-    if (!panel) return ZSV_E_NULL;
-    PanelScope scope(PANEL_LAUNCH_ONLY, const_cast<void*>(panel), panel_bytes);
-    return zsv_conv3d_dgrad_add(d, dy, w, add, dx, workspace, workspace_bytes, stream);
+    PanelCtx pc = {PANEL_LAUNCH_ONLY, const_cast<void*>(panel), panel_bytes};
+    return !panel ? ZSV_E_NULL : dgrad_add(d, dy, w, add, dx, workspace, workspace_bytes, (hipStream_t)stream, pc);
 }
 
 extern "C" int zsv_conv3d_dgrad_add_strided_panel(const zsv_conv_desc* d, const float* dy, const float* w, const float* sub, int32_t st,
                                                   int32_t sh, int32_t sw, float* dx, void* workspace, size_t workspace_bytes,
                                                   void* stream, const void* panel, size_t panel_bytes) {
-    if (!panel) return ZSV_E_NULL;
-    PanelScope scope(PANEL_LAUNCH_ONLY, const_cast<void*>(panel), panel_bytes);
-    return zsv_conv3d_dgrad_add_strided(d, dy, w, sub, st, sh, sw, dx, workspace, workspace_bytes, stream);
+    PanelCtx pc = {PANEL_LAUNCH_ONLY, const_cast<void*>(panel), panel_bytes};
+    return !panel ? ZSV_E_NULL : dgrad_add_strided(d, dy, w, sub, st, sh, sw, dx, workspace, workspace_bytes, (hipStream_t)stream, pc);
 }

@@ -347,7 +347,7 @@ bool dgrad_s2_sub_supported(const zsv_conv_desc* d, int st, int sh, int sw) {
 }
 
 int dgrad_s2(const zsv_conv_desc* d, const float* dy, const float* w, const float* sub, int sub_st, float* dx, void* workspace,
-             size_t workspace_bytes, hipStream_t stream) {
+             size_t workspace_bytes, hipStream_t stream, PanelCtx& pc) {
     S2Plan pl;
     if (!s2_plan(d, pl)) return ZSV_E_UNSUPPORTED;
     if (sub != nullptr && !dgrad_s2_sub_supported(d, sub_st, 2, 2)) return ZSV_E_UNSUPPORTED;
@@ -367,22 +367,17 @@ int dgrad_s2(const zsv_conv_desc* d, const float* dy, const float* w, const floa
     p.ksplit = pl.ks; p.chunks_per_split = pl.cps;
     p.slab_elems = (int)((long)d->N * d->Cin * p.oS);
     p.sub = sub; p.sub_st = sub ? sub_st : 1; p.subT = sub ? (d->Ti + sub_st - 1) / sub_st : 0;
-    float* wp;
-    int pst;
-    if (!panel_place(s2_panel_bytes(d, pl), workspace, wp, pst)) return pst;
     float* slabs = (float*)((char*)workspace + s2_panel_bytes(d, pl));
     const long total = (long)pl.nchunks * ntap * 8 * p.Mp;
-    if (g_panel.mode == PANEL_RECORD) {
-        pack_job_s2(g_panel.job, PackS2Args{p.M, p.Mp, p.Cout, ntap}, w, wp, total);
-        g_panel.jobs++;
-        return ZSV_OK;
-    }
-    if (g_panel.mode != PANEL_LAUNCH_ONLY) {
+    auto record = [&](zsv_pack_job& job, float* panel) { pack_job_s2(job, PackS2Args{p.M, p.Mp, p.Cout, ntap}, w, panel, total); };
+    auto pack = [&](float* panel) {
         long pb = (total + 255) / 256;
         if (pb > 4096) pb = 4096;
-        hipLaunchKernelGGL(dgrad_s2_pack_kernel, dim3((unsigned)pb), dim3(256), 0, stream, w, wp, p.M, p.Mp, p.Cout, ntap, total);
-        if (hipGetLastError() != hipSuccess) return ZSV_E_LAUNCH;
-    }
+        hipLaunchKernelGGL(dgrad_s2_pack_kernel, dim3((unsigned)pb), dim3(256), 0, stream, w, panel, p.M, p.Mp, p.Cout, ntap, total);
+    };
+    float* wp;
+    int pst;
+    if (!panel_ready(pc, s2_panel_bytes(d, pl), workspace, wp, pst, record, pack)) return pst;
     float* out = pl.ks > 1 ? slabs : dx;
     int st;
     // the spatial form stores pairs: a dx off an 8-byte boundary takes the 4-byte stores (and the 4-byte image DMAs: one more

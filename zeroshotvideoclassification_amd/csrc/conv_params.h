@@ -67,8 +67,8 @@ __host__ __device__ inline long t2_weight_offset(int co2, int c2, int cin) {
 }
 
 // ---- weight panels supplied by the caller (zsv_hip.h: zsv_conv3d_*_panel) -------------------------------------------------
-// The public entry points keep ONE dispatch: the *_panel / query / job forms set this thread-local context and call the
-// ordinary entry point; the function that would launch a pack kernel looks at it.
+// The public entry points keep ONE dispatch: every form of a call -- ordinary, *_panel, query, job -- describes its panel request
+// in a PanelCtx of its own and hands it down as an argument to the function that would launch a pack kernel (panel_ready).
 enum { PANEL_NONE = 0, PANEL_LAUNCH_ONLY = 2, PANEL_RECORD = 3, PANEL_QUERY = 4 };
 struct PanelCtx {
     int mode;
@@ -77,12 +77,13 @@ struct PanelCtx {
     size_t need;            // QUERY: bytes of the panel this call would pack
     int jobs;               // QUERY / RECORD: pack launches the call would make (> 1: not cacheable)
     zsv_pack_job job;       // RECORD: the pack launch as a job of zsv_pack_multi
+    bool probing() const { return mode == PANEL_RECORD || mode == PANEL_QUERY; }      // nothing is launched, nothing dereferenced
 };
-extern thread_local PanelCtx g_panel;
-inline bool panel_stop() { return g_panel.mode == PANEL_RECORD || g_panel.mode == PANEL_QUERY; }
-// Where the panel of this call lives: the caller's buffer or the head of the workspace.  false = stop here (status in `st`).
-inline bool panel_place(size_t need, void* workspace, float*& panel, int& st) {
-    PanelCtx& pc = g_panel;
+// The pack site of a convolution path.  `panel` = where the panel of this call lives: the caller's buffer or the head of the
+// workspace.  true: it is packed (by `pack(panel)` here, or ahead of the call by zsv_pack_multi), launch the convolution;
+// false: return `st` now -- the size is reported, the job is written down by `record(job, panel)`, or the panel was refused.
+template <class Record, class Pack>
+inline bool panel_ready(PanelCtx& pc, size_t need, void* workspace, float*& panel, int& st, Record record, Pack pack) {
     st = ZSV_OK;
     panel = (float*)workspace;
     if (pc.mode == PANEL_QUERY) { pc.need = need; pc.jobs++; return false; }
@@ -90,7 +91,11 @@ inline bool panel_place(size_t need, void* workspace, float*& panel, int& st) {
         if (!pc.ptr || pc.bytes < need || (reinterpret_cast<uintptr_t>(pc.ptr) & 15) != 0) { st = ZSV_E_WORKSPACE; return false; }
         panel = (float*)pc.ptr;
     }
-    return true;
+    if (pc.mode == PANEL_RECORD) { record(pc.job, panel); pc.jobs++; return false; }
+    if (pc.mode == PANEL_LAUNCH_ONLY) return true;
+    pack(panel);
+    if (hipGetLastError() != hipSuccess) st = ZSV_E_LAUNCH;
+    return st == ZSV_OK;
 }
 
 template <int X> struct LdPad { static constexpr int value = (X % 32 == 16) ? X : X + 16; };
@@ -228,7 +233,7 @@ bool igemm_tap_applicable(const IgemmParams& prm);
 size_t igemm_tap_workspace_bytes(const IgemmParams& prm);
 // `slabs` != nullptr with prm.ksplit > 1: partial sums go to slabs[split][...] (reduce afterwards)
 int igemm_tap(const IgemmParams& prm, const float* W, int w_m_stride, int w_c_stride, const float* G,
-              const float* bias, float* C, void* workspace, size_t workspace_bytes, float* slabs, hipStream_t stream);
+              const float* bias, float* C, void* workspace, size_t workspace_bytes, float* slabs, hipStream_t stream, PanelCtx& pc);
 int igemm_tap_ksplit(const IgemmParams& prm);     // suggested split of the K range (1 = none)
 int igemm_tap_stat_tiles(const IgemmParams& prm, const float* C);   // column tiles if the epilogue can emit BN partials, else 0
 int splitk_reduce(const float* slabs, int ksplit, long elems, int M, int oS, const float* bias, int relu, float* C,
@@ -241,23 +246,23 @@ int wgrad_generic(const zsv_conv_desc* d, const float* x, const float* dy, float
 bool wino_dgrad_applicable(const zsv_conv_desc* d);
 size_t wino_dgrad_workspace_bytes(const zsv_conv_desc* d);
 int wino_dgrad(const zsv_conv_desc* d, const float* dy, const float* w, const float* add, float* dx, void* workspace,
-               size_t workspace_bytes, hipStream_t stream);
+               size_t workspace_bytes, hipStream_t stream, PanelCtx& pc);
 // every residue class of a stride-2 dgrad in one launch (conv_dgrad_s2.hip): 1x3x3 stride (1,2,2) and 3x1x1 stride (2,1,1)
 bool dgrad_s2_applicable(const zsv_conv_desc* d);
 size_t dgrad_s2_workspace_bytes(const zsv_conv_desc* d);
 bool dgrad_s2_sub_supported(const zsv_conv_desc* d, int st, int sh, int sw);
 int dgrad_s2(const zsv_conv_desc* d, const float* dy, const float* w, const float* sub, int sub_st, float* dx, void* workspace,
-             size_t workspace_bytes, hipStream_t stream);
+             size_t workspace_bytes, hipStream_t stream, PanelCtx& pc);
 bool wino_fwd_applicable(const zsv_conv_desc* d);
 bool wino_fwd_pre_capable(const zsv_conv_desc* d);   // the temporal F(2,3)-along-T forward: can apply a BatchNorm + ReLU prologue
 int wino_fwd_pre(const zsv_conv_desc* d, const float* x, const float* pre_coef, int pre_pitch, const float* w, float* stat_sum,
-                 float* stat_sq, float* y, void* workspace, size_t workspace_bytes, hipStream_t stream);
+                 float* stat_sq, float* y, void* workspace, size_t workspace_bytes, hipStream_t stream, PanelCtx& pc);
 bool wino_fwd_fusable(const zsv_conv_desc* d);       // false: split-K form, no statistics / add / residual in the epilogue
 bool wino_dgrad_fusable(const zsv_conv_desc* d);
 int wino_fwd_stat_tiles(const zsv_conv_desc* d);
 size_t wino_fwd_workspace_bytes(const zsv_conv_desc* d);
 int wino_fwd(const zsv_conv_desc* d, const float* x, const float* w, const float* bias, const float* residual, int relu,
-             float* stat_sum, float* stat_sq, float* y, void* workspace, size_t workspace_bytes, hipStream_t stream);
+             float* stat_sum, float* stat_sq, float* y, void* workspace, size_t workspace_bytes, hipStream_t stream, PanelCtx& pc);
 // LDS-DMA weight gradient of stride-1 "same" convolutions (conv_wgrad_dma.hip): writes the per-slice
 // slabs [slice][Cout][taps*Cpad] at the start of `workspace`
 bool wgrad_dma_applicable(const zsv_conv_desc* d, const float* x, const float* dy);

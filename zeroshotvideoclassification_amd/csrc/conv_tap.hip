@@ -577,7 +577,7 @@ int igemm_tap_ksplit(const IgemmParams& prm) {
 }
 
 int igemm_tap(const IgemmParams& prm_in, const float* W, int w_m_stride, int w_c_stride, const float* G,
-              const float* bias, float* C, void* workspace, size_t workspace_bytes, float* slabs, hipStream_t stream) {
+              const float* bias, float* C, void* workspace, size_t workspace_bytes, float* slabs, hipStream_t stream, PanelCtx& pc) {
     int cfg, tiles_m, Mp, nblk, Cpad;
     tap_layout(prm_in, cfg, tiles_m, Mp, nblk, Cpad);
     IgemmParams prm = prm_in;
@@ -590,34 +590,31 @@ int igemm_tap(const IgemmParams& prm_in, const float* W, int w_m_stride, int w_c
     const size_t need = ((size_t)prm.taps * Cpad + 16) * Mp * sizeof(float);
     if (!workspace || workspace_bytes < need) return ZSV_E_WORKSPACE;
     if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ZSV_E_WORKSPACE;
-    float* Wp;
-    int pst;
-    if (!panel_place(need, workspace, Wp, pst)) return pst;
     const long total = ((long)prm.taps * Cpad + 16) * Mp;           // the 16 extra rows are zero
     const int rows_total = prm.taps * Cpad + 16;
-    if (g_panel.mode == PANEL_RECORD) {
-        pack_job_tap(g_panel.job, pack_tap_args(prm, w_m_stride, w_c_stride, Cpad, Mp), W, Wp, total);
-        g_panel.jobs++;
-        return ZSV_OK;
-    }
-    if (g_panel.mode == PANEL_LAUNCH_ONLY) {
-        // (the caller's panel was packed by zsv_pack_multi from this call's job)
-    } else if ((long)prm.M * prm.gC * prm.taps >= 65536 && prm.taps <= 27 && !ZSV_KNOB(NO_PACK_TILED)) {
-        // (+1 channel block: the 16 trailing zero rows; c >= gC packs zeros)
-        const int mt = prm.taps <= 9 ? 32 : 16;
-        const dim3 grid((unsigned)(nblk + 1), (unsigned)((Mp + mt - 1) / mt));
-        const size_t lds = (size_t)prm.taps * 16 * (mt + 1) * sizeof(float);
-        if (mt == 32)
-            hipLaunchKernelGGL((pack_weights_tiled_kernel<32, 5>), grid, dim3(256), lds, stream, prm, W, Wp, w_m_stride, w_c_stride, Cpad, Mp, rows_total);
-        else
-            hipLaunchKernelGGL((pack_weights_tiled_kernel<16, 7>), grid, dim3(256), lds, stream, prm, W, Wp, w_m_stride, w_c_stride, Cpad, Mp, rows_total);
-    } else {
-        long pb = (total + 255) / 256;
-        if (pb > 4096) pb = 4096;
-        hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)pb), dim3(256), 0, stream, prm, W, Wp, w_m_stride, w_c_stride,
-                           Cpad, Mp, total);
-    }
-    if (hipGetLastError() != hipSuccess) return ZSV_E_LAUNCH;
+    auto record = [&](zsv_pack_job& job, float* panel) {
+        pack_job_tap(job, pack_tap_args(prm, w_m_stride, w_c_stride, Cpad, Mp), W, panel, total);
+    };
+    auto pack = [&](float* panel) {
+        if ((long)prm.M * prm.gC * prm.taps >= 65536 && prm.taps <= 27 && !ZSV_KNOB(NO_PACK_TILED)) {
+            // (+1 channel block: the 16 trailing zero rows; c >= gC packs zeros)
+            const int mt = prm.taps <= 9 ? 32 : 16;
+            const dim3 grid((unsigned)(nblk + 1), (unsigned)((Mp + mt - 1) / mt));
+            const size_t lds = (size_t)prm.taps * 16 * (mt + 1) * sizeof(float);
+            if (mt == 32)
+                hipLaunchKernelGGL((pack_weights_tiled_kernel<32, 5>), grid, dim3(256), lds, stream, prm, W, panel, w_m_stride, w_c_stride, Cpad, Mp, rows_total);
+            else
+                hipLaunchKernelGGL((pack_weights_tiled_kernel<16, 7>), grid, dim3(256), lds, stream, prm, W, panel, w_m_stride, w_c_stride, Cpad, Mp, rows_total);
+        } else {
+            long pb = (total + 255) / 256;
+            if (pb > 4096) pb = 4096;
+            hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)pb), dim3(256), 0, stream, prm, W, panel, w_m_stride, w_c_stride,
+                               Cpad, Mp, total);
+        }
+    };
+    float* Wp;
+    int pst;
+    if (!panel_ready(pc, need, workspace, Wp, pst, record, pack)) return pst;
     switch (cfg) {
         case 0: return tap_launch<9, 2, 1, 4>(prm, Wp, G, bias, C, tiles_m, Mp, nblk, stream);
         case 1: return tap_launch<4, 4, 2, 2>(prm, Wp, G, bias, C, tiles_m, Mp, nblk, stream);

@@ -1532,11 +1532,29 @@ static int winot4_launch(const WinoParams& p, const float* up, const float* in, 
     return p.stat_sum != nullptr ? winot4_launch_epi<TM, PRE, 1>(p, up, in, out, stream) : winot4_launch_epi<TM, PRE, 0>(p, up, in, out, stream);
 }
 
+// the weight panel of a launch, F(2,3) or F(4,3) form, p.R row taps (1: the temporal form): packed here, packed ahead of the call
+// into the caller's buffer, or written down as a job (conv_params.h: panel_ready)
+static long wino_panel_elems(const WinoParams& p, bool f43) { return (long)p.nblk * p.R * (f43 ? 6 : 4) * 16 * p.Mp; }
+static bool wino_panel(PanelCtx& pc, const WinoParams& p, bool f43, const float* w, long sm, long sc, int flip, size_t need, void* workspace,
+                       float*& up, int& st, hipStream_t stream) {
+    const long total = wino_panel_elems(p, f43);
+    auto record = [&](zsv_pack_job& job, float* panel) {
+        pack_job_wino(job, f43 ? 6 : 4, PackWinoArgs{p.M, p.Mp, p.C, p.nblk, p.R, flip, sm, sc}, w, panel, total);
+    };
+    auto pack = [&](float* panel) {
+        long pb = (total + 255) / 256;
+        if (pb > 4096) pb = 4096;
+        hipLaunchKernelGGL(f43 ? wino4_pack_kernel : wino_pack_kernel, dim3((unsigned)pb), dim3(256), 0, stream, w, panel, p.M, p.Mp, p.C,
+                           p.nblk, p.R, sm, sc, flip, total);
+    };
+    return panel_ready(pc, need, workspace, up, st, record, pack);
+}
+
 // the temporal form: M rows from C reduction channels; G[m][c][kt] = w[m*sm + c*sc + (flip ? 2 - kt : kt)]
 static int winot_run(const zsv_conv_desc* d, int M, int C, const float* in, const float* w, long sm, long sc, int flip,
                      const float* add, const float* bias, int relu, float* stat_sum, float* stat_sq, const float* pre_coef,
                      int pre_pitch, float* out,
-                     void* workspace, size_t workspace_bytes, hipStream_t stream) {
+                     void* workspace, size_t workspace_bytes, hipStream_t stream, PanelCtx& pc) {
     if (!workspace || workspace_bytes < wino_bytes(d, M, C)) return ZSV_E_WORKSPACE;
     const int tm = wino_tm(M), bm = 16 * tm;
     WinoParams p;
@@ -1557,24 +1575,11 @@ static int winot_run(const zsv_conv_desc* d, int M, int C, const float* in, cons
     p.add = add; p.bias = bias; p.relu = relu; p.stat_sum = stat_sum; p.stat_sq = stat_sq;
     p.ksplit = 1; p.chunks_per_split = p.nblk; p.slab_elems = 0;
     p.pre_coef = pre_coef; p.pre_pitch = pre_pitch;
+    const bool f43 = ZSV_KNOB(WINOT_NO_F43) == nullptr;          // (T is 4, 8 or 16 here: whole frame quads)
+    p.u_bytes = (unsigned)(wino_panel_elems(p, f43) * sizeof(float));
     float* up;
     int pst;
-    if (!panel_place(wino_bytes(d, M, C), workspace, up, pst)) return pst;
-    const bool f43 = ZSV_KNOB(WINOT_NO_F43) == nullptr;          // (T is 4, 8 or 16 here: whole frame quads)
-    const long total = (long)p.nblk * (f43 ? 6 : 4) * 16 * p.Mp;
-    p.u_bytes = (unsigned)(total * sizeof(float));
-    if (g_panel.mode == PANEL_RECORD) {
-        pack_job_wino(g_panel.job, f43 ? 6 : 4, PackWinoArgs{p.M, p.Mp, p.C, p.nblk, 1, flip, sm, sc}, w, up, total);
-        g_panel.jobs++;
-        return ZSV_OK;
-    }
-    if (g_panel.mode != PANEL_LAUNCH_ONLY) {
-        long pb = (total + 255) / 256;
-        if (pb > 4096) pb = 4096;
-        hipLaunchKernelGGL(f43 ? wino4_pack_kernel : wino_pack_kernel, dim3((unsigned)pb), dim3(256), 0, stream, w, up, p.M, p.Mp, p.C, p.nblk, 1, sm, sc, flip,
-                           total);
-        if (hipGetLastError() != hipSuccess) return ZSV_E_LAUNCH;
-    }
+    if (!wino_panel(pc, p, f43, w, sm, sc, flip, wino_bytes(d, M, C), workspace, up, pst, stream)) return pst;
     if (f43) {
         if (pre_coef) return tm == 3 ? winot4_launch<3, true>(p, up, in, out, stream) : winot4_launch<4, true>(p, up, in, out, stream);
         return tm == 3 ? winot4_launch<3, false>(p, up, in, out, stream) : winot4_launch<4, false>(p, up, in, out, stream);
@@ -1586,7 +1591,7 @@ static int winot_run(const zsv_conv_desc* d, int M, int C, const float* in, cons
 // out[m] = sum_c G[m][c] (*) in[c]; G[m][c][tap] = w[m*sm + c*sc + (flip ? 9*kT-1 - tap : tap)]
 static int wino_run(const zsv_conv_desc* d, int M, int C, const float* in, const float* w, long sm, long sc, int flip,
                     const float* add, const float* bias, int relu, float* stat_sum, float* stat_sq, float* out,
-                    void* workspace, size_t workspace_bytes, hipStream_t stream) {
+                    void* workspace, size_t workspace_bytes, hipStream_t stream, PanelCtx& pc) {
     float* const final_out = out;
     if (!workspace || workspace_bytes < wino_total_bytes(d, M, C)) return ZSV_E_WORKSPACE;
     const int tm = wino_tm_for(d, M), bm = 16 * tm;
@@ -1616,26 +1621,13 @@ static int wino_run(const zsv_conv_desc* d, int M, int C, const float* in, const
     p.ksplit = ks;
     p.chunks_per_split = (p.nblk * p.R + ks - 1) / ks;
     p.slab_elems = (long)d->N * M * p.S;
-    float* up;
-    int pst;
-    if (!panel_place(wino_bytes(d, M, C), workspace, up, pst)) return pst;
     float* slabs = (float*)((char*)workspace + wino_bytes(d, M, C));
     if (ks > 1) { p.bias = nullptr; p.relu = 0; out = slabs; }         // bias / ReLU move to the ordered sum of the parts
     const bool f43 = wino_f43(d);
     p.u_bytes = (unsigned)wino_bytes(d, M, C);
-    const long total = (long)p.nblk * p.R * (f43 ? 6 : 4) * 16 * p.Mp;
-    if (g_panel.mode == PANEL_RECORD) {
-        pack_job_wino(g_panel.job, f43 ? 6 : 4, PackWinoArgs{p.M, p.Mp, p.C, p.nblk, p.R, flip, sm, sc}, w, up, total);
-        g_panel.jobs++;
-        return ZSV_OK;
-    }
-    if (g_panel.mode != PANEL_LAUNCH_ONLY) {
-        long pb = (total + 255) / 256;
-        if (pb > 4096) pb = 4096;
-        hipLaunchKernelGGL(f43 ? wino4_pack_kernel : wino_pack_kernel, dim3((unsigned)pb), dim3(256), 0, stream, w, up, p.M, p.Mp, p.C,
-                           p.nblk, p.R, sm, sc, flip, total);
-        if (hipGetLastError() != hipSuccess) return ZSV_E_LAUNCH;
-    }
+    float* up;
+    int pst;
+    if (!wino_panel(pc, p, f43, w, sm, sc, flip, wino_bytes(d, M, C), workspace, up, pst, stream)) return pst;
     const bool x4 = d->Wi % 4 == 0 && ZSV_KNOB(WINO_NO_X4) == nullptr;
     int st;
     if (p.Wv) {
@@ -1654,34 +1646,34 @@ static int wino_run(const zsv_conv_desc* d, int M, int C, const float* in, const
 }
 
 int wino_dgrad(const zsv_conv_desc* d, const float* dy, const float* w, const float* add, float* dx, void* workspace,
-               size_t workspace_bytes, hipStream_t stream) {
+               size_t workspace_bytes, hipStream_t stream, PanelCtx& pc) {
     if (winot_geometry(d, d->Cin))          // G[m = ci][c = co][kt] = W[co][ci][2 - kt]
         return winot_run(d, d->Cin, d->Cout, dy, w, 3, (long)d->Cin * 3, 1, add, nullptr, 0, nullptr, nullptr, nullptr, 0, dx, workspace,
-                         workspace_bytes, stream);
+                         workspace_bytes, stream, pc);
     // G[m = ci][c = co][kt][kh][kw] = W[co][ci][kT-1-kt][2-kh][2-kw]: stride of m is 9*kT, of c is Cin*9*kT, taps flipped
     const long taps = 9L * d->kT;
     return wino_run(d, d->Cin, d->Cout, dy, w, taps, (long)d->Cin * taps, 1, add, nullptr, 0, nullptr, nullptr, dx, workspace,
-                    workspace_bytes, stream);
+                    workspace_bytes, stream, pc);
 }
 
 bool wino_fwd_pre_capable(const zsv_conv_desc* d) { return winot_geometry(d, d->Cout) && ZSV_KNOB(NO_WINO_FWD) == nullptr; }
 
 // the temporal forward with the BatchNorm + ReLU in front of it applied on the fly (conv_winot_kernel PRE)
 int wino_fwd_pre(const zsv_conv_desc* d, const float* x, const float* pre_coef, int pre_pitch, const float* w, float* stat_sum,
-                 float* stat_sq, float* y, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+                 float* stat_sq, float* y, void* workspace, size_t workspace_bytes, hipStream_t stream, PanelCtx& pc) {
     if (!wino_fwd_pre_capable(d)) return ZSV_E_UNSUPPORTED;
     return winot_run(d, d->Cout, d->Cin, x, w, (long)d->Cin * 3, 3, 0, nullptr, nullptr, 0, stat_sum, stat_sq, pre_coef, pre_pitch, y, workspace,
-                     workspace_bytes, stream);
+                     workspace_bytes, stream, pc);
 }
 
 int wino_fwd(const zsv_conv_desc* d, const float* x, const float* w, const float* bias, const float* residual, int relu,
-             float* stat_sum, float* stat_sq, float* y, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+             float* stat_sum, float* stat_sq, float* y, void* workspace, size_t workspace_bytes, hipStream_t stream, PanelCtx& pc) {
     if (winot_geometry(d, d->Cout))
         return winot_run(d, d->Cout, d->Cin, x, w, (long)d->Cin * 3, 3, 0, residual, bias, relu, stat_sum, stat_sq, nullptr, 0, y,
-                         workspace, workspace_bytes, stream);
+                         workspace, workspace_bytes, stream, pc);
     const long taps = 9L * d->kT;
     return wino_run(d, d->Cout, d->Cin, x, w, (long)d->Cin * taps, taps, 0, residual, bias, relu, stat_sum, stat_sq, y, workspace,
-                    workspace_bytes, stream);
+                    workspace_bytes, stream, pc);
 }
 
 }  // namespace zsv

@@ -1,5 +1,4 @@
-// pack_multi.hip -- every weight panel of a training step in ONE launch (zsv_hip.h: zsv_pack_multi), and the thread-local
-// context through which the *_panel entry points reach the pack sites of the convolution paths.
+// pack_multi.hip -- every weight panel of a training step in ONE launch (zsv_hip.h: zsv_pack_multi).
 //
 // A job is a pack launch written down by the path that would have made it (PANEL_RECORD, conv_params.h): kernel kind, scalar
 // arguments, the weight tensor and the panel.  Block b of the grid serves 1024 consecutive panel elements of the job whose
@@ -9,8 +8,6 @@
 #include "pack_bodies.h"
 
 namespace zsv {
-
-thread_local PanelCtx g_panel = {PANEL_NONE, nullptr, 0, 0, 0, {}};
 
 __global__ __launch_bounds__(256) void pack_multi_kernel(const zsv_pack_job* __restrict__ jobs, int count) {
     const long b = blockIdx.x;

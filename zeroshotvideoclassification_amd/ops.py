@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import os
 import threading
+import weakref
 
 from ctypes import byref, c_size_t, c_void_p
 from typing import Optional, Sequence, Tuple
@@ -277,7 +278,6 @@ class _Panel:
 
 class _PanelCache:
     def __init__(self, device):
-        import threading
         self.device = device
         self.entries = {}            # key -> _Panel (None: this geometry has no single panel)
         self.knob_gen = _lib.knob_generation()
@@ -298,7 +298,6 @@ class _PanelCache:
 
     def get(self, weight, d, direction, extras):
         """The up-to-date panel tensor of this call, or None (not cacheable / cache disabled)."""
-        import weakref
         with self.lock:
             if self.knob_gen != _lib.knob_generation():          # the switches changed: layouts may have too
                 self.entries.clear()
@@ -313,7 +312,7 @@ class _PanelCache:
                 if self.nbytes > self.limit:
                     self.entries.clear()
                     self.nbytes = 0
-                e = self._create(weight, d, direction, extras, weakref)
+                e = self._create(weight, d, direction, extras)
                 self.entries[key] = e
                 self.table = None
                 if e is not None:
@@ -332,7 +331,7 @@ class _PanelCache:
                     self.foreign.append(cur)                     # (the next re-pack waits for what this stream has queued: ADVICE r3)
             return e.panel
 
-    def _create(self, weight, d, direction, extras, weakref):
+    def _create(self, weight, d, direction, extras):
         lib = _lib.load()
         nb = c_size_t(0)
         _lib.check(lib.zsv_conv3d_panel_query(byref(d), direction, extras, byref(nb)), "zsv_conv3d_panel_query")
@@ -381,7 +380,6 @@ class _PanelCache:
 
     def _refresh(self):
         """Re-pack every panel whose weight changed, in one launch on the current stream."""
-        import ctypes
         stale, dead = [], []
         for key, e in self.entries.items():
             if e is None:
@@ -461,6 +459,30 @@ def invalidate_panels():
     _PANEL_CACHES.clear()
 
 
+def _call_with_panel(name, panel, *args):
+    """Entry point ``name``, which packs its weight panel itself, or ``name + "_panel"`` with the kept ``panel`` appended."""
+    lib = _lib.load()
+    if panel is None:
+        _lib.check(getattr(lib, name)(*args), name)
+    else:
+        _lib.check(getattr(lib, name + "_panel")(*args, panel.data_ptr(), panel.numel()), name + "_panel")
+
+
+def _conv_dgrad(d, dy, weight, out, add=None, sub=None, sub_strides=None):
+    """``out`` = input gradient of the convolution ``d`` (+ ``add``, laid out like ``out``; or + the compact gradient ``sub`` of a
+    1x1x1 shortcut convolution of strides ``sub_strides`` on the same input), with the cached weight panel when there is one."""
+    lib = _lib.load()
+    nbytes = lib.zsv_conv3d_dgrad_workspace_bytes(byref(d))
+    ws = _workspace(nbytes, dy.device)
+    panel = _panel_for(weight, d, 1, False)
+    if sub is not None:
+        _call_with_panel("zsv_conv3d_dgrad_add_strided", panel, byref(d), dy.data_ptr(), weight.data_ptr(), sub.data_ptr(), *sub_strides,
+                         out.data_ptr(), _ptr(ws), nbytes, _stream())
+    else:
+        _call_with_panel("zsv_conv3d_dgrad_add", panel, byref(d), dy.data_ptr(), weight.data_ptr(), _ptr(add), out.data_ptr(), _ptr(ws),
+                         nbytes, _stream())
+
+
 def conv_desc(x_shape: Sequence[int], w_shape: Sequence[int], stride, padding) -> ConvDesc:
     n, cin, ti, hi, wi = (int(v) for v in x_shape)
     cout, cin_w, kt, kh, kw = (int(v) for v in w_shape)
@@ -535,14 +557,8 @@ class _Conv3d(Function):
                     stats = torch.empty((2, d.Cout, tiles), dtype=torch.float32, device=x.device)
             ev = timer.start() if (timer is not None and timer.wants("conv_fwd", d)) else None
             panel = _panel_for(weight, d, 0, bias is not None or relu or stats is not None, _recording())
-            if panel is None:
-                _lib.check(lib.zsv_conv3d_fwd_stats(byref(d), x.data_ptr(), weight.data_ptr(), _ptr(bias), y.data_ptr(),
-                                                    1 if relu else 0, _ptr(stats), tiles, _ptr(ws), nbytes, _stream()),
-                           "zsv_conv3d_fwd")
-            else:
-                _lib.check(lib.zsv_conv3d_fwd_full_panel(byref(d), x.data_ptr(), weight.data_ptr(), _ptr(bias), None, y.data_ptr(),
-                                                         1 if relu else 0, _ptr(stats), tiles, _ptr(ws), nbytes, _stream(),
-                                                         panel.data_ptr(), panel.numel()), "zsv_conv3d_fwd (panel)")
+            _call_with_panel("zsv_conv3d_fwd_full", panel, byref(d), x.data_ptr(), weight.data_ptr(), _ptr(bias), None, y.data_ptr(),
+                             1 if relu else 0, _ptr(stats), tiles, _ptr(ws), nbytes, _stream())
             if ev is not None:
                 timer.stop(ev)
         ctx.desc = d
@@ -596,46 +612,21 @@ class _Conv3d(Function):
                 # grid), parked for the block's first convolution; this node contributes no full-size gradient
                 d1 = conv_desc((d.N, d.Cin, d.To, d.Ho, d.Wo), weight.shape, (1, 1, 1), (0, 0, 0))
                 dsub = torch.empty((d.N, d.Cin, d.To, d.Ho, d.Wo), dtype=torch.float32, device=dy.device)
-                nbytes = lib.zsv_conv3d_dgrad_workspace_bytes(byref(d1))
-                ws = _workspace(nbytes, dy.device)
-                panel = _panel_for(weight, d1, 1, False)
-                if panel is None:
-                    _lib.check(lib.zsv_conv3d_dgrad(byref(d1), dy.data_ptr(), weight.data_ptr(), dsub.data_ptr(), _ptr(ws), nbytes,
-                                                    _stream()), "zsv_conv3d_dgrad (compact shortcut gradient)")
-                else:
-                    _lib.check(lib.zsv_conv3d_dgrad_add_panel(byref(d1), dy.data_ptr(), weight.data_ptr(), None, dsub.data_ptr(), _ptr(ws),
-                                                              nbytes, _stream(), panel.data_ptr(), panel.numel()),
-                               "zsv_conv3d_dgrad (compact shortcut gradient, panel)")
+                _conv_dgrad(d1, dy, weight, dsub)
                 src.dsub = dsub
             elif ctx.needs_input_grad[0]:
                 dx = torch.empty_like(x)
-                nbytes = lib.zsv_conv3d_dgrad_workspace_bytes(byref(d))
-                ws = _workspace(nbytes, dy.device)
                 add = None
                 if ctx.skip_link is not None:            # the shortcut's gradient, parked by the block's tail
                     add, ctx.skip_link.dres = ctx.skip_link.dres, None
                 link = ctx.down_link
                 if link is not None:
                     link.consumed = True
-                panel = _panel_for(weight, d, 1, False)
-                pp, pn = (panel.data_ptr(), panel.numel()) if panel is not None else (None, 0)
                 if link is not None and link.dsub is not None:      # the strided shortcut's compact gradient
                     sub, link.dsub = link.dsub, None
-                    if panel is None:
-                        _lib.check(lib.zsv_conv3d_dgrad_add_strided(byref(d), dy.data_ptr(), weight.data_ptr(), sub.data_ptr(),
-                                                                    link.strides[0], link.strides[1], link.strides[2], dx.data_ptr(),
-                                                                    _ptr(ws), nbytes, _stream()), "zsv_conv3d_dgrad_add_strided")
-                    else:
-                        _lib.check(lib.zsv_conv3d_dgrad_add_strided_panel(byref(d), dy.data_ptr(), weight.data_ptr(), sub.data_ptr(),
-                                                                          link.strides[0], link.strides[1], link.strides[2], dx.data_ptr(),
-                                                                          _ptr(ws), nbytes, _stream(), pp, pn),
-                                   "zsv_conv3d_dgrad_add_strided (panel)")
-                elif panel is None:
-                    _lib.check(lib.zsv_conv3d_dgrad_add(byref(d), dy.data_ptr(), weight.data_ptr(), _ptr(add), dx.data_ptr(),
-                                                        _ptr(ws), nbytes, _stream()), "zsv_conv3d_dgrad")
+                    _conv_dgrad(d, dy, weight, dx, sub=sub, sub_strides=link.strides)
                 else:
-                    _lib.check(lib.zsv_conv3d_dgrad_add_panel(byref(d), dy.data_ptr(), weight.data_ptr(), _ptr(add), dx.data_ptr(),
-                                                              _ptr(ws), nbytes, _stream(), pp, pn), "zsv_conv3d_dgrad (panel)")
+                    _conv_dgrad(d, dy, weight, dx, add=add)
             if ctx.needs_input_grad[1]:
                 nbytes = lib.zsv_conv3d_wgrad_workspace_bytes(byref(d))
 
@@ -877,13 +868,8 @@ class _Conv3dPre(Function):
                 if tiles > 0:
                     stats = torch.empty((2, d.Cout, tiles), dtype=torch.float32, device=x.device)
             panel = _panel_for(weight, d, 0, False, _recording())
-            if panel is None:
-                _lib.check(lib.zsv_conv3d_fwd_pre(byref(d), x.data_ptr(), coef.data_ptr(), int(coef.shape[1]), weight.data_ptr(),
-                                                  y.data_ptr(), _ptr(stats), tiles, _ptr(ws), nbytes, _stream()), "zsv_conv3d_fwd_pre")
-            else:
-                _lib.check(lib.zsv_conv3d_fwd_pre_panel(byref(d), x.data_ptr(), coef.data_ptr(), int(coef.shape[1]), weight.data_ptr(),
-                                                        y.data_ptr(), _ptr(stats), tiles, _ptr(ws), nbytes, _stream(), panel.data_ptr(),
-                                                        panel.numel()), "zsv_conv3d_fwd_pre (panel)")
+            _call_with_panel("zsv_conv3d_fwd_pre", panel, byref(d), x.data_ptr(), coef.data_ptr(), int(coef.shape[1]), weight.data_ptr(),
+                             y.data_ptr(), _ptr(stats), tiles, _ptr(ws), nbytes, _stream())
         ctx.desc = d
         ctx.save_for_backward(x, coef, weight)
         if stats is not None:
@@ -903,15 +889,7 @@ class _Conv3dPre(Function):
         with torch.cuda.device(dy.device):
             if ctx.needs_input_grad[0]:                     # gradient w.r.t. the virtual activation relu(bn(x))
                 dx = torch.empty_like(x)
-                nbytes = lib.zsv_conv3d_dgrad_workspace_bytes(byref(d))
-                ws = _workspace(nbytes, dy.device)
-                panel = _panel_for(weight, d, 1, False)
-                if panel is None:
-                    _lib.check(lib.zsv_conv3d_dgrad(byref(d), dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), _ptr(ws), nbytes,
-                                                    _stream()), "zsv_conv3d_dgrad")
-                else:
-                    _lib.check(lib.zsv_conv3d_dgrad_add_panel(byref(d), dy.data_ptr(), weight.data_ptr(), None, dx.data_ptr(), _ptr(ws),
-                                                              nbytes, _stream(), panel.data_ptr(), panel.numel()), "zsv_conv3d_dgrad (panel)")
+                _conv_dgrad(d, dy, weight, dx)
             if ctx.needs_input_grad[2]:
                 nbytes = lib.zsv_conv3d_wgrad_workspace_bytes(byref(d))
                 pitch = int(coef.shape[1])
