@@ -106,8 +106,8 @@ def conv_operands(seed, xs, ws, stride, pad):
 
 
 # =========================================================================================================================
-# the weight gradients: conv_wgrad_tring.hip:524, conv_wgrad_wino.hip:551, conv_wgrad.hip:526 / 612 (LDS-DMA),
-# conv_wgrad_generic.hip:433 (stem rows), conv_wgrad.hip:635 (av4 on dy)
+# the weight gradients: conv_wgrad.hip:564 (wgrad_dispatch's one aligned16(x, dy) in front of the route table: frame ring, Winograd
+# form, LDS-DMA), conv_wgrad_generic.hip:397 (stem rows), conv_wgrad.hip:427 (av4 on dy)
 # =========================================================================================================================
 WGRAD_SITES = [
     # site, the row, (N, Cin, T, H, W), (Cout, Cin, k), stride, padding, tolerance of the row's own test, switches that pin the route,

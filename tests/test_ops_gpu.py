@@ -804,6 +804,85 @@ def test_conv3d_wgrad_temporal_ring_path(case, monkeypatch):
     assert not torch.equal(a, c), "the slice-count knob of the ring kernel had no effect: is the kernel in use?"
 
 
+# The slab sums (csrc/wgrad_sum.hip) give slices g, g+8, ... to group g of 8, which enters the 4-ahead loop iff g + 24 < slices
+# and the 2-ahead loop iff g + 8 < slices: 1, 7 (a group with nothing), 9, 17 (2-ahead only), 24 (tail only), 25 (group 0 alone in
+# the 4-ahead loop), 34 (once round the loop, then the tail) are the counts at which a layout's sum can go wrong.  The rows are the
+# smallest that keep each route applicable (16384 voxels for the ring and Winograd forms) and whose plans keep the requested
+# count through their own rounding (33 does not survive 1024 chunks: 34).
+_SUM_WINO = ((2, 32, 1, 128, 128), (1, 3, 3), (0, 1, 1))
+_SUM_DMA = {"ZSV_NO_WGRAD_WINO": "1"}
+SUM_BOUNDARY_ROWS = [
+    # name, x shape, Cout, kernel, padding, fixed switches, the slice-count knob, counts
+    ("ring", (1, 128, 4, 64, 64), 64, (3, 1, 1), (1, 0, 0), {}, "ZSV_WGRAD_TRING_SLICES", (1, 7, 9, 24, 25, 34)),
+    ("ring_winograd_form", (1, 128, 8, 32, 64), 64, (3, 1, 1), (1, 0, 0), {}, "ZSV_WGRAD_TRING_SLICES", (1, 7, 9, 24, 25, 33)),
+    ("winograd_f23", _SUM_WINO[0], 64, *_SUM_WINO[1:], {}, "ZSV_WGRAD_WINO_SLICES", (1, 7, 9, 17, 24, 25, 34)),
+    ("winograd_f43", _SUM_WINO[0], 128, *_SUM_WINO[1:], {}, "ZSV_WGRAD_WINO_SLICES", (1, 7, 9, 17, 24, 25, 34)),
+    ("lds_dma_group_sum", _SUM_WINO[0], 64, *_SUM_WINO[1:], {**_SUM_DMA, "ZSV_NO_SLAB_SUM_ROWS": "1"}, "ZSV_WGRAD_DMA_SLICES",
+     (1, 7, 9, 24, 25, 33, 34)),
+    # up to 32 slices this geometry takes slab_sum_rows_kernel and its 3-ahead loop; 33 must fall back to the group sum
+    ("lds_dma_rows_sum", _SUM_WINO[0], 64, *_SUM_WINO[1:], _SUM_DMA, "ZSV_WGRAD_DMA_SLICES", (1, 2, 3, 4, 5, 7, 32, 33)),
+]
+
+
+@pytest.mark.parametrize("row", SUM_BOUNDARY_ROWS, ids=[r[0] for r in SUM_BOUNDARY_ROWS])
+def test_slab_sums_at_the_slice_counts_where_their_loops_change(row, monkeypatch):
+    name, xs, cout, k, pad, fixed, knob, counts = row
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+    x = torch.randn(*xs, generator=g)
+    dy = torch.randn(xs[0], cout, *xs[2:], generator=g)
+    wshape = (cout, xs[1]) + k
+    ref = torch.nn.grad.conv3d_weight(x.double(), wshape, dy.double(), padding=pad)
+    xg, dyg = x.to(DEV), dy.to(DEV)
+
+    def run():
+        wg = torch.zeros(wshape, device=DEV).requires_grad_()
+        ops.conv3d(xg, wg, None, 1, pad).backward(dyg)
+        return wg.grad
+
+    for key, v in fixed.items():
+        monkeypatch.setenv(key, v)
+    got = {}
+    for c in counts:
+        monkeypatch.setenv(knob, str(c))
+        got[c] = run()
+        close(got[c], ref, what=f"{name} wgrad, {c} slices")
+        assert torch.equal(got[c], run()), f"{name}, {c} slices: bitwise reproducible"
+    for i, a in enumerate(counts):
+        for b in counts[i + 1:]:
+            assert not torch.equal(got[a], got[b]), f"{name}: {a} and {b} slices gave the same bits: did the knob reach the kernel?"
+    if name == "lds_dma_rows_sum":
+        # the rows kernel adds the slices one after the other, the group sum in 8 interleaved groups: different bits past 8 slices
+        monkeypatch.setenv("ZSV_NO_SLAB_SUM_ROWS", "1")
+        for c, same in ((32, False), (33, True)):
+            monkeypatch.setenv(knob, str(c))
+            assert torch.equal(got[c], run()) == same, f"{c} slices: the rows kernel should {'not ' if same else ''}have taken it"
+
+
+@pytest.mark.parametrize("frames", [1, 9, 34])
+def test_generic_slab_sum_at_the_slice_counts_where_its_loop_changes(frames):
+    """A 3-channel 1x3x3 convolution over `frames` frames of 16x16 on 2 clips is cut into exactly `frames` slices (16 chunks of 32
+    voxels each, one output tile): the flat sum of the generic route with 1, 9 and 34 slices."""
+    g = torch.Generator().manual_seed(frames)
+    x = torch.randn(2, 3, frames, 16, 16, generator=g)
+    dy = torch.randn(2, 16, frames, 16, 16, generator=g)
+    wshape = (16, 3, 1, 3, 3)
+    ref = torch.nn.grad.conv3d_weight(x.double(), wshape, dy.double(), padding=(0, 1, 1))
+
+    def run():
+        wg = torch.zeros(wshape, device=DEV).requires_grad_()
+        ops.conv3d(x.to(DEV), wg, None, 1, (0, 1, 1)).backward(dy.to(DEV))
+        return wg.grad
+
+    import ctypes
+    from zeroshotvideoclassification_amd import _lib
+    d = ops.conv_desc(x.shape, wshape, 1, (0, 1, 1))
+    slab_bytes = 16 * 27 * 4                    # (a single slice is written straight to dw: no workspace)
+    assert _lib.load().zsv_conv3d_wgrad_workspace_bytes(ctypes.byref(d)) == (frames * slab_bytes if frames > 1 else 0)
+    a = run()
+    close(a, ref, what=f"generic wgrad, {frames} slices")
+    assert torch.equal(a, run()), "bitwise reproducible"
+
+
 @pytest.mark.parametrize("n,cin,cout,thw", [(2, 144, 64, (8, 32, 32)), (3, 230, 128, (4, 32, 48)), (2, 130, 56, (16, 16, 64))],
                          ids=["t1_like", "ragged_230_to_128", "padded_rows_and_columns"])
 def test_batchnorm_relu_folded_into_the_temporal_convolution(n, cin, cout, thw, monkeypatch):
@@ -1154,8 +1233,8 @@ def test_two_frame_temporal_conv_in_dense_form(n, cin, cout, hw, monkeypatch):
 
 
 def test_weight_gradient_slab_sum_rows_equals_the_generic_sum(monkeypatch):
-    """conv_wgrad.hip: few slices of a large gradient are added by slab_sum_rows_kernel (coalesced, LDS-transposed) -- same
-    slice order as slab_sum_kernel, so the same bits (ZSV_NO_SLAB_SUM_ROWS=1 selects the generic kernel)."""
+    """wgrad_sum.hip: few slices of a large gradient are added by slab_sum_rows_kernel (coalesced, LDS-transposed) -- same
+    slice order as the group sum (wgrad_sum_kernel), so the same bits (ZSV_NO_SLAB_SUM_ROWS=1 selects the group sum)."""
     g = torch.Generator().manual_seed(5)
     x = torch.randn(6, 96, 2, 7, 7, generator=g).to(DEV)
     dy = torch.randn(6, 200, 2, 7, 7, generator=g).to(DEV)

@@ -92,10 +92,10 @@ def numel(shape):
 # one falls back to.  For a listed call the element-aligned run is held to the fp64 reference and the tolerance of the row's own test
 # in test_ops_gpu.py, never to the first run.  The last test of the file fails for an entry no call matched and for a listed call
 # whose bytes equalled the first run's after all: the list cannot grow slack.
-TRING = "conv_wgrad_tring.hip:524 (wgrad_tring_applicable: x | dy)"
-WINO = "conv_wgrad_wino.hip:551 (wgrad_wino_applicable: x | dy)"
-DMA = "conv_wgrad_dma.hip:306 (wgrad_dma_applicable: x | dy; asked at conv_wgrad.hip:612, sized at :526)"
-STEM = "conv_wgrad_generic.hip:433 (the stem row kernel: x | dy)"
+TRING = "conv_wgrad.hip:564 (wgrad_dispatch: aligned16(x, dy) in front of the route table; the frame ring's entry)"
+WINO = "conv_wgrad.hip:564 (wgrad_dispatch: aligned16(x, dy) in front of the route table; the Winograd form's entry)"
+DMA = "conv_wgrad.hip:564 (wgrad_dispatch: aligned16(x, dy) in front of the route table; the LDS-DMA entry, sized at :490)"
+STEM = "conv_wgrad_generic.hip:397 (the stem row kernel: aligned16(x, dy))"
 STATS = "conv_tap.hip:560 (tap_lds_epilogue_ok: y -- zsv_conv3d_fwd_stat_tiles(d, y) answers 0, the plain form runs, no statistics)"
 BIAS = "elementwise_pool.hip:384 (zsv_relu_bwd_bias: the float4 route sums db in another order; dx is the same bits)"
 ROUTE_CHANGES = {}
@@ -109,7 +109,7 @@ def _listed(entries, line, rows, unless=()):
             ROUTE_CHANGES[(entry, route)] = None
 
 
-_WGRAD = ("zsv_conv3d_wgrad", "zsv_conv3d_wgrad_masked")                    # one dispatch: wgrad_dispatch, conv_wgrad.hip:588
+_WGRAD = ("zsv_conv3d_wgrad", "zsv_conv3d_wgrad_masked")                    # one dispatch: wgrad_dispatch, conv_wgrad.hip:544
 _listed(_WGRAD, TRING, [f"WGRAD_TRING_CASES/{r}" for r in ("t1_like", "cin230_cout128", "ragged_both", "many_clips")])      # (switched off: the LDS-DMA kernel, DMA)
 _listed(_WGRAD, WINO, [f"WGRAD_WINO_CASES/{r}" for r in ("w_10_odd_chunks", "r3d_layer1_like_64_rows", "m56_ragged_columns", "partial_chunk_aligned_w",
                                                          "unaligned_w_whole_chunks", "two_144_row_tiles", "m200_ragged_second_tile")],

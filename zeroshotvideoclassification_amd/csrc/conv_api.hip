@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include "conv_params.h"
 #include "knobs.h"
+#include "wgrad_plan.h"
 
 using namespace zsv;
 
@@ -83,7 +84,6 @@ const zsv_conv_desc linear_desc(int32_t rows, int32_t in_features, int32_t out_f
 }  // namespace
 
 // workspace layout of a tap-kernel call: [packed weights (16-B aligned)] [split-K slabs]
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // two-frame temporal convolutions in dense 1x1x1 form (conv_params.h: t2_dense_shape)
 static bool t2_dense(const zsv_conv_desc* d) { return t2_dense_shape(d) && !ZSV_KNOB(NO_T2_DENSE); }
@@ -208,7 +208,7 @@ extern "C" int zsv_conv3d_fwd_full(const zsv_conv_desc* d, const float* x, const
 // (Conv2Plus1D's `BatchNorm3d(mid) -> ReLU -> temporal conv`, resnet.py:46-52): both the forward (direct kernel, PRE form)
 // and the weight gradient (frame-ring kernel, PRE form) must be able to apply the affine + ReLU while they read x.
 extern "C" int32_t zsv_conv3d_pre_supported(const zsv_conv_desc* d) {
-    if (conv_check(d) != ZSV_OK || ZSV_KNOB(NO_BN_FUSION) || !wgrad_tring_applicable(d, nullptr, nullptr)) return 0;
+    if (conv_check(d) != ZSV_OK || ZSV_KNOB(NO_BN_FUSION) || !wgrad_tring_shape(d)) return 0;
     if (wino_fwd_applicable(d)) return wino_fwd_pre_capable(d) ? 1 : 0;          // (the temporal F(2,3)-along-T kernel)
     IgemmParams p;
     fwd_params(p, d, 0);

@@ -23,6 +23,7 @@
 #include <stdlib.h>
 #include "conv_params.h"
 #include "knobs.h"
+#include "wgrad_plan.h"
 #include "pack_bodies.h"
 
 namespace zsv {
@@ -306,10 +307,9 @@ static bool s2_plan(const zsv_conv_desc* d, S2Plan& pl) {
     return true;
 }
 
-static size_t s2_align(size_t b) { return (b + 255) & ~(size_t)255; }
 static size_t s2_panel_bytes(const zsv_conv_desc* d, const S2Plan& pl) {
     const int ntap = pl.kind == KIND_HW ? 9 : 3;
-    return s2_align((size_t)pl.nchunks * ntap * 8 * pl.tiles_m * 64 * sizeof(float));
+    return align256((size_t)pl.nchunks * ntap * 8 * pl.tiles_m * 64 * sizeof(float));
 }
 
 bool dgrad_s2_applicable(const zsv_conv_desc* d) {

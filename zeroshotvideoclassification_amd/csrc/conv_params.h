@@ -263,28 +263,34 @@ int wino_fwd_stat_tiles(const zsv_conv_desc* d);
 size_t wino_fwd_workspace_bytes(const zsv_conv_desc* d);
 int wino_fwd(const zsv_conv_desc* d, const float* x, const float* w, const float* bias, const float* residual, int relu,
              float* stat_sum, float* stat_sq, float* y, void* workspace, size_t workspace_bytes, hipStream_t stream, PanelCtx& pc);
-// LDS-DMA weight gradient of stride-1 "same" convolutions (conv_wgrad_dma.hip): writes the per-slice
-// slabs [slice][Cout][taps*Cpad] at the start of `workspace`
-bool wgrad_dma_applicable(const zsv_conv_desc* d, const float* x, const float* dy);
+// ---- the fp32 weight gradient's specialised routes (conv_wgrad.hip keeps the table: priority order, alignment test) ----------
+// `*_shape`: the geometry and the switches admit the route (operand addresses are the dispatch's business); every route writes
+// partial slabs into `workspace`, adds them in a fixed order (wgrad_sum.hip) and writes dw.  `vm_ext` != nullptr: the caller
+// keeps the tap-validity table (zsv_conv3d_wgrad_masked), else the route builds it at the end of `workspace`.
+// LDS-DMA weight gradient of stride-1 "same" convolutions (conv_wgrad_dma.hip)
+bool wgrad_dma_shape(const zsv_conv_desc* d);
 size_t wgrad_dma_workspace_bytes(const zsv_conv_desc* d);
-int wgrad_dma(const zsv_conv_desc* d, const float* x, const float* dy, void* workspace, size_t workspace_bytes,
-              int* slices_out, int* cpad_out, hipStream_t stream, const unsigned* vm_ext = nullptr);
+int wgrad_dma(const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes,
+              hipStream_t stream, const unsigned* vm_ext);
 // per-voxel tap-validity words of one clip (S words; bit tap <=> the tap's input voxel is inside): used by both
 // LDS-DMA weight-gradient kernels
 int wgrad_vmask(const zsv_conv_desc* d, unsigned* out, hipStream_t stream);
-// weight gradient of the temporal 3x1x1 stride-1 convolutions with a ring of dY frames in LDS (conv_wgrad_tring.hip): slabs,
-// ordered reduction; writes dw
-bool wgrad_tring_applicable(const zsv_conv_desc* d, const float* x, const float* dy);
+// the temporal 3x1x1 stride-1 convolutions with a ring of dY frames in LDS (conv_wgrad_tring.hip); pre_coef != nullptr: x is
+// the INPUT of a BatchNorm + ReLU whose output is the convolution's input
+bool wgrad_tring_shape(const zsv_conv_desc* d);
 size_t wgrad_tring_workspace_bytes(const zsv_conv_desc* d);
 int wgrad_tring_pre(const zsv_conv_desc* d, const float* x, const float* pre_coef, int pre_pitch, const float* dy, float* dw,
                     void* workspace, size_t workspace_bytes, hipStream_t stream);
-int wgrad_tring(const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes,
-                hipStream_t stream);
-// Winograd-form weight gradient of the 1x3x3 / 3x3x3 stride-1 "same" convolutions (conv_wgrad_wino.hip): slabs, mask
-// table, ordered reduction and output transform; writes dw
-bool wgrad_wino_applicable(const zsv_conv_desc* d, const float* x, const float* dy);
+// Winograd form of the 1x3x3 / 3x3x3 stride-1 "same" convolutions (conv_wgrad_wino.hip)
+bool wgrad_wino_shape(const zsv_conv_desc* d);
 size_t wgrad_wino_workspace_bytes(const zsv_conv_desc* d);
 int wgrad_wino(const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes,
-               hipStream_t stream, const unsigned* vm_ext = nullptr);
+               hipStream_t stream, const unsigned* vm_ext);
+// the ordered slab sums (wgrad_sum.hip), one per slab layout
+int slab_sum(const float* slabs, float* dw, int M, int Cin, int taps, int Cpad, int slices, hipStream_t stream);
+int slab_sum_flat(const float* slabs, float* dw, long n, int slices, hipStream_t stream);
+int slab_sum_flat_chunked(const float* slabs, float* part, float* dw, long n, int slices, hipStream_t stream);
+int wgrad_tring_sum(const float* slabs, float* dw, int M, int Cin, int slices, bool wino_form, hipStream_t stream);
+int wgrad_wino_sum(const float* slabs, float* dw, int M, int Cin, int R, int Cpad, int slices, int points, hipStream_t stream);
 
 }  // namespace zsv

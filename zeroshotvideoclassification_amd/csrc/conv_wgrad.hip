@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include "conv_params.h"
 #include "knobs.h"
+#include "wgrad_plan.h"
 
 namespace zsv {
 
@@ -308,93 +309,6 @@ __global__ __launch_bounds__(256, (BP == 16 ? 3 : 2)) void conv_wgrad_kernel(Wgr
     }
 }
 
-// dw[co][ci][tap] = sum_s slab[s][co][tap * Cpad + ci].  A block owns 32 consecutive slab elements (ci
-// fastest: coalesced reads) x 8 slice groups: group g adds slices g, g+8, ... in order, the 8 partials
-// are added in group order -- a fixed order, so bitwise reproducible, with 8x the loads in flight of a
-// one-thread-per-element loop (the ~250 slices of a layer1 gradient made that loop latency-bound).
-__global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ slabs, float* __restrict__ out,
-                                                       int M, int Cin, int taps, int Cpad, int slices) {
-    __shared__ float part[8][32];
-    const size_t slab = (size_t)M * taps * Cpad;
-    const int e = threadIdx.x & 31, g = threadIdx.x >> 5;
-    for (size_t j0 = (size_t)blockIdx.x * 32; j0 < slab; j0 += (size_t)gridDim.x * 32) {
-        const size_t j = j0 + e;
-        const int ci = (int)(j % Cpad);
-        const bool live = j < slab && ci < Cin;
-        float s = 0.f;
-        if (live) {
-            const float* src = slabs + j;
-            int k = g;
-            for (; k + 24 < slices; k += 32) {                    // four loads in flight, added in the same order
-                const float v0 = src[(size_t)k * slab], v1 = src[(size_t)(k + 8) * slab];
-                const float v2 = src[(size_t)(k + 16) * slab], v3 = src[(size_t)(k + 24) * slab];
-                s += v0; s += v1; s += v2; s += v3;
-            }
-            for (; k < slices; k += 8) s += src[(size_t)k * slab];
-        }
-        part[g][e] = s;
-        __syncthreads();
-        if (g == 0 && live) {
-            float t = part[0][e];
-#pragma unroll
-            for (int q = 1; q < 8; ++q) t += part[q][e];
-            const size_t r = j / Cpad;
-            const int tap = (int)(r % taps);
-            const int co = (int)(r / taps);
-            out[((size_t)co * Cin + ci) * taps + tap] = t;
-        }
-        __syncthreads();
-    }
-}
-
-// The same sum for FEW slices and a large slab (the small-voxel layers: 2-4 slices of a 17-21 MB gradient): one block per
-// output channel reads its [taps][Cpad] row of every slice with 16-byte loads (coalesced), adds the slices in order (up to 8
-// slices that is also slab_sum_kernel's order: the same bits) and writes dw[co][ci][tap] through an LDS
-// transpose as whole contiguous rows (slab_sum_kernel's 4-byte writes at stride `taps` made it run at 1 TB/s).
-__global__ __launch_bounds__(256) void slab_sum_rows_kernel(const float* __restrict__ slabs, float* __restrict__ out,
-                                                            int M, int Cin, int taps, int Cpad, int slices) {
-    extern __shared__ __attribute__((aligned(16))) float row[];          // [taps][Cpad]
-    const int co = blockIdx.x;
-    const int len = taps * Cpad;                                        // (Cpad % 16 == 0: whole float4s)
-    const size_t slab = (size_t)M * len;
-    const float* src = slabs + (size_t)co * len;
-    for (int i = 4 * (int)threadIdx.x; i < len; i += 1024) {
-        f32x4 t = *reinterpret_cast<const f32x4*>(src + i);
-        int k = 1;
-        for (; k + 2 < slices; k += 3) {                          // three slices' loads in flight, added in the same order
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(src + (size_t)k * slab + i);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(src + (size_t)(k + 1) * slab + i);
-            const f32x4 v2 = *reinterpret_cast<const f32x4*>(src + (size_t)(k + 2) * slab + i);
-            t += v0; t += v1; t += v2;
-        }
-        for (; k < slices; ++k) t += *reinterpret_cast<const f32x4*>(src + (size_t)k * slab + i);
-        *reinterpret_cast<f32x4*>(row + i) = t;
-    }
-    __syncthreads();
-    float* dst = out + (size_t)co * Cin * taps;
-    const int n = Cin * taps;
-    for (int o = (int)threadIdx.x; o < n; o += 256) {
-        const int ci = o / taps, tap = o - ci * taps;
-        dst[o] = row[tap * Cpad + ci];
-    }
-}
-
-// launches the slab sum that fits the geometry (same result bits either way)
-int slab_sum(const float* slabs, float* dw, int M, int Cin, int taps, int Cpad, int slices, hipStream_t stream) {
-    const size_t row_bytes = (size_t)taps * Cpad * sizeof(float);
-    if (slices <= 32 && (long)M * slices <= 16384 && row_bytes <= 64 * 1024 && (reinterpret_cast<uintptr_t>(slabs) & 15) == 0 && !ZSV_KNOB(NO_SLAB_SUM_ROWS)) {
-        static const hipError_t attr = hipFuncSetAttribute((const void*)slab_sum_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        if (attr != hipSuccess) return ZSV_E_LAUNCH;
-        hipLaunchKernelGGL(slab_sum_rows_kernel, dim3((unsigned)M), dim3(256), row_bytes, stream, slabs, dw, M, Cin, taps, Cpad, slices);
-        return hipGetLastError() == hipSuccess ? ZSV_OK : ZSV_E_LAUNCH;
-    }
-    const long n = (long)M * taps * Cpad;
-    long blocks = (n + 31) / 32;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, slabs, dw, M, Cin, taps, Cpad, slices);
-    return hipGetLastError() == hipSuccess ? ZSV_OK : ZSV_E_LAUNCH;
-}
-
 static int wgrad_bp() { return 32; }
 
 // the dense gradient dW'[2 Cout][2 Cin] of a two-frame temporal convolution (conv_params.h: t2_dense_shape) folded back
@@ -419,27 +333,11 @@ struct WgradPlan {
     int Cpad, nblk, Kp;
 };
 
-// Slice count for `tiles` output tiles: one full round of resident workgroups (256 CUs x the
-// LDS-limited 2-4 per CU) -- every workgroup then runs start to finish concurrently and the slab
-// traffic is minimal.  Returns the round-fill efficiency of the best count (fewer slices on ties).
-static double wgrad_slices(long tiles, long chunks, int bp, int bm, int bn, long& slices) {
+// one full round of resident workgroups = 256 CUs x the LDS-limited 2-4 per CU: every workgroup then runs start to finish
+// concurrently and the slab traffic is minimal
+static long wgrad_resident(int bm, int bn) {
     const long lds_bytes = (long)(bm + bn) * 34 * 4 * 2;
-    long per_cu = (160L * 1024) / lds_bytes;
-    if (per_cu > 4) per_cu = 4;
-    if (per_cu < 1) per_cu = 1;
-    const long resident = 256L * per_cu;
-    long max_slices = (chunks * bp + 511) / 512;         // at least 512 voxels per slice
-    if (max_slices < 1) max_slices = 1;
-    if (max_slices > 1024) max_slices = 1024;
-    slices = 1;
-    double best_eff = -1.0;
-    for (long s = 1; s <= max_slices && tiles * s <= 4 * resident + tiles; ++s) {
-        const long wgs = tiles * s;
-        const long rounds = (wgs + resident - 1) / resident;
-        const double eff = (double)wgs / (double)(rounds * resident) - 0.02 * (double)wgs / (double)resident;
-        if (eff > best_eff + 1e-9) { best_eff = eff; slices = s; }
-    }
-    return best_eff;
+    return 256L * clamp1((160L * 1024) / lds_bytes, 4);
 }
 
 static WgradPlan wgrad_plan(const zsv_conv_desc* d) {
@@ -452,6 +350,7 @@ static WgradPlan wgrad_plan(const zsv_conv_desc* d) {
     const long P = (long)d->N * d->To * d->Ho * d->Wo;
     const int bp = wgrad_bp();
     const long chunks = (P + bp - 1) / bp;
+    const long max_slices = clamp1((chunks * bp + 511) / 512, 1024);       // at least 512 voxels per slice
     // Tile = the (rows, columns) pair with the least estimated time: padded MACs x a per-shape factor
     // (narrow tiles issue fewer MFMAs per fragment read) / round-fill efficiency.  Factors fitted on a
     // sweep of all 8 pairs over the R(2+1)D-18 layers at N = 22 (within 0.1 % of the per-layer best).
@@ -460,12 +359,11 @@ static WgradPlan wgrad_plan(const zsv_conv_desc* d) {
     const int bns[2] = {128, 64};
     const double pen_n[2] = {1.00, 1.10};
     int best_m = 0, best_n = 0;
-    double best_w = 1e300;
+    double best_w = 1e300, eff;
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 2; ++j) {
             const long tm = (M + bms[i] - 1) / bms[i], tn = (pl.Kp + bns[j] - 1) / bns[j];
-            long sl;
-            const double eff = wgrad_slices(tm * tn, chunks, bp, bms[i], bns[j], sl);
+            slices_by_fill(tm * tn, wgrad_resident(bms[i], bns[j]), max_slices, &eff);
             const double w = (double)(tm * bms[i]) * (double)(tn * bns[j]) * pen_m[i] * pen_n[j] / (eff > 1e-3 ? eff : 1e-3);
             if (w < best_w * 0.999) { best_w = w; best_m = i; best_n = j; }
         }
@@ -477,14 +375,9 @@ static WgradPlan wgrad_plan(const zsv_conv_desc* d) {
     pl.tiles_m = (M + pl.bm - 1) / pl.bm;
     pl.tiles_n = (pl.Kp + pl.bn - 1) / pl.bn;
     const long tiles = (long)pl.tiles_m * pl.tiles_n;
-    long slices;
-    wgrad_slices(tiles, chunks, bp, pl.bm, pl.bn, slices);
-    const long max_slices = ((chunks * bp + 511) / 512) < 1 ? 1 : ((chunks * bp + 511) / 512 > 1024 ? 1024 : (chunks * bp + 511) / 512);
+    long slices = slices_by_fill(tiles, wgrad_resident(pl.bm, pl.bn), max_slices, &eff);
     if (const char* e = ZSV_KNOB(WGRAD_WGS)) slices = atol(e) / tiles;
-    if (slices > max_slices) slices = max_slices;
-    if (slices < 1) slices = 1;
-    pl.chunks_per_slice = (int)((chunks + slices - 1) / slices);
-    pl.slices = (int)((chunks + pl.chunks_per_slice - 1) / pl.chunks_per_slice);
+    split_chunks(chunks, clamp1(slices, max_slices), &pl.chunks_per_slice, &pl.slices);
     return pl;
 }
 
@@ -507,12 +400,84 @@ static bool wgrad_two_taps(int taps, int nblk, int bn) {
     return true;
 }
 
+static size_t wgrad_staged_workspace_bytes(const zsv_conv_desc* d) {
+    const WgradPlan pl = wgrad_plan(d);
+    return (size_t)pl.slices * d->Cout * pl.Kp * sizeof(float);
+}
+
+// the register-staged kernel above: any geometry with Cin >= 16, operands at any 4-byte aligned address
+static int wgrad_staged(const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, hipStream_t stream) {
+    const WgradPlan pl = wgrad_plan(d);
+    WgradParams p;
+    p.M = d->Cout;
+    p.Cin = d->Cin; p.Cpad = pl.Cpad; p.nblk = pl.nblk;
+    p.taps = d->kT * d->kH * d->kW;
+    p.kHW = d->kH * d->kW; p.kW = d->kW;
+    p.Kp = pl.Kp;
+    p.P = d->N * d->To * d->Ho * d->Wo;
+    p.oS = d->To * d->Ho * d->Wo; p.oHW = d->Ho * d->Wo; p.oW = d->Wo;
+    p.m_oS = make_magic((unsigned)p.oS); p.m_oHW = make_magic((unsigned)p.oHW); p.m_oW = make_magic((unsigned)p.oW);
+    p.gT = d->Ti; p.gH = d->Hi; p.gW = d->Wi;
+    p.gS = d->Ti * d->Hi * d->Wi; p.gHW = d->Hi * d->Wi; p.gCS = d->Cin * p.gS;
+    p.sT = d->sT; p.sH = d->sH; p.sW = d->sW; p.pT = d->pT; p.pH = d->pH; p.pW = d->pW;
+    p.chunks_per_slice = pl.chunks_per_slice;
+    p.x_bytes = 4u * (unsigned)((long)d->N * d->Cin * p.gS);
+    p.dy_bytes = 4u * (unsigned)((long)d->N * d->Cout * p.oS);
+
+    const bool av4 = (p.oS % 4 == 0) && (p.P >= 4) && aligned16(dy);
+    const bool twotap = wgrad_two_taps(p.taps, pl.nblk, pl.bn) && !ZSV_KNOB(WGRAD_NO_TWOTAP);
+    const int tiles_mn = pl.tiles_m * pl.tiles_n;
+    const dim3 grid((unsigned)(tiles_mn * pl.slices));
+    float* out = (float*)workspace;
+    if (pl.bn == 64) {
+        switch (pl.cfg) {
+            case 0: wgrad_launch<9, 1, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
+            case 1: wgrad_launch<8, 1, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
+            case 2: wgrad_launch<4, 1, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
+            default: wgrad_launch<5, 1, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
+        }
+    } else
+    switch (pl.cfg) {
+        case 0: wgrad_launch<9, 2, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
+        case 1: wgrad_launch<4, 4, 2, 2>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
+        case 2: wgrad_launch<4, 2, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
+        default: wgrad_launch<5, 2, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
+    }
+    if (hipGetLastError() != hipSuccess) return ZSV_E_LAUNCH;
+    return slab_sum((const float*)workspace, dw, p.M, p.Cin, p.taps, pl.Cpad, pl.slices, stream);
+}
+
+// ---- the specialised routes, in priority order ---------------------------------------------------------------------------
+// Every user below walks this table: the workspace query (any route the shape admits may run: the operands' alignment decides at
+// call time), the mask query, the dispatch and the prologue form.  A route takes x and dy at 16-byte aligned addresses only
+// (16-byte LDS-DMAs); that is tested once, in wgrad_dispatch, and the register-staged kernel serves the rest.
+struct WgradRoute {
+    bool (*shape)(const zsv_conv_desc* d);              // the geometry and the switches admit it
+    size_t (*workspace_bytes)(const zsv_conv_desc* d);
+    bool takes_mask;                                    // reads the per-voxel tap-validity table (wgrad_vmask)
+    int (*run)(const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes,
+               hipStream_t stream, const unsigned* vm_ext);
+};
+enum { ROUTE_WINO, ROUTE_TRING, ROUTE_DMA, ROUTE_COUNT };
+static const WgradRoute wgrad_routes[ROUTE_COUNT] = {
+    {wgrad_wino_shape, wgrad_wino_workspace_bytes, true, wgrad_wino},
+    {wgrad_tring_shape, wgrad_tring_workspace_bytes, false,
+     [](const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes, hipStream_t stream,
+        const unsigned*) { return wgrad_tring_pre(d, x, nullptr, 0, dy, dw, workspace, workspace_bytes, stream); }},
+    {wgrad_dma_shape, wgrad_dma_workspace_bytes, true, wgrad_dma},
+};
+static const WgradRoute* wgrad_route(const zsv_conv_desc* d) {
+    for (const WgradRoute& r : wgrad_routes)
+        if (r.shape(d)) return &r;
+    return nullptr;
+}
+
 }  // namespace zsv
 
 using namespace zsv;
 
 static bool t2_dense(const zsv_conv_desc* d) { return t2_dense_shape(d) && !ZSV_KNOB(NO_T2_DENSE); }
-static size_t t2_dw_bytes(const zsv_conv_desc* d) { return ((size_t)4 * d->Cout * d->Cin * sizeof(float) + 255) & ~(size_t)255; }
+static size_t t2_dw_bytes(const zsv_conv_desc* d) { return align256((size_t)4 * d->Cout * d->Cin * sizeof(float)); }
 
 extern "C" size_t zsv_conv3d_wgrad_workspace_bytes(const zsv_conv_desc* d) {
     if (conv_check(d) != ZSV_OK) return 0;
@@ -521,20 +486,12 @@ extern "C" size_t zsv_conv3d_wgrad_workspace_bytes(const zsv_conv_desc* d) {
         return t2_dw_bytes(d) + zsv_conv3d_wgrad_workspace_bytes(&d2);
     }
     if (d->Cin < 16) return wgrad_generic_workspace_bytes(d);
-    const WgradPlan pl = wgrad_plan(d);
-    size_t need = (size_t)pl.slices * d->Cout * pl.Kp * sizeof(float);
-    if (wgrad_dma_applicable(d, nullptr, nullptr)) {        // (the pointer alignment decides at call time)
-        const size_t b = wgrad_dma_workspace_bytes(d);
-        if (b > need) need = b;
-    }
-    if (wgrad_wino_applicable(d, nullptr, nullptr)) {
-        const size_t b = wgrad_wino_workspace_bytes(d);
-        if (b > need) need = b;
-    }
-    if (wgrad_tring_applicable(d, nullptr, nullptr)) {
-        const size_t b = wgrad_tring_workspace_bytes(d);
-        if (b > need) need = b;
-    }
+    size_t need = wgrad_staged_workspace_bytes(d);
+    for (const WgradRoute& r : wgrad_routes)
+        if (r.shape(d)) {
+            const size_t b = r.workspace_bytes(d);
+            if (b > need) need = b;
+        }
     return need;
 }
 
@@ -546,7 +503,7 @@ extern "C" int zsv_conv3d_wgrad_pre(const zsv_conv_desc* d, const float* x, cons
     // (the shape alone decides: the frame-ring kernel is the only one with the prologue, and its 16-byte LDS-DMAs take x and dy at any
     // 4-byte aligned address -- the same bits as on aligned ones, tests/test_alignment_gpu.py; zsv_conv3d_wgrad's dispatch, which has
     // other kernels to give such tensors to, keeps asking for 16 bytes)
-    if (!zsv_conv3d_pre_supported(d) || coef_pitch < d->Cin || !wgrad_tring_applicable(d, nullptr, nullptr)) return ZSV_E_UNSUPPORTED;
+    if (!zsv_conv3d_pre_supported(d) || coef_pitch < d->Cin || !wgrad_routes[ROUTE_TRING].shape(d)) return ZSV_E_UNSUPPORTED;
     if (!workspace || workspace_bytes < zsv_conv3d_wgrad_workspace_bytes(d)) return ZSV_E_WORKSPACE;
     return wgrad_tring_pre(d, x, pre_coef, coef_pitch, dy, dw, workspace, workspace_bytes, (hipStream_t)stream_);
 }
@@ -564,9 +521,8 @@ extern "C" int zsv_conv3d_wgrad(const zsv_conv_desc* d, const float* x, const fl
 // the kernels of the weight-gradient queue).  A caller that keeps the table passes it here.
 static bool wgrad_takes_mask(const zsv_conv_desc* d) {
     if (conv_check(d) != ZSV_OK || t2_dense(d) || d->Cin < 16) return false;
-    if (wgrad_wino_applicable(d, nullptr, nullptr)) return true;
-    if (wgrad_tring_applicable(d, nullptr, nullptr)) return false;
-    return wgrad_dma_applicable(d, nullptr, nullptr);
+    const WgradRoute* r = wgrad_route(d);
+    return r != nullptr && r->takes_mask;
 }
 
 extern "C" size_t zsv_conv3d_wgrad_mask_bytes(const zsv_conv_desc* d) {
@@ -604,55 +560,10 @@ static int wgrad_dispatch(const zsv_conv_desc* d, const float* x, const float* d
         return hipGetLastError() == hipSuccess ? ZSV_OK : ZSV_E_LAUNCH;
     }
     if (d->Cin < 16) return wgrad_generic(d, x, dy, dw, workspace, workspace_bytes, stream);
-    const WgradPlan pl = wgrad_plan(d);
-    const size_t need = zsv_conv3d_wgrad_workspace_bytes(d);
-    if (!workspace || workspace_bytes < need) return ZSV_E_WORKSPACE;
-    if (wgrad_wino_applicable(d, x, dy)) return wgrad_wino(d, x, dy, dw, workspace, workspace_bytes, stream, vm_ext);
-    if (wgrad_tring_applicable(d, x, dy)) return wgrad_tring(d, x, dy, dw, workspace, workspace_bytes, stream);
-    if (wgrad_dma_applicable(d, x, dy)) {
-        int slices = 0, cpad = 0;
-        st = wgrad_dma(d, x, dy, workspace, workspace_bytes, &slices, &cpad, stream, vm_ext);
-        if (st) return st;
-        return slab_sum((const float*)workspace, dw, d->Cout, d->Cin, d->kT * d->kH * d->kW, cpad, slices, stream);
-    }
-
-    WgradParams p;
-    p.M = d->Cout;
-    p.Cin = d->Cin; p.Cpad = pl.Cpad; p.nblk = pl.nblk;
-    p.taps = d->kT * d->kH * d->kW;
-    p.kHW = d->kH * d->kW; p.kW = d->kW;
-    p.Kp = pl.Kp;
-    p.P = d->N * d->To * d->Ho * d->Wo;
-    p.oS = d->To * d->Ho * d->Wo; p.oHW = d->Ho * d->Wo; p.oW = d->Wo;
-    p.m_oS = make_magic((unsigned)p.oS); p.m_oHW = make_magic((unsigned)p.oHW); p.m_oW = make_magic((unsigned)p.oW);
-    p.gT = d->Ti; p.gH = d->Hi; p.gW = d->Wi;
-    p.gS = d->Ti * d->Hi * d->Wi; p.gHW = d->Hi * d->Wi; p.gCS = d->Cin * p.gS;
-    p.sT = d->sT; p.sH = d->sH; p.sW = d->sW; p.pT = d->pT; p.pH = d->pH; p.pW = d->pW;
-    p.chunks_per_slice = pl.chunks_per_slice;
-    p.x_bytes = 4u * (unsigned)((long)d->N * d->Cin * p.gS);
-    p.dy_bytes = 4u * (unsigned)((long)d->N * d->Cout * p.oS);
-
-    const bool av4 = (p.oS % 4 == 0) && (p.P >= 4) && ((reinterpret_cast<uintptr_t>(dy) & 15) == 0);
-    const bool twotap = wgrad_two_taps(p.taps, pl.nblk, pl.bn) && !ZSV_KNOB(WGRAD_NO_TWOTAP);
-    const int tiles_mn = pl.tiles_m * pl.tiles_n;
-    const dim3 grid((unsigned)(tiles_mn * pl.slices));
-    float* out = (float*)workspace;
-    if (pl.bn == 64) {
-        switch (pl.cfg) {
-            case 0: wgrad_launch<9, 1, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
-            case 1: wgrad_launch<8, 1, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
-            case 2: wgrad_launch<4, 1, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
-            default: wgrad_launch<5, 1, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
-        }
-    } else
-    switch (pl.cfg) {
-        case 0: wgrad_launch<9, 2, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
-        case 1: wgrad_launch<4, 4, 2, 2>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
-        case 2: wgrad_launch<4, 2, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
-        default: wgrad_launch<5, 2, 1, 4>(p, av4, twotap, grid, stream, x, dy, out, pl.tiles_m, tiles_mn); break;
-    }
-    if (hipGetLastError() != hipSuccess) return ZSV_E_LAUNCH;
-    return slab_sum((const float*)workspace, dw, p.M, p.Cin, p.taps, pl.Cpad, pl.slices, stream);
+    if (!workspace || workspace_bytes < zsv_conv3d_wgrad_workspace_bytes(d)) return ZSV_E_WORKSPACE;
+    if (aligned16(x, dy))
+        if (const WgradRoute* r = wgrad_route(d)) return r->run(d, x, dy, dw, workspace, workspace_bytes, stream, vm_ext);
+    return wgrad_staged(d, x, dy, dw, workspace, stream);
 }
 
 extern "C" size_t zsv_linear_wgrad_workspace_bytes(int32_t rows, int32_t in_features, int32_t out_features) {

@@ -17,7 +17,7 @@
 //     call by wgrad_vmask_kernel, S words) is DMA'd next to the operands; a lane zeroes the voxels of
 //     its 4 whose tap falls outside the input.  Rows read past a clip plane pick up the neighbouring
 //     plane's values, which the same mask discards.
-// Output: the same per-slice slabs OUT[slice][co][tap*Cpad + ci] as conv_wgrad.hip (slab_sum_kernel
+// Output: the same per-slice slabs OUT[slice][co][tap*Cpad + ci] as conv_wgrad.hip (slab_sum, wgrad_sum.hip,
 // reduces them in slice order: bitwise reproducible).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -26,6 +26,7 @@
 #include "zsv_common.h"
 #include "zsv_hip.h"
 #include "knobs.h"
+#include "wgrad_plan.h"
 
 namespace zsv {
 
@@ -294,7 +295,7 @@ __global__ __launch_bounds__(256, (TM * TN > 27 ? 2 : 3)) void conv_wgrad_dma_ke
 }
 
 // ---- host side -----------------------------------------------------------------------------------
-bool wgrad_dma_applicable(const zsv_conv_desc* d, const float* x, const float* dy) {
+bool wgrad_dma_shape(const zsv_conv_desc* d) {
     if (ZSV_KNOB(NO_WGRAD_DMA)) return false;
     if (d->Cin < 16 || d->Cout < 16) return false;
     if (d->sT != 1 || d->sH != 1 || d->sW != 1) return false;
@@ -303,7 +304,6 @@ bool wgrad_dma_applicable(const zsv_conv_desc* d, const float* x, const float* d
     if (S % 16 != 0 || d->kT * d->kH * d->kW > 32) return false;
     if (d->kT * d->kH * d->kW * ((d->Cin + 15) / 16 * 16) < 256) return false;     // few columns (T0: 144): measured slower
     if ((long)d->N * d->Cin * S >= (1L << 31) || (long)d->N * d->Cout * S >= (1L << 31)) return false;
-    if (x != nullptr && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) != 0) return false;
     return true;
 }
 
@@ -324,9 +324,7 @@ static WgradDmaPlan wgrad_dma_plan(const zsv_conv_desc* d) {
     const double pen_m[4] = {1.00, 1.00, 1.05, 1.08};
     const int tns[4] = {2, 3, 1, 7};                    // 7: a 64-row problem with <= 448 columns in ONE tile (dY read once)
     const double pen_n[4] = {1.00, 1.00, 1.06, 1.00};
-    long max_slices = (chunks * 16 + 511) / 512;         // at least 512 voxels per slice
-    if (max_slices < 1) max_slices = 1;
-    if (max_slices > 1024) max_slices = 1024;
+    const long max_slices = clamp1((chunks * 16 + 511) / 512, 1024);       // at least 512 voxels per slice
     double best_w = 1e300;
     pl.tm = 9; pl.tn = 2; pl.slices = 1;
     for (int i = 0; i < 4; ++i)
@@ -338,14 +336,8 @@ static WgradDmaPlan wgrad_dma_plan(const zsv_conv_desc* d) {
             long per_cu = (160L * 1024) / lds;
             const long by_regs = tms[i] * tns[j] > 27 ? 2 : 3;     // __launch_bounds__
             if (per_cu > by_regs) per_cu = by_regs;
-            const long resident = 256L * per_cu;
-            long sl = 1;
-            double best_eff = -1.0;
-            for (long s = 1; s <= max_slices && tiles * s <= 4 * resident + tiles; ++s) {
-                const long wgs = tiles * s, rounds = (wgs + resident - 1) / resident;
-                const double eff = (double)wgs / (double)(rounds * resident) - 0.02 * (double)wgs / (double)resident;
-                if (eff > best_eff + 1e-9) { best_eff = eff; sl = s; }
-            }
+            double best_eff;
+            const long sl = slices_by_fill(tiles, 256L * per_cu, max_slices, &best_eff);
             const double w = (double)(tm_ * bm) * (double)(tn_ * bn) * pen_m[i] * pen_n[j] / (best_eff > 1e-3 ? best_eff : 1e-3);
             if (w < best_w * 0.999) { best_w = w; pl.tm = tms[i]; pl.tn = tns[j]; pl.slices = (int)sl; }
         }
@@ -355,14 +347,9 @@ static WgradDmaPlan wgrad_dma_plan(const zsv_conv_desc* d) {
     pl.tiles_m = (M + bm - 1) / bm;
     pl.tiles_n = (pl.Kp + bn - 1) / bn;
     if (const char* e = ZSV_KNOB(WGRAD_DMA_SLICES)) pl.slices = atoi(e);
-    if (pl.slices > max_slices) pl.slices = (int)max_slices;
-    if (pl.slices < 1) pl.slices = 1;
-    pl.chunks_per_slice = (int)((chunks + pl.slices - 1) / pl.slices);
-    pl.slices = (int)((chunks + pl.chunks_per_slice - 1) / pl.chunks_per_slice);
+    split_chunks(chunks, clamp1(pl.slices, max_slices), &pl.chunks_per_slice, &pl.slices);
     return pl;
 }
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 size_t wgrad_dma_workspace_bytes(const zsv_conv_desc* d) {
     const WgradDmaPlan pl = wgrad_dma_plan(d);
@@ -403,9 +390,9 @@ int wgrad_vmask(const zsv_conv_desc* d, unsigned* out, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? ZSV_OK : ZSV_E_LAUNCH;
 }
 
-// slabs + mask table live in `workspace`; returns the slab geometry for slab_sum_kernel
-int wgrad_dma(const zsv_conv_desc* d, const float* x, const float* dy, void* workspace, size_t workspace_bytes,
-              int* slices_out, int* cpad_out, hipStream_t stream, const unsigned* vm_ext) {
+// slabs + mask table live in `workspace`
+int wgrad_dma(const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes,
+              hipStream_t stream, const unsigned* vm_ext) {
     const WgradDmaPlan pl = wgrad_dma_plan(d);
     if (!workspace || workspace_bytes < wgrad_dma_workspace_bytes(d)) return ZSV_E_WORKSPACE;
     WgradDmaParams p;
@@ -432,9 +419,8 @@ int wgrad_dma(const zsv_conv_desc* d, const float* x, const float* dy, void* wor
         case 5: st = wgrad_dma_launch_tn<5>(pl.tn, p, pl.slices, stream, x, dy, vm, slabs); break;
         default: st = wgrad_dma_launch_tn<4>(pl.tn, p, pl.slices, stream, x, dy, vm, slabs); break;
     }
-    *slices_out = pl.slices;
-    *cpad_out = pl.Cpad;
-    return st;
+    if (st) return st;
+    return slab_sum(slabs, dw, p.M, p.Cin, p.taps, pl.Cpad, pl.slices, stream);
 }
 
 }  // namespace zsv

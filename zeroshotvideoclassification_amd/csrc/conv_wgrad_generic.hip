@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include "conv_params.h"
 #include "knobs.h"
+#include "wgrad_plan.h"
 
 namespace zsv {
 
@@ -187,30 +188,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_generic_kernel(WgradGenParams 
     }
 }
 
-// dw[i] = sum_s slab[s][i].  A block owns 32 elements x 8 slice groups (group g adds slices
-// g, g+8, ... in order; the 8 partials are then added in group order): fixed order, deterministic,
-// and the few thousand elements of a stem gradient still spread over the whole chip.
-__global__ __launch_bounds__(256) void slab_sum_generic_kernel(const float* __restrict__ slabs, float* __restrict__ out,
-                                                       long n, int slices) {
-    __shared__ float part[8][32];
-    const int e = threadIdx.x & 31, g = threadIdx.x >> 5;
-    for (long i0 = (long)blockIdx.x * 32; i0 < n; i0 += (long)gridDim.x * 32) {
-        const long i = i0 + e;
-        float s = 0.f;
-        if (i < n)
-            for (int k = g; k < slices; k += 8) s += slabs[(size_t)k * n + i];
-        part[g][e] = s;
-        __syncthreads();
-        if (g == 0 && i < n) {
-            float t = part[0][e];
-#pragma unroll
-            for (int q = 1; q < 8; ++q) t += part[q][e];
-            out[i] = t;
-        }
-        __syncthreads();
-    }
-}
-
 // ================================================================================================
 // The R(2+1)D stem's weight gradient (resnet.py:170: Conv3d(3, 45, (1,7,7), stride (1,2,2), padding (0,3,3))) with its operands as ROWS.
 // It is the last kernel of a training step and runs alone (its dY is the last gradient the backward produces), so its time is on the
@@ -223,7 +200,7 @@ __global__ __launch_bounds__(256) void slab_sum_generic_kernel(const float* __re
 //     fragment is read at stride 2 along the row (address 2w' + kw + 1), the row out of the image is a DMA that reads zeros;
 //   * columns = 3 x 64 (a channel's 49 taps padded to 64), wave w owns columns 16w .. 16w+15 of each channel, 3 x 3 accumulator tiles;
 //   * a workgroup walks `rows` consecutive output rows of one frame and writes its partial dW in the weight tensor's own layout; the
-//     partials are added in a fixed order by slab_sum_generic_kernel.
+//     partials are added in a fixed order by the flat slab sum (wgrad_sum.hip).
 struct StemWgradParams {
     int N, T, Ho, Wo, Hi, Wi, Cout;
     int rows, parts;                 // output rows per workgroup, workgroups per frame
@@ -372,17 +349,6 @@ static int stem_wgrad_parts(const zsv_conv_desc* d) {
     return (int)((d->Ho + rows - 1) / rows);
 }
 
-// first level of a two-level slab sum: block row c adds slabs [c * per, (c + 1) * per) into part[c][i] (fixed order)
-__global__ __launch_bounds__(256) void slab_sum_chunks_kernel(const float* __restrict__ slabs, float* __restrict__ part, long n, int slices,
-                                                              int per) {
-    const int c = blockIdx.y, k0 = c * per, k1 = min(slices, k0 + per);
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        float s = 0.f;
-        for (int k = k0; k < k1; ++k) s += slabs[(size_t)k * n + i];
-        part[(size_t)c * n + i] = s;
-    }
-}
-
 struct WgradGenPlan {
     int cfg;        // 0: 128x128, 1: 64x128 (small Cout), 2: 144x64
     int tiles_m, tiles_n, slices, chunks_per_slice;
@@ -407,11 +373,9 @@ static WgradGenPlan wgrad_gen_plan(const zsv_conv_desc* d) {
     if (slices > max_slices) slices = max_slices;
     if (slices < 1) slices = 1;
     if (slices > 1024) slices = 1024;
-    pl.chunks_per_slice = (int)((chunks + slices - 1) / slices);
-    pl.slices = (int)((chunks + pl.chunks_per_slice - 1) / pl.chunks_per_slice);
+    split_chunks(chunks, slices, &pl.chunks_per_slice, &pl.slices);
     return pl;
 }
-
 
 static size_t wgrad_gen_plan_bytes(const zsv_conv_desc* d) {
     const WgradGenPlan pl = wgrad_gen_plan(d);
@@ -430,7 +394,7 @@ size_t wgrad_generic_workspace_bytes(const zsv_conv_desc* d) {
 
 int wgrad_generic(const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace,
                   size_t workspace_bytes, hipStream_t stream) {
-    if (stem_wgrad_shape(d) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0) {
+    if (stem_wgrad_shape(d) && aligned16(x, dy)) {
         if (!workspace || workspace_bytes < stem_wgrad_bytes(d)) return ZSV_E_WORKSPACE;
         StemWgradParams p;
         p.N = d->N; p.T = d->To; p.Ho = d->Ho; p.Wo = d->Wo; p.Hi = d->Hi; p.Wi = d->Wi; p.Cout = d->Cout;
@@ -442,19 +406,9 @@ int wgrad_generic(const zsv_conv_desc* d, const float* x, const float* dy, float
         hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, p, x, dy, (float*)workspace);
         if (hipGetLastError() != hipSuccess) return ZSV_E_LAUNCH;
         const long n = (long)d->Cout * 147;
-        const long blocks = (n + 31) / 32;
-        if (wgs <= 64) {
-            hipLaunchKernelGGL(slab_sum_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)workspace, dw, n, (int)wgs);
-            return hipGetLastError() == hipSuccess ? ZSV_OK : ZSV_E_LAUNCH;
-        }
-        // two levels, both in a fixed order: 32 chunks of slabs, then the 32 partial sums
-        float* part = (float*)workspace + (size_t)wgs * n;
-        const int per = (int)((wgs + 31) / 32), chunks = (int)((wgs + per - 1) / per);
-        hipLaunchKernelGGL(slab_sum_chunks_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)chunks), dim3(256), 0, stream, (const float*)workspace,
-                           part, n, (int)wgs, per);
-        if (hipGetLastError() != hipSuccess) return ZSV_E_LAUNCH;
-        hipLaunchKernelGGL(slab_sum_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)part, dw, n, chunks);
-        return hipGetLastError() == hipSuccess ? ZSV_OK : ZSV_E_LAUNCH;
+        const float* slabs = (const float*)workspace;
+        if (wgs <= 64) return slab_sum_flat(slabs, dw, n, (int)wgs, stream);
+        return slab_sum_flat_chunked(slabs, (float*)workspace + (size_t)wgs * n, dw, n, (int)wgs, stream);
     }
     const WgradGenPlan pl = wgrad_gen_plan(d);
     const size_t need = wgrad_gen_plan_bytes(d);
@@ -480,13 +434,7 @@ int wgrad_generic(const zsv_conv_desc* d, const float* x, const float* dy, float
         default: hipLaunchKernelGGL((conv_wgrad_generic_kernel<9, 1, 1, 4>), grid, dim3(256), 0, stream, p, x, dy, out, pl.tiles_m); break;
     }
     if (hipGetLastError() != hipSuccess) return ZSV_E_LAUNCH;
-    if (pl.slices > 1) {
-        const long n = (long)p.M * p.K;
-        long blocks = (n + 31) / 32;
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(slab_sum_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)workspace, dw, n, pl.slices);
-        if (hipGetLastError() != hipSuccess) return ZSV_E_LAUNCH;
-    }
+    if (pl.slices > 1) return slab_sum_flat((const float*)workspace, dw, (long)p.M * p.K, pl.slices, stream);
     return ZSV_OK;
 }
 

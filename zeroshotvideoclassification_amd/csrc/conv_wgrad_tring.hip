@@ -13,7 +13,7 @@
 // of 16, three per wave; MFMA k order k = 4*(lane>>4) + step, so a lane reads its row's 4 voxels for the 4 steps with one
 // ds_read_b128; LDS rows are 64 bytes with the 16-byte slot XOR-swizzled on the source side (conflict-free fragments, as in
 // conv_wgrad_dma.hip).  The reduction is cut into slices (about one round of resident workgroups); slices write slabs
-// [slice][ci][kt*M + co], wgrad_tring_sum_kernel adds them in a fixed order: bitwise reproducible.
+// [slice][ci][kt*M + co], the ring sum (wgrad_sum.hip) adds them in a fixed order: bitwise reproducible.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
@@ -21,6 +21,7 @@
 #include "zsv_common.h"
 #include "zsv_hip.h"
 #include "knobs.h"
+#include "wgrad_plan.h"
 
 namespace zsv {
 
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_tring_kernel(WgradTringPara
 // (TM blocks), columns = (point, 64 output channels) = 16 blocks, wave w = output-channel block w with its four points.  X frames
 // live in a FIFO ring of 6 slots (4 in use + the next pair's 2, or the next segment's first 3 while the last pair of a segment
 // runs: its frame T is padding and needs no slot), dY frame pairs in 2 x 2 slots.  Slabs [slice][point][ci][co], summed in a fixed
-// order by wgrad_twino_sum_kernel, which also applies the output transform.  PRE as above.
+// order by the ring sum's Winograd form (wgrad_sum.hip), which also applies the output transform.  PRE as above.
 template <int TM, bool PRE>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_twino_kernel(WgradTringParams prm, const float* __restrict__ X,
                                                                   const float* __restrict__ DY, float* __restrict__ OUT) {
@@ -384,106 +385,24 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_twino_kernel(WgradTringPara
 #endif
 }
 
-// dW[co][ci][kt] from the slabs [slice][point][ci][co]: fixed summation order (8 slice groups, then the groups), then the
-// output transform of the Winograd form
-__global__ __launch_bounds__(256) void wgrad_twino_sum_kernel(const float* __restrict__ slabs, float* __restrict__ dw, int M,
-                                                              int Cin, int slices) {
-    __shared__ float part[8][4][32];
-    const size_t plane = (size_t)Cin * M;
-    const int e = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    for (size_t j0 = (size_t)blockIdx.x * 32; j0 < plane; j0 += (size_t)gridDim.x * 32) {
-        const size_t j = j0 + e;
-        const bool live = j < plane;
-        float s[4] = {0.f, 0.f, 0.f, 0.f};
-        if (live) {
-            // (the loads of four slices are issued before their adds -- same order of addition, same bits: one slice at a time the
-            // loop waited out an HBM round trip per slice, 86 us for the 512 slices of a layer1 gradient)
-            int k = grp;
-            for (; k + 24 < slices; k += 32) {
-                float v[4][4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) v[u][p] = slabs[((size_t)(k + 8 * u) * 4 + p) * plane + j];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) s[p] += v[u][p];
-            }
-            for (; k < slices; k += 8)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) s[p] += slabs[((size_t)k * 4 + p) * plane + j];
-        }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) part[grp][p][e] = s[p];
-        __syncthreads();
-        if (grp == 0 && live) {
-            float Mv[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                float t = part[0][p][e];
-#pragma unroll
-                for (int q = 1; q < 8; ++q) t += part[q][p][e];
-                Mv[p] = t;
-            }
-            const int co = (int)(j % M), ci = (int)(j / M);
-            float* o = dw + ((size_t)co * Cin + ci) * 3;
-            const float h = 0.5f * (Mv[1] + Mv[2]);
-            o[0] = Mv[0] + h;
-            o[1] = 0.5f * (Mv[1] - Mv[2]);
-            o[2] = h - Mv[3];
-        }
-        __syncthreads();
-    }
-}
-
-// dW[co][ci][kt] from the slabs [slice][ci][kt * M + co]: 32 elements x 8 slice groups per block, fixed order
-__global__ __launch_bounds__(256) void wgrad_tring_sum_kernel(const float* __restrict__ slabs, float* __restrict__ dw, int M,
-                                                              int Cin, int slices) {
-    __shared__ float part[8][32];
-    const size_t slab = (size_t)Cin * 3 * M;
-    const int e = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    for (size_t j0 = (size_t)blockIdx.x * 32; j0 < slab; j0 += (size_t)gridDim.x * 32) {
-        const size_t j = j0 + e;
-        const bool live = j < slab;
-        float s = 0.f;
-        if (live) {
-            int k = grp;
-            for (; k + 24 < slices; k += 32) {                    // four loads in flight, added in the same order
-                const float v0 = slabs[(size_t)k * slab + j], v1 = slabs[(size_t)(k + 8) * slab + j];
-                const float v2 = slabs[(size_t)(k + 16) * slab + j], v3 = slabs[(size_t)(k + 24) * slab + j];
-                s += v0; s += v1; s += v2; s += v3;
-            }
-            for (; k < slices; k += 8) s += slabs[(size_t)k * slab + j];
-        }
-        part[grp][e] = s;
-        __syncthreads();
-        if (grp == 0 && live) {
-            float v = part[0][e];
-#pragma unroll
-            for (int q = 1; q < 8; ++q) v += part[q][e];
-            const int co = (int)(j % M);
-            const size_t rr = j / M;
-            const int kt = (int)(rr % 3), ci = (int)(rr / 3);
-            dw[((size_t)co * Cin + ci) * 3 + kt] = v;
-        }
-        __syncthreads();
-    }
-}
-
 // ---- host side -----------------------------------------------------------------------------------
 struct WgradTringPlan {
     int tm, tiles_m, tiles_n, slices, chunks_per_slice;
 };
 
-static WgradTringPlan wgrad_tring_plan(const zsv_conv_desc* d) {
+// the part both forms share: 144- or 128-row tiles of input channels x 64-column tiles of output channels
+static WgradTringPlan wgrad_tring_tiles(const zsv_conv_desc* d) {
     WgradTringPlan pl;
-    const int C = d->Cin;
-    const int p9 = (C + 143) / 144 * 144, p8 = (C + 127) / 128 * 128;
-    pl.tm = p9 <= p8 ? 9 : 8;
-    const int bm = 16 * pl.tm;
-    pl.tiles_m = (C + bm - 1) / bm;
+    pl.tm = rows_144_or_128(d->Cin) / 16;
+    pl.tiles_m = (d->Cin + 16 * pl.tm - 1) / (16 * pl.tm);
     pl.tiles_n = (d->Cout + 63) / 64;
+    pl.slices = pl.chunks_per_slice = 0;
+    return pl;
+}
+
+static WgradTringPlan wgrad_tring_plan(const zsv_conv_desc* d) {
+    WgradTringPlan pl = wgrad_tring_tiles(d);
+    const int C = d->Cin, bm = 16 * pl.tm;
     const long chunks = (long)d->N * d->Ti * (d->Hi * d->Wi / 16);
     const long tiles = (long)pl.tiles_m * pl.tiles_n;
     long resident = pl.tm == 9 ? 512 : 768;                // workgroups per round (3 fit a CU; measured: 2 per CU is the better fill for the 144-row tile)
@@ -491,24 +410,14 @@ static WgradTringPlan wgrad_tring_plan(const zsv_conv_desc* d) {
     // slices: MFMA time / fill of the rounds of resident workgroups + slab write / read, >= 32 chunks per slice
     const double t_mfma = 2.0 * (double)(pl.tiles_m * bm) * (double)(pl.tiles_n * 192) * (double)chunks * 16.0 / 1.1e14;
     const double t_slice = 2.0 * (double)C * 3.0 * d->Cout * sizeof(float) / 6.0e12;
-    long max_sl = chunks / 32;
-    if (max_sl < 1) max_sl = 1;
-    if (max_sl > 4096) max_sl = 4096;
-    long sl = 1;
-    double best = 1e300;
-    for (long c = 1; c <= max_sl; ++c) {
-        const long wgs = tiles * c, rounds = (wgs + resident - 1) / resident;
-        const double cost = t_mfma * (double)(rounds * resident) / (double)wgs + t_slice * (double)c;
-        if (cost < best * 0.999) { best = cost; sl = c; }
-    }
+    long sl = slices_by_cost(tiles, resident, t_mfma, t_slice, clamp1(chunks / 32, 4096));
     if (const char* e = ZSV_KNOB(WGRAD_TRING_SLICES)) sl = atol(e) > 0 ? atol(e) : 1;
     if (sl > chunks) sl = chunks;
-    pl.chunks_per_slice = (int)((chunks + sl - 1) / sl);
-    pl.slices = (int)((chunks + pl.chunks_per_slice - 1) / pl.chunks_per_slice);
+    split_chunks(chunks, sl, &pl.chunks_per_slice, &pl.slices);
     return pl;
 }
 
-bool wgrad_tring_applicable(const zsv_conv_desc* d, const float* x, const float* dy) {
+bool wgrad_tring_shape(const zsv_conv_desc* d) {
     if (ZSV_KNOB(NO_WGRAD_TRING)) return false;
     if (d->kT != 3 || d->kH != 1 || d->kW != 1 || d->sT != 1 || d->sH != 1 || d->sW != 1 || d->pT != 1 || d->pH != 0 || d->pW != 0)
         return false;
@@ -516,25 +425,18 @@ bool wgrad_tring_applicable(const zsv_conv_desc* d, const float* x, const float*
     if (d->Cout < 32) return false;
     const long S = (long)d->Ti * d->Hi * d->Wi;
     if ((long)d->N * d->Cin * S >= (1L << 29) || (long)d->N * d->Cout * S >= (1L << 29)) return false;      // int byte offsets
-    const int C = d->Cin, p9 = (C + 143) / 144 * 144, p8 = (C + 127) / 128 * 128, pc = p9 <= p8 ? p9 : p8;
-    if (pc * 10 > C * 13) return false;                                 // row padding above 30 %
+    if (pad_144_or_128(d->Cin) * 10 > d->Cin * 13) return false;        // row padding above 30 %
     const int pm = (d->Cout + 63) / 64 * 64;
     if (pm * 10 > d->Cout * 13) return false;
     if ((long)d->N * S < 16384) return false;
-    if (x != nullptr && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) != 0) return false;
     return true;
 }
 
 // the Winograd form (conv_wgrad_twino_kernel): chunks are frame pairs, two workgroups per CU
 static bool wgrad_twino_shape(const zsv_conv_desc* d) { return d->Ti >= 8 && ZSV_KNOB(NO_WGRAD_TWINO) == nullptr; }
 static WgradTringPlan wgrad_twino_plan(const zsv_conv_desc* d) {
-    WgradTringPlan pl;
-    const int C = d->Cin;
-    const int p9 = (C + 143) / 144 * 144, p8 = (C + 127) / 128 * 128;
-    pl.tm = p9 <= p8 ? 9 : 8;
-    const int bm = 16 * pl.tm;
-    pl.tiles_m = (C + bm - 1) / bm;
-    pl.tiles_n = (d->Cout + 63) / 64;
+    WgradTringPlan pl = wgrad_tring_tiles(d);
+    const int C = d->Cin, bm = 16 * pl.tm;
     const long chunks = (long)d->N * (d->Ti / 2) * (d->Hi * d->Wi / 16);
     const long tiles = (long)pl.tiles_m * pl.tiles_n;
     long resident = 512;
@@ -542,18 +444,10 @@ static WgradTringPlan wgrad_twino_plan(const zsv_conv_desc* d) {
     // slices: MFMA time / fill of the rounds of resident workgroups + slab write / read, >= 16 chunks per slice
     const double t_mfma = 2.0 * (double)(pl.tiles_m * bm) * (double)(pl.tiles_n * 256) * (double)chunks * 16.0 / 1.1e14;
     const double t_slice = 2.0 * (double)C * 4.0 * d->Cout * sizeof(float) / 6.0e12;
-    long max_sl = chunks / 16;
-    if (max_sl < 1) max_sl = 1;
-    if (max_sl > 4096) max_sl = 4096;
-    long sl = 1;
-    double best = 1e300;
-    for (long c = 1; c <= max_sl; ++c) {
-        const long wgs = tiles * c, rounds = (wgs + resident - 1) / resident;
-        const double cost = t_mfma * (double)(rounds * resident) / (double)wgs + t_slice * (double)c;
-        if (cost < best * 0.999) { best = cost; sl = c; }
-    }
+    long sl = slices_by_cost(tiles, resident, t_mfma, t_slice, clamp1(chunks / 16, 4096));
     if (const char* e = ZSV_KNOB(WGRAD_TRING_SLICES)) sl = atol(e) > 0 ? atol(e) : 1;
-    // the slices take whole (clip, segment) jobs, job j to slice j % slices (see the kernel): no slice without a job
+    // the slices take whole (clip, segment) jobs, job j to slice j % slices (see the kernel): no slice without a job, and the
+    // count is taken as it is (no rounding to equal shares)
     const long jobs = (long)d->N * (d->Hi * d->Wi / 16);
     if (sl > jobs) sl = jobs;
     pl.slices = (int)sl;
@@ -596,11 +490,6 @@ static int wgrad_tring_launch(const WgradTringParams& p, int slices, hipStream_t
     return launch_status();
 }
 
-int wgrad_tring(const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes,
-                hipStream_t stream) {
-    return wgrad_tring_pre(d, x, nullptr, 0, dy, dw, workspace, workspace_bytes, stream);
-}
-
 // pre_coef != nullptr: x is the INPUT of a BatchNorm + ReLU whose output is the convolution's input (see the kernel's PRE)
 int wgrad_tring_pre(const zsv_conv_desc* d, const float* x, const float* pre_coef, int pre_pitch, const float* dy, float* dw,
                     void* workspace, size_t workspace_bytes, hipStream_t stream) {
@@ -625,24 +514,14 @@ int wgrad_tring_pre(const zsv_conv_desc* d, const float* x, const float* pre_coe
         else st = pl.tm == 9 ? wgrad_twino_launch<9, false>(p, pl.slices, stream, x, dy, slabs)
                              : wgrad_twino_launch<8, false>(p, pl.slices, stream, x, dy, slabs);
         if (st) return st;
-        const long n = (long)d->Cin * d->Cout;
-        long blocks = (n + 31) / 32;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(wgrad_twino_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)slabs, dw, d->Cout,
-                           d->Cin, pl.slices);
-        return launch_status();
+        return wgrad_tring_sum(slabs, dw, d->Cout, d->Cin, pl.slices, true, stream);
     }
     if (pre_coef) st = pl.tm == 9 ? wgrad_tring_launch<9, true>(p, pl.slices, stream, x, dy, slabs)
                                   : wgrad_tring_launch<8, true>(p, pl.slices, stream, x, dy, slabs);
     else st = pl.tm == 9 ? wgrad_tring_launch<9, false>(p, pl.slices, stream, x, dy, slabs)
                          : wgrad_tring_launch<8, false>(p, pl.slices, stream, x, dy, slabs);
     if (st) return st;
-    const long n = (long)d->Cin * 3 * d->Cout;
-    long blocks = (n + 31) / 32;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(wgrad_tring_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)slabs, dw, d->Cout,
-                       d->Cin, pl.slices);
-    return launch_status();
+    return wgrad_tring_sum(slabs, dw, d->Cout, d->Cin, pl.slices, false, stream);
 }
 
 }  // namespace zsv

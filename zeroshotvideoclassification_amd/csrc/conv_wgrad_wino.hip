@@ -13,7 +13,7 @@
 // GEMM per point: rows = 16*TM output channels, columns = 64*TN (r, ci) pairs per workgroup (TN 16-column blocks per wave:
 // 1 for the 128 / 144-row tiles, 2 for the 64-row tile of the 64-channel layers),
 // reduction over voxel pairs, cut into slices (one round of workgroups covers the problem); every slice writes its
-// partial [point][co][(r, ci)] slab and wgrad_wino_sum_kernel adds the slabs in a fixed order and applies the output
+// partial [point][co][(r, ci)] slab and the Winograd-form sum (wgrad_sum.hip) adds the slabs in a fixed order and applies the output
 // transform: bitwise reproducible, no float atomics.
 //   * MFMA k order as in conv_wgrad_dma.hip: k = 4*(lane>>4) + step, so a lane needs 4 consecutive PAIRS = 8 voxels
 //     of its row for the 4 steps of a 32-voxel chunk: two ds_read_b128 per fragment (+ the two halo voxels of the X row).
@@ -32,6 +32,7 @@
 #include "zsv_common.h"
 #include "zsv_hip.h"
 #include "knobs.h"
+#include "wgrad_plan.h"
 
 namespace zsv {
 
@@ -432,69 +433,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_wino4_kernel(WgradWinoParams p
 #endif
 }
 
-// dW[co][ci][r][kw] from the slabs [slice][point][co][r * Cpad + ci]: 32 elements x 8 slice groups per block (group g adds
-// slices g, g+8, ... in order, then the groups are added in order -- fixed order, bitwise reproducible), then G^T.
-template <int PTS>
-__global__ __launch_bounds__(256) void wgrad_wino_sum_kernel(const float* __restrict__ slabs, float* __restrict__ dw, int M,
-                                                             int Cin, int R, int Cpad, int slices) {
-    __shared__ float part[8][PTS][32];
-    const size_t plane = (size_t)M * R * Cpad;              // one point of one slice
-    const int e = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    for (size_t j0 = (size_t)blockIdx.x * 32; j0 < plane; j0 += (size_t)gridDim.x * 32) {
-        const size_t j = j0 + e;
-        const int ci = (int)(j % Cpad);
-        const bool live = j < plane && ci < Cin;
-        float s[PTS];
-#pragma unroll
-        for (int p = 0; p < PTS; ++p) s[p] = 0.f;
-        if (live) {
-            int k = grp;
-            for (; k + 8 < slices; k += 16) {                     // two slices' loads in flight, added in the same order
-                float v[2][PTS];
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int p = 0; p < PTS; ++p) v[u][p] = slabs[((size_t)(k + 8 * u) * PTS + p) * plane + j];
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int p = 0; p < PTS; ++p) s[p] += v[u][p];
-            }
-            for (; k < slices; k += 8)
-#pragma unroll
-                for (int p = 0; p < PTS; ++p) s[p] += slabs[((size_t)k * PTS + p) * plane + j];
-        }
-#pragma unroll
-        for (int p = 0; p < PTS; ++p) part[grp][p][e] = s[p];
-        __syncthreads();
-        if (grp == 0 && live) {
-            float Mv[PTS];
-#pragma unroll
-            for (int p = 0; p < PTS; ++p) {
-                float t = part[0][p][e];
-#pragma unroll
-                for (int q = 1; q < 8; ++q) t += part[q][p][e];
-                Mv[p] = t;
-            }
-            const size_t rr = j / Cpad;
-            const int r = (int)(rr % R), co = (int)(rr / R);
-            float* o = dw + (((size_t)co * Cin + ci) * R + r) * 3;
-            if constexpr (PTS == 4) {
-                const float h = 0.5f * (Mv[1] + Mv[2]);
-                o[0] = Mv[0] + h;
-                o[1] = 0.5f * (Mv[1] - Mv[2]);
-                o[2] = h - Mv[3];
-            } else {                                                // G^T of F(4,3)
-                const float s12 = Mv[1] + Mv[2], d12 = Mv[2] - Mv[1], s34 = Mv[3] + Mv[4], d34 = Mv[3] - Mv[4];
-                o[0] = 0.25f * Mv[0] - s12 * (1.f / 6.f) + s34 * (1.f / 24.f);
-                o[1] = d12 * (1.f / 6.f) + d34 * (1.f / 12.f);
-                o[2] = Mv[5] - s12 * (1.f / 6.f) + s34 * (1.f / 6.f);
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // ---- host side -----------------------------------------------------------------------------------
 struct WgradWinoPlan {
     int tm, tn, tiles_m, tiles_n, slices, chunks_per_slice, Cpad, Kp;
@@ -505,8 +443,7 @@ static WgradWinoPlan wgrad_wino_plan(const zsv_conv_desc* d) {
     const int M = d->Cout;
     pl.Cpad = (d->Cin + 15) / 16 * 16;
     pl.Kp = 3 * d->kT * pl.Cpad;
-    const int p9 = (M + 143) / 144 * 144, p8 = (M + 127) / 128 * 128;
-    pl.tm = M <= 64 ? 4 : (p9 <= p8 ? 9 : 8);
+    pl.tm = M <= 64 ? 4 : rows_144_or_128(M) / 16;
     pl.tn = pl.tm == 4 ? 2 : 1;
     const int bm = 16 * pl.tm, bn = 64 * pl.tn;
     pl.tiles_m = (M + bm - 1) / bm;
@@ -518,25 +455,13 @@ static WgradWinoPlan wgrad_wino_plan(const zsv_conv_desc* d) {
     const double voxels = (double)chunks * 32.0;
     const double t_mfma = 4.0 * (double)(pl.tiles_m * bm) * (double)(pl.tiles_n * bn) * voxels / 1.1e14;
     const double t_slice = 2.0 * 4.0 * (double)M * pl.Kp * sizeof(float) / 6.0e12;
-    long max_sl = chunks / 24;
-    if (max_sl < 1) max_sl = 1;
-    if (max_sl > 4096) max_sl = 4096;
-    long sl = 1;
-    double best = 1e300;
-    for (long c = 1; c <= max_sl; ++c) {
-        const long wgs = tiles * c, rounds = (wgs + resident - 1) / resident;
-        const double cost = t_mfma * (double)(rounds * resident) / (double)wgs + t_slice * (double)c;
-        if (cost < best * 0.999) { best = cost; sl = c; }
-    }
+    long sl = slices_by_cost(tiles, resident, t_mfma, t_slice, clamp1(chunks / 24, 4096));
     if (const char* e = ZSV_KNOB(WGRAD_WINO_SLICES)) sl = atol(e);
-    if (sl < 1) sl = 1;
-    if (sl > chunks) sl = chunks;
-    pl.chunks_per_slice = (int)((chunks + sl - 1) / sl);
-    pl.slices = (int)((chunks + pl.chunks_per_slice - 1) / pl.chunks_per_slice);
+    split_chunks(chunks, clamp1(sl, chunks), &pl.chunks_per_slice, &pl.slices);
     return pl;
 }
 
-bool wgrad_wino_applicable(const zsv_conv_desc* d, const float* x, const float* dy) {
+bool wgrad_wino_shape(const zsv_conv_desc* d) {
     if (ZSV_KNOB(NO_WINO) || ZSV_KNOB(NO_WGRAD_WINO)) return false;
     if ((d->kT != 1 && d->kT != 3) || d->kH != 3 || d->kW != 3 || d->sT != 1 || d->sH != 1 || d->sW != 1 || d->pT != d->kT / 2 ||
         d->pH != 1 || d->pW != 1)
@@ -545,33 +470,30 @@ bool wgrad_wino_applicable(const zsv_conv_desc* d, const float* x, const float* 
     const long S = (long)d->Ti * d->Hi * d->Wi;
     if (S % 4 != 0) return false;                                // a 16-byte dY piece never straddles the end of a clip
     if ((long)d->N * d->Cin * S >= (1L << 29) || (long)d->N * d->Cout * S >= (1L << 29)) return false;   // int byte offsets
-    const int M = d->Cout, p9 = (M + 143) / 144 * 144, p8 = (M + 127) / 128 * 128, pm = M <= 64 ? 64 : (p9 <= p8 ? p9 : p8);
+    const int M = d->Cout, pm = M <= 64 ? 64 : pad_144_or_128(M);
     if (pm * 10 > M * 13) return false;                          // row padding above 30 %: the plain kernel's tiles fit better
     if ((long)d->N * S < 16384) return false;                    // too few voxels to give the workgroups useful slices
-    if (x != nullptr && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) != 0) return false;
     return true;
 }
-
-static size_t ww_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // F(4,3) form (conv_wgrad_wino4_kernel): rows in 144- or 128-row tiles, one 8-wave workgroup per CU
 struct WgradWino4Plan {
     int tma, tmb, tiles_m, tiles_n, slices, chunks_per_slice, Cpad, Kp;
 };
 
-static bool wgrad_wino4_applicable(const zsv_conv_desc* d) {
-    if (ZSV_KNOB(NO_WGRAD_WINO4)) return false;
+// (the shape alone: the workspace query must hold whether or not the knob is set at call time)
+static bool wgrad_wino4_shape(const zsv_conv_desc* d) {
     const long S = (long)d->Ti * d->Hi * d->Wi;
     return d->Wi % 4 == 0 && S % 32 == 0 && d->Cout > 64;
 }
+static bool wgrad_wino4_applicable(const zsv_conv_desc* d) { return !ZSV_KNOB(NO_WGRAD_WINO4) && wgrad_wino4_shape(d); }
 
 static WgradWino4Plan wgrad_wino4_plan(const zsv_conv_desc* d) {
     WgradWino4Plan pl;
     const int M = d->Cout;
     pl.Cpad = (d->Cin + 15) / 16 * 16;
     pl.Kp = 3 * d->kT * pl.Cpad;
-    const int p9 = (M + 143) / 144 * 144, p8 = (M + 127) / 128 * 128;
-    pl.tma = p9 <= p8 ? 5 : 4;
+    pl.tma = rows_144_or_128(M) == 144 ? 5 : 4;
     pl.tmb = 4;
     const int bm = 16 * (pl.tma + pl.tmb);
     pl.tiles_m = (M + bm - 1) / bm;
@@ -581,31 +503,19 @@ static WgradWino4Plan wgrad_wino4_plan(const zsv_conv_desc* d) {
     const double voxels = (double)chunks * 32.0;
     const double t_mfma = 3.0 * (double)(pl.tiles_m * bm) * (double)(pl.tiles_n * 64) * voxels / 1.1e14;
     const double t_slice = 2.0 * 6.0 * (double)M * pl.Kp * sizeof(float) / 6.0e12;
-    long max_sl = chunks / 24;
-    if (max_sl < 1) max_sl = 1;
-    if (max_sl > 4096) max_sl = 4096;
-    long sl = 1;
-    double best = 1e300;
-    for (long c = 1; c <= max_sl; ++c) {
-        const long wgs = tiles * c, rounds = (wgs + resident - 1) / resident;
-        const double cost = t_mfma * (double)(rounds * resident) / (double)wgs + t_slice * (double)c;
-        if (cost < best * 0.999) { best = cost; sl = c; }
-    }
+    long sl = slices_by_cost(tiles, resident, t_mfma, t_slice, clamp1(chunks / 24, 4096));
     if (const char* e = ZSV_KNOB(WGRAD_WINO_SLICES)) sl = atol(e);
-    if (sl < 1) sl = 1;
-    if (sl > chunks) sl = chunks;
-    pl.chunks_per_slice = (int)((chunks + sl - 1) / sl);
-    pl.slices = (int)((chunks + pl.chunks_per_slice - 1) / pl.chunks_per_slice);
+    split_chunks(chunks, clamp1(sl, chunks), &pl.chunks_per_slice, &pl.slices);
     return pl;
 }
 
 size_t wgrad_wino_workspace_bytes(const zsv_conv_desc* d) {
     const WgradWinoPlan pl = wgrad_wino_plan(d);
     const size_t S = (size_t)d->Ti * d->Hi * d->Wi;
-    size_t slabs = ww_align((size_t)pl.slices * 4 * d->Cout * pl.Kp * sizeof(float));
-    if (d->Wi % 4 == 0 && S % 32 == 0 && d->Cout > 64) {           // (the knob may change between the query and the call)
+    size_t slabs = align256((size_t)pl.slices * 4 * d->Cout * pl.Kp * sizeof(float));
+    if (wgrad_wino4_shape(d)) {                                     // (the knob may change between the query and the call)
         const WgradWino4Plan p4 = wgrad_wino4_plan(d);
-        const size_t s4 = ww_align((size_t)p4.slices * 6 * d->Cout * p4.Kp * sizeof(float));
+        const size_t s4 = align256((size_t)p4.slices * 6 * d->Cout * p4.Kp * sizeof(float));
         if (s4 > slabs) slabs = s4;
     }
     return slabs + S * sizeof(unsigned);
@@ -680,16 +590,7 @@ int wgrad_wino(const zsv_conv_desc* d, const float* x, const float* dy, float* d
         st = edge ? wgrad_wino_launch<4, 2, true>(p, pl.slices, stream, x, dy, vm, slabs)
                   : wgrad_wino_launch<4, 2, false>(p, pl.slices, stream, x, dy, vm, slabs);
     if (st) return st;
-    const long n = (long)d->Cout * p.R * pl.Cpad;
-    long blocks = (n + 31) / 32;
-    if (blocks > 8192) blocks = 8192;
-    if (points == 6)
-        hipLaunchKernelGGL(wgrad_wino_sum_kernel<6>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)slabs, dw, d->Cout,
-                           d->Cin, p.R, pl.Cpad, pl.slices);
-    else
-        hipLaunchKernelGGL(wgrad_wino_sum_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)slabs, dw, d->Cout,
-                           d->Cin, p.R, pl.Cpad, pl.slices);
-    return launch_status();
+    return wgrad_wino_sum(slabs, dw, d->Cout, d->Cin, p.R, pl.Cpad, pl.slices, points, stream);
 }
 
 }  // namespace zsv

@@ -28,6 +28,7 @@
 #include "zsv_common.h"
 #include "zsv_hip.h"
 #include "knobs.h"
+#include "wgrad_plan.h"
 #include "pack_bodies.h"
 
 namespace zsv {
@@ -1338,7 +1339,6 @@ __global__ __launch_bounds__(256, 2) void conv_winot4_kernel(WinoParams prm, con
 }
 
 // ---- host side -----------------------------------------------------------------------------------
-static size_t wino_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // rows per workgroup for M produced channels: 64, or 48 when that pads less (144 = 3 x 48, 288 = 6 x 48)
 static int wino_tm(int M) {
@@ -1462,9 +1462,9 @@ static int wino_tm_for(const zsv_conv_desc* d, int M) {
 }
 static size_t wino_bytes(const zsv_conv_desc* d, int M, int C) {
     const int bm = 16 * wino_tm_for(d, M), Mp = (M + bm - 1) / bm * bm, nblk = (C + 15) / 16;
-    if (winot_shape(d)) return wino_align((size_t)nblk * 6 * 16 * Mp * sizeof(float));            // (no row taps; 6 points: the F(4,3) form, the F(2,3) form uses 4)
+    if (winot_shape(d)) return align256((size_t)nblk * 6 * 16 * Mp * sizeof(float));            // (no row taps; 6 points: the F(4,3) form, the F(2,3) form uses 4)
     const int points = wino_f43(d) ? 6 : 4;
-    return wino_align((size_t)nblk * 3 * d->kT * points * 16 * Mp * sizeof(float));
+    return align256((size_t)nblk * 3 * d->kT * points * 16 * Mp * sizeof(float));
 }
 // transformed weights + (split-K) the parts' slabs
 static size_t wino_total_bytes(const zsv_conv_desc* d, int M, int C) {
