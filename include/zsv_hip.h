@@ -147,6 +147,29 @@ int zsv_conv3d_wgrad_mask(const zsv_conv_desc* d, void* mask, void* stream);
 int zsv_conv3d_wgrad_masked(const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace,
                             size_t workspace_bytes, const void* mask, void* stream);
 
+/* ---- depthwise convolution (groups == channels) ------------------------------------------------------ */
+/* nn.Conv3d(C, C, k, groups=C): the 3x3x3 middle convolution of the channel-separated residual unit
+ * (1x1x1 -> 3x3x3 depthwise -> 1x1x1 in resnet.Bottleneck's frame, resnet.py:116-162), and the 1x3x3 / 3x1x1 depthwise pairs.
+ * The descriptor is zsv_conv_desc read as depthwise: Cin == Cout == C, x (N,C,Ti,Hi,Wi), w (C,1,kT,kH,kW), y (N,C,To,Ho,Wo),
+ * contiguous fp32.  Supported: every kernel extent 1 or 3, every stride 1 or 2, every padding < its kernel extent
+ * (zsv_dwconv3d_supported(d) == 1 exactly when the launching entry points take d).  Decided on the host before any launch:
+ * ZSV_E_NULL (a missing pointer; bias may be NULL), ZSV_E_BAD_SHAPE (Cin != Cout, extents that do not follow from the formula),
+ * ZSV_E_UNSUPPORTED (a consistent descriptor outside the set above), ZSV_E_TOO_LARGE (x or y of 2^31 elements or more),
+ * ZSV_E_WORKSPACE.  Every operand needs 4-byte alignment only and the same inputs give the same bits at any alignment (the
+ * kernels take 4-byte accesses); the workspace is 16-byte aligned.  No atomics.
+ *   zsv_dwconv3d_fwd    y = relu?(conv(x, w) + bias[c]) in one launch: a ring of kT input frames' rows in LDS per workgroup.
+ *   zsv_dwconv3d_dgrad  one launch that writes EVERY element of dx (voxels no output touches: 0.0).  Stride 1: the forward
+ *                       kernel with flipped taps and padding k-1-p; otherwise the gather form over the taps with
+ *                       (i + p - k) % s == 0.
+ *   zsv_dwconv3d_wgrad  dw (C,1,kT,kH,kW): per (channel, slice of the clips x tiles) the taps' partial sums in registers,
+ *                       reduced in a fixed order into a [slice][C * taps] slab row; the slabs are added in slice order. */
+int32_t zsv_dwconv3d_supported(const zsv_conv_desc* d);
+int zsv_dwconv3d_fwd(const zsv_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int fuse_relu, void* stream);
+int zsv_dwconv3d_dgrad(const zsv_conv_desc* d, const float* dy, const float* w, float* dx, void* stream);
+size_t zsv_dwconv3d_wgrad_workspace_bytes(const zsv_conv_desc* d);
+int zsv_dwconv3d_wgrad(const zsv_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* ---- convolution fed by a BatchNorm + ReLU that is never written out ------------------------------ */
 /* Conv2Plus1D runs `Conv3d(1x3x3) -> BatchNorm3d -> ReLU -> Conv3d(3x1x1)` (resnet.py:40-52).  Instead of one HBM pass
  * that normalises the 636 MB mid tensor and a second that reads it back, the temporal convolution (forward and weight

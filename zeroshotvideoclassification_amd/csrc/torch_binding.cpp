@@ -5,7 +5,7 @@
 // descriptor from the tensor sizes, takes the stream torch is currently recording on, allocates the workspace from torch's caching
 // allocator and calls the same `zsv_*` entry point the ctypes glue (`_lib.py` / `ops.py`) calls -- after checking every operand
 // (`want`, `describe`, `fit`) and under a device guard on the operands' device.  The differentiable forms
-// (`zsv::conv3d`, `zsv::batch_norm_relu`, `zsv::batch_norm_relu_eval`, `zsv::relu`, `zsv::linear`) register an Autograd kernel,
+// (`zsv::conv3d`, `zsv::depthwise_conv3d`, `zsv::batch_norm_relu`, `zsv::batch_norm_relu_eval`, `zsv::relu`, `zsv::linear`) register an Autograd kernel,
 // so C++ / TorchScript callers get the reference's
 // `nn.Conv3d` (resnet.py:23-30,40-52; network.py:102-117) and `nn.BatchNorm3d (+ ReLU)` (resnet.py:46-49,94-98) semantics
 // without Python.  The training harness of this repo keeps the ctypes path (panel cache, side-stream weight gradients, fused
@@ -149,6 +149,67 @@ at::Tensor conv3d_wgrad(const at::Tensor& x, const at::Tensor& dy, at::IntArrayR
     at::Tensor ws = scratch(bytes, x);
     ok(zsv_conv3d_wgrad(&d, x.data_ptr<float>(), dy.data_ptr<float>(), dw.data_ptr<float>(), ws.data_ptr(), bytes, stream_of(x)),
        "zsv_conv3d_wgrad");
+    return dw;
+}
+
+// ---- depthwise convolution (groups == channels): w is (C, 1, kT, kH, kW) ------------------------------------------------------
+// the dense descriptor of a (C, C, kT, kH, kW) weight, which the zsv_dwconv3d_* entry points read as depthwise
+zsv_conv_desc describe_depthwise(at::IntArrayRef x, const char* xname, at::IntArrayRef w, const char* wname, at::IntArrayRef stride,
+                                 at::IntArrayRef padding) {
+    TORCH_CHECK(x.size() == 5 && w.size() == 5, "depthwise_conv3d: ", xname, " and ", wname, " are 5-d");
+    TORCH_CHECK(w[0] == x[1] && w[1] == 1, "depthwise_conv3d: ", wname, " is (C, 1, kT, kH, kW) with C = ", x[1], " channels of ", xname,
+                ", got ", w);
+    const int64_t dense[5] = {w[0], w[0], w[2], w[3], w[4]};
+    const zsv_conv_desc d = describe(x, xname, dense, wname, stride, padding);
+    TORCH_CHECK(zsv_dwconv3d_supported(&d) == 1, "depthwise_conv3d: kernel extents 1 or 3, strides 1 or 2, padding < kernel and tensors "
+                "below 2^31 elements are supported");
+    return d;
+}
+
+at::Tensor depthwise_conv3d_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, at::IntArrayRef stride,
+                                at::IntArrayRef padding, bool relu) {
+    const c10::Device dev = x.device();
+    want(x, "x", dev, ANY5);
+    want(w, "w", dev, ANY5);
+    const zsv_conv_desc d = describe_depthwise(x.sizes(), "x", w.sizes(), "w", stride, padding);
+    const float* b = nullptr;
+    if (bias.has_value() && bias->defined()) {
+        want(*bias, "bias", dev, {d.Cout});
+        b = bias->data_ptr<float>();
+    }
+    const c10::DeviceGuard guard(dev);
+    at::Tensor y = at::empty({d.N, d.Cout, d.To, d.Ho, d.Wo}, x.options());
+    ok(zsv_dwconv3d_fwd(&d, x.data_ptr<float>(), w.data_ptr<float>(), b, y.data_ptr<float>(), relu ? 1 : 0, stream_of(x)),
+       "zsv_dwconv3d_fwd");
+    return y;
+}
+
+at::Tensor depthwise_conv3d_dgrad(const at::Tensor& dy, const at::Tensor& w, at::IntArrayRef x_sizes, at::IntArrayRef stride,
+                                  at::IntArrayRef padding) {
+    const c10::Device dev = dy.device();
+    want(dy, "dy", dev, ANY5);
+    want(w, "w", dev, ANY5);
+    const zsv_conv_desc d = describe_depthwise(x_sizes, "x_sizes", w.sizes(), "w", stride, padding);
+    want(dy, "dy", dev, {d.N, d.Cout, d.To, d.Ho, d.Wo});
+    const c10::DeviceGuard guard(dev);
+    at::Tensor dx = at::empty(x_sizes, dy.options());
+    ok(zsv_dwconv3d_dgrad(&d, dy.data_ptr<float>(), w.data_ptr<float>(), dx.data_ptr<float>(), stream_of(dy)), "zsv_dwconv3d_dgrad");
+    return dx;
+}
+
+at::Tensor depthwise_conv3d_wgrad(const at::Tensor& x, const at::Tensor& dy, at::IntArrayRef w_sizes, at::IntArrayRef stride,
+                                  at::IntArrayRef padding) {
+    const c10::Device dev = x.device();
+    want(x, "x", dev, ANY5);
+    want(dy, "dy", dev, ANY5);
+    const zsv_conv_desc d = describe_depthwise(x.sizes(), "x", w_sizes, "w_sizes", stride, padding);
+    want(dy, "dy", dev, {d.N, d.Cout, d.To, d.Ho, d.Wo});
+    const c10::DeviceGuard guard(dev);
+    at::Tensor dw = at::empty(w_sizes, x.options());
+    const size_t bytes = zsv_dwconv3d_wgrad_workspace_bytes(&d);
+    at::Tensor ws = scratch(bytes, x);
+    ok(zsv_dwconv3d_wgrad(&d, x.data_ptr<float>(), dy.data_ptr<float>(), dw.data_ptr<float>(), ws.data_ptr(), bytes, stream_of(x)),
+       "zsv_dwconv3d_wgrad");
     return dw;
 }
 
@@ -355,6 +416,38 @@ at::Tensor conv3d_autograd(const at::Tensor& x, const at::Tensor& w, const c10::
     return Conv3dFn::apply(x, w, bias, stride.vec(), padding.vec());
 }
 
+struct DepthwiseConv3dFn : public torch::autograd::Function<DepthwiseConv3dFn> {
+    static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& x, const at::Tensor& w,
+                              const c10::optional<at::Tensor>& bias, std::vector<int64_t> stride, std::vector<int64_t> padding) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        ctx->save_for_backward({x, w});
+        ctx->saved_data["stride"] = stride;
+        ctx->saved_data["padding"] = padding;
+        ctx->saved_data["has_bias"] = bias.has_value() && bias->defined();
+        return depthwise_conv3d_fwd(x, w, bias, stride, padding, false);
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
+        const auto saved = ctx->get_saved_variables();
+        const at::Tensor &x = saved[0], &w = saved[1];
+        const auto stride = ctx->saved_data["stride"].toIntVector(), padding = ctx->saved_data["padding"].toIntVector();
+        const at::Tensor dy = grads[0].contiguous();
+        at::Tensor dx, dw, db;
+        if (ctx->needs_input_grad(0)) dx = depthwise_conv3d_dgrad(dy, w, x.sizes(), stride, padding);
+        if (ctx->needs_input_grad(1)) dw = depthwise_conv3d_wgrad(x, dy, w.sizes(), stride, padding);
+        if (ctx->saved_data["has_bias"].toBool() && ctx->needs_input_grad(2)) db = dy.sum({0, 2, 3, 4});
+        return {dx, dw, db, at::Tensor(), at::Tensor()};
+    }
+};
+
+at::Tensor depthwise_conv3d_autograd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
+                                     at::IntArrayRef stride, at::IntArrayRef padding) {
+    return DepthwiseConv3dFn::apply(x, w, bias, stride.vec(), padding.vec());
+}
+at::Tensor depthwise_conv3d_plain(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, at::IntArrayRef stride,
+                                  at::IntArrayRef padding) {
+    return depthwise_conv3d_fwd(x, w, bias, stride, padding, false);
+}
+
 struct BatchNormReluFn : public torch::autograd::Function<BatchNormReluFn> {
     static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& x, const at::Tensor& gamma, const at::Tensor& beta,
                               at::Tensor running_mean, at::Tensor running_var, double momentum, double eps, bool relu) {
@@ -456,6 +549,10 @@ TORCH_LIBRARY(zsv, m) {
     m.def("conv3d_fwd(Tensor x, Tensor w, Tensor? bias, int[3] stride, int[3] padding, bool relu=False) -> Tensor");
     m.def("conv3d_dgrad(Tensor dy, Tensor w, int[] x_sizes, int[3] stride, int[3] padding) -> Tensor");
     m.def("conv3d_wgrad(Tensor x, Tensor dy, int[] w_sizes, int[3] stride, int[3] padding) -> Tensor");
+    m.def("depthwise_conv3d_fwd(Tensor x, Tensor w, Tensor? bias, int[3] stride, int[3] padding, bool relu=False) -> Tensor");
+    m.def("depthwise_conv3d_dgrad(Tensor dy, Tensor w, int[] x_sizes, int[3] stride, int[3] padding) -> Tensor");
+    m.def("depthwise_conv3d_wgrad(Tensor x, Tensor dy, int[] w_sizes, int[3] stride, int[3] padding) -> Tensor");
+    m.def("depthwise_conv3d(Tensor x, Tensor w, Tensor? bias, int[3] stride, int[3] padding) -> Tensor");
     m.def("bn_train_fwd(Tensor x, Tensor weight, Tensor bias, Tensor(a!) running_mean, Tensor(b!) running_var, float momentum, "
           "float eps, bool relu=False) -> (Tensor, Tensor, Tensor)");
     m.def("bn_train_bwd(Tensor dy, Tensor x, Tensor y, Tensor weight, Tensor bias, Tensor save_mean, Tensor save_invstd, "
@@ -482,6 +579,10 @@ TORCH_LIBRARY_IMPL(zsv, CUDA, m) {      // torch's name of the HIP backend on RO
     m.impl("conv3d_fwd", conv3d_fwd);
     m.impl("conv3d_dgrad", conv3d_dgrad);
     m.impl("conv3d_wgrad", conv3d_wgrad);
+    m.impl("depthwise_conv3d_fwd", depthwise_conv3d_fwd);
+    m.impl("depthwise_conv3d_dgrad", depthwise_conv3d_dgrad);
+    m.impl("depthwise_conv3d_wgrad", depthwise_conv3d_wgrad);
+    m.impl("depthwise_conv3d", depthwise_conv3d_plain);
     m.impl("bn_train_fwd", bn_train_fwd);
     m.impl("bn_train_bwd", bn_train_bwd);
     m.impl("conv3d", conv3d_plain);
@@ -500,6 +601,7 @@ TORCH_LIBRARY_IMPL(zsv, CUDA, m) {      // torch's name of the HIP backend on RO
 
 TORCH_LIBRARY_IMPL(zsv, Autograd, m) {
     m.impl("conv3d", conv3d_autograd);
+    m.impl("depthwise_conv3d", depthwise_conv3d_autograd);
     m.impl("batch_norm_relu", batch_norm_relu_autograd);
     m.impl("batch_norm_relu_eval", batch_norm_relu_eval_autograd);
     m.impl("relu", relu_autograd);

@@ -14,21 +14,26 @@ from . import ops
 
 
 class Conv3d(nn.Conv3d):
-    """nn.Conv3d with dilation 1, groups 1, zero padding (all the reference uses)."""
+    """nn.Conv3d with dilation 1, zero padding and groups 1 (all the reference uses) or groups == in_channels == out_channels
+    (depthwise: the middle convolution of the channel-separated residual unit)."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
-        if self.dilation != (1, 1, 1) or self.groups != 1 or self.padding_mode != "zeros" \
+        depthwise = self.groups == self.in_channels == self.out_channels
+        if self.dilation != (1, 1, 1) or not (self.groups == 1 or depthwise) or self.padding_mode != "zeros" \
                 or isinstance(self.padding, str):
-            raise NotImplementedError("only dilation=1, groups=1, zero padding are on the hot path")
+            raise NotImplementedError("only dilation=1, groups=1 or depthwise (groups == in_channels == out_channels), zero padding "
+                                      "are on the hot path")
 
     def forward(self, x, relu: bool = False, want_stats: bool = False):
         """``want_stats=True`` returns ``(y, stats)``: BatchNorm partial statistics of ``y`` gathered in
-        the kernel epilogue (None when the geometry does not provide them)."""
-        return ops.conv3d(x, self.weight, self.bias, self.stride, self.padding, relu=relu, want_stats=want_stats)
+        the kernel epilogue (None when the geometry does not provide them; always None for a depthwise layer)."""
+        return ops.conv3d(x, self.weight, self.bias, self.stride, self.padding, relu=relu, want_stats=want_stats, groups=self.groups)
 
     def pre_supported(self, x_shape) -> bool:
         """Can this convolution take a training-mode ``BatchNorm3d -> ReLU`` in front of it inside its own kernels?"""
+        if self.groups != 1:
+            return False
         return self.bias is None and ops.conv_pre_supported(x_shape, self.weight.shape, self.stride, self.padding)
 
     def forward_pre(self, x, coef, want_stats: bool = False):

@@ -32,6 +32,8 @@ def get_network(opt):
         factory = models.r3d_18
     elif "2plus1d" in name:
         factory = models.r2plus1d_18
+    elif "csn" in name:
+        factory = models.ir_csn_50
     elif "c3d" in name:
         return C3D(fixconvs=opt.fixconvs, nopretrained=opt.nopretrained)
     else:
@@ -63,7 +65,7 @@ class MLP(nn.Module):
 
 
 class Model(nn.Module):
-    """Video trunk -> mean over (T,H,W) -> MLP(512,512,300,2) -> L2 normalise.
+    """Video trunk -> mean over (T,H,W) -> MLP(trunk width,512,300,2) -> L2 normalise (the width is 512 in the reference).
     Returns ``(embeddings, None)`` like the fork (network.py:600)."""
 
     def __init__(self, network, fixconvs=False, nopretrained=False):
@@ -82,7 +84,7 @@ class Model(nn.Module):
             nn.TransformerEncoderLayer(d_model=self.d_model, dim_feedforward=self.d_model * 4, nhead=8, dropout=0.1,
                                        activation="gelu"),
             num_layers=6, enable_nested_tensor=False)
-        self.output2emb_proj = MLP(512, 512, 300, 2)
+        self.output2emb_proj = MLP(self.model.fc.in_features, 512, 300, 2)      # 512 for the *_18 trunks, 2048 for Bottleneck trunks
         self.reset_parameters()
 
     def reset_parameters(self):

@@ -644,14 +644,101 @@ class _Conv3d(Function):
         return dx, dw, db, None, None, None, None, None, None, None
 
 
-def conv3d(x, weight, bias=None, stride=1, padding=0, relu=False, want_stats=False):
+class _DepthwiseConv3d(Function):
+    """aten::conv3d with groups == channels, fwd / dgrad / wgrad (zsv_dwconv3d_*): the 3x3x3 of the channel-separated residual
+    unit; optional bias and fused ReLU as ``_Conv3d``.  No BatchNorm-statistics epilogue, no shortcut links."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding, relu):
+        _require(x, weight, bias)
+        if x.dim() != 5 or weight.dim() != 5:
+            raise RuntimeError("conv3d expects (N,C,T,H,W) input and (C,1,kT,kH,kW) depthwise weight")
+        x = x.contiguous()
+        weight = weight.contiguous()
+        c = int(x.shape[1])
+        if int(weight.shape[0]) != c or int(weight.shape[1]) != 1:
+            raise RuntimeError(f"depthwise conv3d: input has {c} channels, weight is {tuple(weight.shape)}")
+        d = conv_desc(x.shape, (c, c) + tuple(weight.shape[2:]), stride, padding)
+        lib = _lib.load()
+        if not lib.zsv_dwconv3d_supported(byref(d)):
+            raise NotImplementedError(f"depthwise conv3d: kernel {(d.kT, d.kH, d.kW)} stride {(d.sT, d.sH, d.sW)} padding "
+                                      f"{(d.pT, d.pH, d.pW)} is not on the hot path (kernel 1 or 3, stride 1 or 2, padding < kernel)")
+        y = torch.empty((d.N, c, d.To, d.Ho, d.Wo), dtype=torch.float32, device=x.device)
+        timer = KERNEL_TIMER
+        with torch.cuda.device(x.device):
+            ev = timer.start() if (timer is not None and timer.wants("dwconv_fwd", d)) else None
+            _lib.check(lib.zsv_dwconv3d_fwd(byref(d), x.data_ptr(), weight.data_ptr(), _ptr(bias), y.data_ptr(), 1 if relu else 0,
+                                            _stream()), "zsv_dwconv3d_fwd")
+            if ev is not None:
+                timer.stop(ev)
+        ctx.desc = d
+        ctx.relu = bool(relu)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x, weight, y if relu else None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        d = ctx.desc
+        lib = _lib.load()
+        dy = dy.contiguous()
+        dx = dw = db = None
+        timer = KERNEL_TIMER
+        with torch.cuda.device(dy.device):
+            if ctx.relu:
+                g = torch.empty_like(dy)
+                if ctx.has_bias and ctx.needs_input_grad[2]:
+                    n_, c_ = int(dy.shape[0]), int(dy.shape[1])
+                    s_ = dy.numel() // (n_ * c_)
+                    db = torch.empty(c_, dtype=torch.float32, device=dy.device)
+                    nb = lib.zsv_channel_sum_workspace_bytes(n_, c_, s_)
+                    wsb = _workspace(nb, dy.device)
+                    _lib.check(lib.zsv_relu_bwd_bias(dy.data_ptr(), y.data_ptr(), g.data_ptr(), n_, c_, s_, db.data_ptr(),
+                                                     _ptr(wsb), nb, _stream()), "zsv_relu_bwd_bias")
+                else:
+                    _lib.check(lib.zsv_relu_bwd(dy.data_ptr(), y.data_ptr(), g.data_ptr(), g.numel(), _stream()), "zsv_relu_bwd")
+                dy = g
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty_like(x)
+                ev = timer.start() if (timer is not None and timer.wants("dwconv_dgrad", d)) else None
+                _lib.check(lib.zsv_dwconv3d_dgrad(byref(d), dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), _stream()),
+                           "zsv_dwconv3d_dgrad")
+                if ev is not None:
+                    timer.stop(ev)
+            if ctx.needs_input_grad[1]:
+                nbytes = lib.zsv_dwconv3d_wgrad_workspace_bytes(byref(d))
+
+                def launch(stream):
+                    out = torch.empty_like(weight)
+                    ws = _workspace(nbytes, dy.device)
+                    _lib.check(lib.zsv_dwconv3d_wgrad(byref(d), x.data_ptr(), dy.data_ptr(), out.data_ptr(), _ptr(ws), nbytes, stream),
+                               "zsv_dwconv3d_wgrad")
+                    return out
+
+                dw = _on_wgrad_stream(launch, (x, dy), weight)
+            if ctx.has_bias and ctx.needs_input_grad[2] and db is None:
+                db = channel_sum(dy)
+        return dx, dw, db, None, None, None
+
+
+def conv3d(x, weight, bias=None, stride=1, padding=0, relu=False, want_stats=False, groups=1):
     """``want_stats``: also return the epilogue's BatchNorm partial statistics (or None when this
     geometry does not produce them) as ``(y, stats)``.  An input tagged with a ``SkipLink`` (by
     ``BasicBlock.forward``: the tensor is also the block's identity shortcut) makes this convolution's
-    backward add the shortcut gradient in its dgrad epilogue."""
+    backward add the shortcut gradient in its dgrad epilogue.  ``groups``: 1, or the channel count of a depthwise
+    convolution (weight (C,1,kT,kH,kW)): no statistics (None) and the link tags on the input are dropped unarmed, so the
+    block tail returns the shortcut gradient the ordinary way."""
     link = x.__dict__.pop("_zsv_skip_link", None) if hasattr(x, "__dict__") else None
     down = x.__dict__.pop("_zsv_down_link", None) if hasattr(x, "__dict__") else None        # (``DownLink``: consumer / producer tags)
     src = x.__dict__.pop("_zsv_down_src", None) if hasattr(x, "__dict__") else None
+    if groups != 1:
+        if x.dim() != 5 or weight.dim() != 5 or not (groups == x.shape[1] == weight.shape[0]) or weight.shape[1] != 1:
+            raise NotImplementedError(f"conv3d: groups={groups} with input {tuple(x.shape)} and weight {tuple(weight.shape)}: only "
+                                      "groups == 1 and depthwise (groups == in_channels == out_channels) are on the hot path")
+        y = _DepthwiseConv3d.apply(x, weight, bias, _triple(stride), _triple(padding), bool(relu))
+        return (y, None) if want_stats else y
     if not (torch.is_grad_enabled() and x.requires_grad):
         link = down = src = None
     # "recording" = a graph is really being built through this call (ADVICE r3): a forward under grad mode whose operands need no

@@ -27,7 +27,7 @@ import os
 from . import ops
 from .layers import AdaptiveAvgPool3d, BatchNorm3d, Conv3d, Linear, ReLU
 
-__all__ = ["r3d_18", "mc3_18", "r2plus1d_18"]
+__all__ = ["r3d_18", "mc3_18", "r2plus1d_18"]          # the reference's list; `ir_csn_50` is this package's own factory
 
 
 def _has_hooks(*mods: nn.Module) -> bool:
@@ -102,6 +102,21 @@ class Conv3DSimple(Conv3d):
     def __init__(self, in_planes: int, out_planes: int, midplanes: Optional[int] = None, stride: int = 1,
                  padding: int = 1) -> None:
         super().__init__(in_planes, out_planes, kernel_size=(3, 3, 3), stride=stride, padding=padding, bias=False)
+
+    @staticmethod
+    def get_downsample_stride(stride: int) -> Tuple[int, int, int]:
+        return stride, stride, stride
+
+
+class Conv3DDepthwise(Conv3d):
+    """3x3x3 depthwise convolution (groups == channels), stride s in every axis: the middle convolution of the
+    channel-separated residual unit (``Bottleneck``: 1x1x1 -> 3x3x3 depthwise -> 1x1x1)."""
+
+    def __init__(self, in_planes: int, out_planes: int, midplanes: Optional[int] = None, stride: int = 1,
+                 padding: int = 1) -> None:
+        assert in_planes == out_planes, "a depthwise convolution keeps the channel count"
+        super().__init__(in_planes, out_planes, kernel_size=(3, 3, 3), stride=stride, padding=padding, groups=in_planes,
+                         bias=False)
 
     @staticmethod
     def get_downsample_stride(stride: int) -> Tuple[int, int, int]:
@@ -196,7 +211,8 @@ class BasicBlock(nn.Module):
 
 
 class Bottleneck(nn.Module):
-    """Present for surface completeness (resnet.py:116-162); no factory in the reference uses it."""
+    """The bottleneck unit (resnet.py:116-162); no factory in the reference uses it.  With ``Conv3DDepthwise`` as its builder it
+    is the channel-separated residual unit of ``ir_csn_50``."""
     expansion = 4
 
     def __init__(self, inplanes: int, planes: int, conv_builder: Callable[..., nn.Module], stride: int = 1,
@@ -322,3 +338,13 @@ def r2plus1d_18(pretrained: bool = False, progress: bool = True, **kwargs: Any) 
     """R(2+1)D-18: every 3-D convolution factorised into 1x3x3 + 3x1x1 (resnet.py:342-362)."""
     return _video_resnet("r2plus1d_18", pretrained, progress, block=BasicBlock, conv_makers=[Conv2Plus1D] * 4,
                          layers=[2, 2, 2, 2], stem=R2Plus1dStem, **kwargs)
+
+
+
+def ir_csn_50(pretrained: bool = False, progress: bool = True, **kwargs: Any) -> VideoResNet:
+    """The channel-separated residual unit (1x1x1 -> 3x3x3 depthwise -> 1x1x1, interaction-reduced) at depth 50, in THIS
+    ``VideoResNet`` frame: ``BasicStem`` and no stem max-pool.  The published CSN models have an overlapping max-pool after the
+    stem and their own key names: this model is NOT key-compatible with published CSN checkpoints.  fp32 only: the bf16 / e4m3
+    engines and ``amp`` refuse Bottleneck trunks."""
+    return _video_resnet("ir_csn_50", pretrained, progress, block=Bottleneck, conv_makers=[Conv3DDepthwise] * 4,
+                         layers=[3, 4, 6, 3], stem=BasicStem, **kwargs)

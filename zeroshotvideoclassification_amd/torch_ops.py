@@ -21,6 +21,8 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libzsv_torc
 OPERATORS = ("version", "conv3d_fwd", "conv3d_dgrad", "conv3d_wgrad", "bn_train_fwd", "bn_train_bwd", "relu_fwd", "relu_bwd",
              "linear_fwd", "linear_dgrad", "linear_wgrad", "conv3d", "batch_norm_relu", "relu", "linear", "bn_eval_fwd",
              "bn_eval_bwd", "batch_norm_relu_eval")
+# the depthwise (groups == channels) family: three plain operators and the differentiable form, the schemas of the dense four
+DEPTHWISE_OPERATORS = ("depthwise_conv3d_fwd", "depthwise_conv3d_dgrad", "depthwise_conv3d_wgrad", "depthwise_conv3d")
 _loaded = False
 
 
