@@ -747,6 +747,64 @@ int zsv_sgd_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t to
                   int32_t first_step, float* const* shadows_device, const zsv_avg_state* avg_state_device, float ema_weight,
                   void* stream);
 
+/* ---- LARS and LAMB: layer-wise trust ratios on the device (csrc/layerwise.hip) -----------------------------------------------
+ * The SGD and Adam rules above with the update of every TENSOR scaled by a ratio of two 2-norms over that tensor.  With
+ * g = g_mem * inv_scale * clip_coef exactly as in zsv_sgd_multi / zsv_adamw_multi_scaled:
+ *   LARS   r = trust_coefficient * |p| / (|g| + weight_decay * |p| + eps)  if adapt and |p| > 0 and |g| > 0, else 1
+ *          d = r * (g + weight_decay * p), then zsv_sgd_multi's momentum rule on d and p = fma(-lr, ., p); with r == 1 the
+ *          element rule is zsv_sgd_multi's, operation for operation
+ *   LAMB   m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2; t = `step`, or steps_done + 1 read on the device
+ *          u = (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps) + weight_decay * p
+ *          r = |p| / |u|  if adapt and |p| > 0 and |u| > 0, else 1;  r = min(r, trust_clip) when trust_clip > 0
+ *          p = fma(-(lr * r), u, p)
+ * A step of one table is three launches: the partials (zsv_lars_norms, or zsv_lamb_moments, which updates m and v in place
+ * and forms u without storing it), zsv_layerwise_finalize (one workgroup per tensor: the partials of its chunks summed in
+ * double in a fixed order, one record written), and the apply (zsv_lars_multi / zsv_lamb_multi, which recomputes u from the
+ * updated m, v and the old p).  No atomics: equal inputs give equal bits, at any alignment -- every array needs 4-byte
+ * alignment only, each on its own, and moves 16 bytes per lane where its base allows.  With a non-NULL scaler state whose
+ * found_inf is set every launch returns before it touches m, v, the momentum buffer, p, the shadows or the records.
+ *
+ * The workspace is ONE buffer for all tables (parameter groups) of a step: `all_count` records, then two floats
+ * {sum p^2, sum q^2} per chunk.  A launch names its table's place in it: `tensor_offset` = tensors of the tables before it,
+ * `chunk_offset` = their chunks.  ZSV_E_NULL (table or workspace NULL), ZSV_E_BAD_SHAPE (count, total_chunks, an offset,
+ * tensor_offset + count > all_count, a hyper-parameter out of range), ZSV_E_WORKSPACE (fewer bytes than the query gives for
+ * chunk_offset + total_chunks chunks and all_count tensors): all before any launch. */
+typedef struct zsv_layer_record {
+    float p_norm;   /* 2-norm of the parameter tensor before the update */
+    float q_norm;   /* LARS: 2-norm of its gradient, unscaled and clipped; LAMB: 2-norm of u */
+    float ratio;    /* the trust ratio the apply launch multiplied the update by (1 where it does not adapt) */
+} zsv_layer_record;
+/* Bytes of the workspace: `count` records rounded up to 16 bytes, then 8 bytes per chunk.  0 for total_chunks or count <= 0. */
+size_t zsv_layerwise_workspace_bytes(int64_t total_chunks, int32_t count);
+int zsv_lars_norms(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, int64_t chunk_offset,
+                   int32_t tensor_offset, int32_t all_count, void* workspace_device, size_t workspace_bytes,
+                   const zsv_scaler_state* state_device, void* stream);
+/* `step` (> 0) is read only when `state_device` is NULL; the exp_avg and exp_avg_sq of the table are written. */
+int zsv_lamb_moments(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, int64_t chunk_offset,
+                     int32_t tensor_offset, int32_t all_count, void* workspace_device, size_t workspace_bytes, float beta1,
+                     float beta2, float eps, double weight_decay, const zsv_clip_record* clip_device,
+                     const zsv_scaler_state* state_device, int32_t grads_unscaled, int32_t step, void* stream);
+/* lamb == 0: the LARS ratio from trust_coefficient (> 0), weight_decay and eps, the gradient norm multiplied by
+ * (float)(1 / (double)scale) (state_device non-NULL and grads_unscaled == 0) and by clip_coef (clip_device non-NULL);
+ * lamb != 0: the LAMB ratio, clamped to trust_clip when that is > 0.  adapt == 0: the norms are recorded, every ratio is 1. */
+int zsv_layerwise_finalize(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks, int64_t chunk_offset,
+                           int32_t tensor_offset, int32_t all_count, void* workspace_device, size_t workspace_bytes,
+                           int32_t lamb, int32_t adapt, double trust_coefficient, double weight_decay, double eps,
+                           double trust_clip, const zsv_clip_record* clip_device, const zsv_scaler_state* state_device,
+                           int32_t grads_unscaled, void* stream);
+/* The apply launches.  `records_device`: the `count` records of THIS table (workspace + tensor_offset records), read only.
+ * Clip record, scaler state, shadows and averaging state are NULL-able exactly as in zsv_sgd_multi; the other arguments of
+ * zsv_lars_multi are zsv_sgd_multi's.  zsv_lamb_multi takes no clip record: the gradient is not read again. */
+int zsv_lars_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks,
+                   const zsv_layer_record* records_device, double lr, float momentum, float dampening, int32_t nesterov,
+                   double weight_decay, int32_t maximize, const zsv_clip_record* clip_device,
+                   const zsv_scaler_state* state_device, int32_t grads_unscaled, int32_t first_step,
+                   float* const* shadows_device, const zsv_avg_state* avg_state_device, float ema_weight, void* stream);
+int zsv_lamb_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks,
+                   const zsv_layer_record* records_device, double lr, float beta1, float beta2, float eps, double weight_decay,
+                   const zsv_scaler_state* state_device, int32_t step, float* const* shadows_device,
+                   const zsv_avg_state* avg_state_device, float ema_weight, void* stream);
+
 /* ---- weight panels packed ahead of the call ---------------------------------------------------------------------------
  * Every forward / dgrad entry point above first re-lays its weights out (a "panel": the direct kernel's [block][tap][16][m]
  * image, the Winograd kernels' transformed weights, the stride-2 dgrad's tap-major image) in a small launch of its own: 76

@@ -145,6 +145,19 @@ SIGNATURES = {
     # shadows, avg state, ema_weight, stream
     "zsv_sgd_multi": (c_int, [_P, c_int32, c_int64, c_double, c_float, c_float, c_int32, c_double, c_int32, _P, _P, c_int32, c_int32,
                               _P, _P, c_float, _P]),
+    # LARS / LAMB (csrc/layerwise.hip).  The three workspace launches: table, count, chunks, chunk_offset, tensor_offset, all_count,
+    # workspace, bytes, then their own arguments; the two apply launches: table, count, chunks, records, then zsv_sgd_multi's
+    # arguments from lr on / lr, betas, eps, weight_decay, scaler state, step, shadows, avg state, ema_weight
+    "zsv_layerwise_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "zsv_lars_norms": (c_int, [_P, c_int32, c_int64, c_int64, c_int32, c_int32, _P, c_size_t, _P, _P]),
+    "zsv_lamb_moments": (c_int, [_P, c_int32, c_int64, c_int64, c_int32, c_int32, _P, c_size_t, c_float, c_float, c_float, c_double,
+                                 _P, _P, c_int32, c_int32, _P]),
+    "zsv_layerwise_finalize": (c_int, [_P, c_int32, c_int64, c_int64, c_int32, c_int32, _P, c_size_t, c_int32, c_int32, c_double,
+                                       c_double, c_double, c_double, _P, _P, c_int32, _P]),
+    "zsv_lars_multi": (c_int, [_P, c_int32, c_int64, _P, c_double, c_float, c_float, c_int32, c_double, c_int32, _P, _P, c_int32,
+                               c_int32, _P, _P, c_float, _P]),
+    "zsv_lamb_multi": (c_int, [_P, c_int32, c_int64, _P, c_double, c_float, c_float, c_float, c_double, _P, c_int32, _P, _P, c_float,
+                               _P]),
     # the four Adam launches with weight averaging: their own arguments up to the stream, then shadows, avg state, ema_weight
     "zsv_adam_multi_avg": (c_int, [_P, c_int32, c_int64, c_float, c_float, c_float, c_float, c_int32, _P, _P, c_float, _P]),
     "zsv_adam_multi_scaled_avg": (c_int, [_P, c_int32, c_int64, c_float, c_float, c_float, c_float, _P, _P, _P, c_float, _P]),

@@ -55,6 +55,12 @@ launches, the host's bookkeeping); a subclass supplies the launch of one group (
 state and shadows are NULL-able arguments of that ONE entry point.  The state is torch's (``momentum_buffer``).  torch's first step
 copies the gradient into the new buffer; here the launch is told -- by the host, or under a scaler by the device-resident count of
 steps taken, so that a skipped first step leaves the next one the first -- whether it is that step.
+
+``FusedLARS`` and ``FusedLAMB`` are ``FusedSGD`` and ``FusedAdam`` with the update of every parameter tensor scaled by a trust ratio of
+two 2-norms over that tensor -- the large-batch forms of the two recipes.  Three launches per parameter group (csrc/layerwise.hip):
+partial sums per chunk (LAMB's also updates the moments), one workgroup per tensor that leaves ``{|p|, |g| or |u|, ratio}`` on the
+device, the update.  No host synchronisation, no atomics; everything the base class gives works with both.  ``layer_norms`` is the
+per-layer norm monitor, ``layerwise_groups(model, weight_decay)`` the usual split into adapting weights and non-adapting affines / biases.
 """
 from __future__ import annotations
 
@@ -101,7 +107,7 @@ class LossScaler:
     def step(self, optimizer) -> None:
         """``scaler.step(optimizer)`` (main.py:200): unscale + non-finite check + (skipped-if-inf) optimizer step."""
         if not isinstance(optimizer, _FusedOptimizer):
-            raise RuntimeError("LossScaler.step drives optim.FusedAdam or optim.FusedSGD "
+            raise RuntimeError("LossScaler.step drives optim.FusedAdam, optim.FusedSGD, optim.FusedLARS or optim.FusedLAMB "
                                "(the check, unscale and skip run inside their kernels)")
         optimizer.step(scaler=self)
 
@@ -112,7 +118,7 @@ class LossScaler:
         ``scaler.unscale_(opt); torch.nn.utils.clip_grad_norm_(...); scaler.step(opt)``; ``FusedAdam(max_grad_norm=)``
         is the fused route, which needs no ``unscale_``."""
         if not isinstance(optimizer, _FusedOptimizer):
-            raise RuntimeError("LossScaler.unscale_ drives optim.FusedAdam or optim.FusedSGD")
+            raise RuntimeError("LossScaler.unscale_ drives optim.FusedAdam, optim.FusedSGD, optim.FusedLARS or optim.FusedLAMB")
         if id(optimizer) in self._unscaled:
             raise RuntimeError("unscale_() has already been called on this optimizer since the last update().")
         optimizer._unscale(self)
@@ -658,6 +664,199 @@ class FusedSGD(_FusedOptimizer):
         return out
 
 
+class _Layerwise:
+    """What ``FusedLARS`` and ``FusedLAMB`` add to the rule they inherit: one workspace for all parameter groups of a step -- a
+    record ``{p_norm, q_norm, ratio}`` per tensor, then two partial sums per 4096-element chunk (``zsv_layerwise_workspace_bytes``)
+    -- each table's place in it, and ``layer_norms`` / ``layer_params``.  Listed before the inherited optimizer in the bases."""
+
+    _layer_keys = ()                                      # the group options a state dict of the inherited optimizer lacks
+
+    def _init_layerwise(self):
+        self._layer_ws = None                             # fp32 view of the workspace (records first)
+        self._layout = ({}, 0, 0)                         # {id(group): (tensor offset, chunk offset)}, tensors, chunks of this step
+        self.layer_params = []                            # the parameters behind the rows of layer_norms, in order
+
+    @property
+    def layer_norms(self) -> torch.Tensor:
+        """``(len(layer_params), 3)`` device tensor of the last step's records: the 2-norm of each parameter before the update, the
+        2-norm of its gradient (LARS: unscaled and clipped) or of its update direction ``u`` (LAMB), and the trust ratio applied.
+        A view of the workspace: reading it does not synchronise, and a step the scaler skips leaves it as it was."""
+        if self._layer_ws is None or not self.layer_params:
+            raise RuntimeError(f"{type(self).__name__}.layer_norms is available after step()")
+        n = len(self.layer_params)
+        return self._layer_ws[:3 * n].view(n, 3)
+
+    def _tables(self):
+        work = super()._tables()
+        offsets, params, tensors, chunks_before = {}, [], 0, 0
+        for group, (table, count, chunks, _keep) in work:
+            offsets[id(group)] = (tensors, chunks_before)
+            if self._static is not None and table is self._static[1]:
+                params += [p for p, _ in self._static[4]]                     # the bucket layout's order
+            else:
+                params += [p for p in group["params"] if p.grad is not None]  # _dynamic_table's order
+            tensors += count
+            chunks_before += chunks
+        assert len(params) == tensors
+        self._layout, self.layer_params = (offsets, tensors, chunks_before), params
+        return work
+
+    def _place(self, lib, group, table, count, chunks):
+        """The leading arguments of the three workspace launches of one table, and the address of its first record."""
+        offsets, tensors, all_chunks = self._layout
+        nbytes = int(lib.zsv_layerwise_workspace_bytes(all_chunks, tensors))
+        ws = self._layer_ws
+        if ws is None or ws.device != table.device or ws.numel() * 4 < nbytes:
+            ws = self._layer_ws = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=table.device)
+        first, chunk_offset = offsets[id(group)]
+        return (table.data_ptr(), count, chunks, chunk_offset, first, tensors, ws.data_ptr(), ws.numel() * 4), ws.data_ptr() + 12 * first
+
+    def load_state_dict(self, state_dict):
+        mine = [dict(g) for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, own in zip(self.param_groups, mine):   # a state dict of the inherited optimizer: these options stay as built
+            for k in self._layer_keys:
+                group.setdefault(k, own[k])
+        self._check_groups()
+
+
+class FusedLARS(_Layerwise, FusedSGD):
+    """LARS (You, Gitman, Ginsburg 2017): ``FusedSGD``'s rule with the update of every parameter TENSOR scaled by a trust ratio,
+
+        r   = trust_coefficient * |p| / (|g| + weight_decay * |p| + eps)     if adapt and |p| > 0 and |g| > 0, else 1
+        d   = r * (g + weight_decay * p)
+        buf = d on the first step taken, else momentum * buf + (1 - dampening) * d
+        p  <- p - lr * (d + momentum * buf if nesterov else buf)
+
+    the norms 2-norms over one tensor, ``g`` unscaled and clipped as in ``FusedSGD``.  Three launches per parameter group and no
+    host synchronisation (csrc/layerwise.hip): partial sums per chunk, one workgroup per tensor that leaves ``{|p|, |g|, r}``
+    on the device, the update.  ``adapt`` is a group option (default True): a group with ``adapt=False`` -- BatchNorm affines and
+    biases, ``layerwise_groups`` -- takes ``r = 1``, which is ``torch.optim.SGD`` and ``FusedSGD`` bit for bit.  State, the
+    first-step rule, ``max_grad_norm``, ``grad_buckets=``, ``LossScaler`` and ``WeightAverage`` are ``FusedSGD``'s;
+    ``layer_norms`` is the per-layer monitor."""
+
+    _layer_keys = ("adapt", "trust_coefficient", "eps")
+
+    def __init__(self, params, lr, momentum=0.9, dampening=0, nesterov=False, weight_decay=1e-4, trust_coefficient=1e-3, eps=1e-8,
+                 maximize=False, max_grad_norm=None, grad_buckets=None):
+        max_grad_norm = self._check_max_grad_norm(max_grad_norm)
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
+                        maximize=bool(maximize), trust_coefficient=trust_coefficient, eps=eps, adapt=True)
+        self._check_group(defaults)
+        torch.optim.Optimizer.__init__(self, params, defaults)
+        for group in self.param_groups:
+            self._check_group(group)
+        self._init_fused(max_grad_norm, grad_buckets)
+        self._started = False
+        self._first_at = -1
+        self._init_layerwise()
+
+    @staticmethod
+    def _check_group(group):
+        FusedSGD._check_group(group)
+        tc, eps = group.get("trust_coefficient", 1e-3), group.get("eps", 1e-8)
+        if not (math.isfinite(tc) and tc > 0):
+            raise ValueError(f"Invalid trust_coefficient value: {tc}")
+        if not (math.isfinite(eps) and eps >= 0):
+            raise ValueError(f"Invalid eps value: {eps}")
+
+    def _update(self, lib, scaler, unscaled, clip_ptr):
+        state_ptr = scaler.state_ptr if scaler is not None else None
+        if scaler is not None:
+            first_step = self._first_at
+        else:
+            first_step = -1 if self._started else 0
+
+        def launch(group, table, count, chunks):
+            place, records = self._place(lib, group, table, count, chunks)
+            wd = float(group["weight_decay"])
+            _lib.check(lib.zsv_lars_norms(*place, state_ptr, _stream()), "zsv_lars_norms")
+            _lib.check(lib.zsv_layerwise_finalize(*place, 0, int(bool(group["adapt"])), float(group["trust_coefficient"]), wd,
+                                                  float(group["eps"]), 0.0, clip_ptr, state_ptr, int(unscaled), _stream()),
+                       "zsv_layerwise_finalize")
+            shadows, avg_state, ema_weight = self._avg_args(table, count) if self._average is not None else (None, None, 0.0)
+            _lib.check(lib.zsv_lars_multi(table.data_ptr(), count, chunks, records, float(group["lr"]), float(group["momentum"]),
+                                          float(group["dampening"]), int(bool(group["nesterov"])), wd, int(bool(group["maximize"])),
+                                          clip_ptr, state_ptr, int(unscaled), first_step, shadows, avg_state, ema_weight, _stream()),
+                       "zsv_lars_multi")
+        return launch
+
+
+class FusedLAMB(_Layerwise, FusedAdam):
+    """LAMB (You et al. 2020): Adam's moments, decoupled weight decay inside the update direction, and a trust ratio per TENSOR,
+
+        m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  t = steps taken + 1 (the scaler's device-resident count under one)
+        u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) + weight_decay * p
+        r = |p| / |u|   if adapt and |p| > 0 and |u| > 0, else 1;   r = min(r, trust_clip) when trust_clip is set
+        p <- p - lr * r * u
+
+    Three launches per parameter group and no host synchronisation (csrc/layerwise.hip): the first updates ``m`` and ``v`` and
+    sums ``p^2`` and ``u^2`` per chunk, the second leaves ``{|p|, |u|, r}`` per tensor on the device, the third recomputes ``u``
+    from the new moments and the old parameter -- ``u`` is never stored, ``.grad`` never rewritten.  ``adapt`` and ``trust_clip``
+    are group options.  The state is ``FusedAdam``'s (``step`` / ``exp_avg`` / ``exp_avg_sq``; a ``FusedAdam`` state dict loads),
+    and so are ``max_grad_norm``, ``grad_buckets=``, ``LossScaler`` and ``WeightAverage``; ``layer_norms`` is the per-layer
+    monitor."""
+
+    _layer_keys = ("adapt", "trust_clip")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, trust_clip=None, max_grad_norm=None,
+                 grad_buckets=None):
+        max_grad_norm = self._check_max_grad_norm(max_grad_norm)
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, trust_clip=trust_clip, adapt=True)
+        self._check_group(defaults)
+        torch.optim.Optimizer.__init__(self, params, defaults)
+        for group in self.param_groups:
+            self._check_group(group)
+        self._init_fused(max_grad_norm, grad_buckets)
+        self._host_steps = 0
+        self._resumed = False
+        self._init_layerwise()
+
+    @classmethod
+    def _check_group(cls, group):
+        lr, eps, (b1, b2), clip = group["lr"], group["eps"], group["betas"], group.get("trust_clip")
+        if not (math.isfinite(lr) and lr >= 0):
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not (math.isfinite(eps) and eps >= 0):
+            raise ValueError(f"Invalid eps value: {eps}")
+        if not (0 <= b1 < 1) or not (0 <= b2 < 1):
+            raise ValueError(f"Invalid betas: {(b1, b2)}")
+        cls._check_decay(group["weight_decay"])
+        if clip is not None and not (isinstance(clip, (int, float)) and math.isfinite(clip) and clip > 0):
+            raise ValueError(f"trust_clip must be a finite positive number or None, not {clip}")
+
+    def _check_groups(self):
+        for group in self.param_groups:
+            self._check_group(group)
+
+    def _update(self, lib, scaler, unscaled, clip_ptr):
+        state_ptr = scaler.state_ptr if scaler is not None else None
+        step = 0 if scaler is not None else self._host_steps + 1      # under a scaler the device counts
+
+        def launch(group, table, count, chunks):
+            place, records = self._place(lib, group, table, count, chunks)
+            b1, b2 = group["betas"]
+            eps, wd = float(group["eps"]), float(group["weight_decay"])
+            _lib.check(lib.zsv_lamb_moments(*place, float(b1), float(b2), eps, wd, clip_ptr, state_ptr, int(unscaled), step, _stream()),
+                       "zsv_lamb_moments")
+            _lib.check(lib.zsv_layerwise_finalize(*place, 1, int(bool(group["adapt"])), 0.0, 0.0, 0.0,
+                                                  float(group["trust_clip"] or 0.0), None, state_ptr, int(unscaled), _stream()),
+                       "zsv_layerwise_finalize")
+            shadows, avg_state, ema_weight = self._avg_args(table, count) if self._average is not None else (None, None, 0.0)
+            _lib.check(lib.zsv_lamb_multi(table.data_ptr(), count, chunks, records, float(group["lr"]), float(b1), float(b2), eps, wd,
+                                          state_ptr, step, shadows, avg_state, ema_weight, _stream()), "zsv_lamb_multi")
+        return launch
+
+
+def layerwise_groups(model, weight_decay):
+    """The two parameter groups LARS and LAMB are usually run with: every trainable parameter with ``dim() >= 2`` (convolution
+    and linear weights) adapts and decays; the rest (BatchNorm affines, biases) takes ``adapt=False`` and no decay."""
+    own = getattr(model, "module", model)
+    params = [p for p in own.parameters() if p.requires_grad]
+    return [dict(params=[p for p in params if p.dim() >= 2], adapt=True, weight_decay=weight_decay),
+            dict(params=[p for p in params if p.dim() < 2], adapt=False, weight_decay=0.0)]
+
+
 class WeightAverage:
     """A running average of the weights for evaluation, kept by the optimizer's own launches.
 
@@ -681,7 +880,7 @@ class WeightAverage:
     def __init__(self, optimizer, decay: Optional[float] = 0.999, model: Optional[torch.nn.Module] = None, buffers: bool = True):
         if not isinstance(optimizer, _FusedOptimizer):
             raise TypeError("WeightAverage averages inside optim.FusedAdam's update launch; got " + type(optimizer).__name__
-                            + " (it takes an optim.FusedAdam or an optim.FusedSGD)")
+                            + " (it takes an optim.FusedAdam, FusedSGD, FusedLARS or FusedLAMB)")
         if decay is not None:
             if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not (0.0 <= decay < 1.0):
                 raise ValueError(f"decay must be None (equal-weight) or a number in [0, 1), not {decay!r}")
