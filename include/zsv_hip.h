@@ -737,7 +737,8 @@ int zsv_swap_multi(const zsv_pair_tensor* table_device, int32_t count, int64_t t
  * leaves steps_done where it was, and the next step is the first one again, as under GradScaler, which never calls
  * optimizer.step() on a skipped step.
  * p, g, buf and the shadows need only be 4-byte aligned, each on its own: a tensor whose pointers are all 16-byte aligned is
- * walked 16 bytes per lane, any other 4 bytes per lane, to the same bits.  No atomics.  No element outside [0, n) of any
+ * walked 16 bytes per lane, any other 4 bytes per lane, to the same bits (all or nothing per tensor: measured faster than
+ * keeping only the aligned arrays of such a tensor on 16 bytes).  No atomics.  No element outside [0, n) of any
  * array is read or written.  ZSV_E_NULL: table NULL, or one of shadows / avg state NULL; ZSV_E_BAD_SHAPE: count <= 0,
  * total_chunks out of range, lr / momentum / weight_decay negative or not finite, nesterov without momentum > 0 and
  * dampening == 0, ema_weight > 1. */
@@ -747,7 +748,7 @@ int zsv_sgd_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t to
                   int32_t first_step, float* const* shadows_device, const zsv_avg_state* avg_state_device, float ema_weight,
                   void* stream);
 
-/* ---- LARS and LAMB: layer-wise trust ratios on the device (csrc/layerwise.hip) -----------------------------------------------
+/* ---- LARS and LAMB: layer-wise trust ratios on the device (csrc/layerwise.hip; zsv_lars_multi: csrc/sgd.hip) ------------------
  * The SGD and Adam rules above with the update of every TENSOR scaled by a ratio of two 2-norms over that tensor.  With
  * g = g_mem * inv_scale * clip_coef exactly as in zsv_sgd_multi / zsv_adamw_multi_scaled:
  *   LARS   r = trust_coefficient * |p| / (|g| + weight_decay * |p| + eps)  if adapt and |p| > 0 and |g| > 0, else 1
@@ -761,8 +762,9 @@ int zsv_sgd_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t to
  * and forms u without storing it), zsv_layerwise_finalize (one workgroup per tensor: the partials of its chunks summed in
  * double in a fixed order, one record written), and the apply (zsv_lars_multi / zsv_lamb_multi, which recomputes u from the
  * updated m, v and the old p).  No atomics: equal inputs give equal bits, at any alignment -- every array needs 4-byte
- * alignment only, each on its own, and moves 16 bytes per lane where its base allows.  With a non-NULL scaler state whose
- * found_inf is set every launch returns before it touches m, v, the momentum buffer, p, the shadows or the records.
+ * alignment only, each on its own, and moves 16 bytes per lane where its base allows (zsv_lars_multi: where all bases of the
+ * tensor allow, as zsv_sgd_multi).  With a non-NULL scaler state whose found_inf is set every launch returns before it
+ * touches m, v, the momentum buffer, p, the shadows or the records.
  *
  * The workspace is ONE buffer for all tables (parameter groups) of a step: `all_count` records, then two floats
  * {sum p^2, sum q^2} per chunk.  A launch names its table's place in it: `tensor_offset` = tensors of the tables before it,
@@ -794,7 +796,8 @@ int zsv_layerwise_finalize(const zsv_adam_tensor* table_device, int32_t count, i
                            int32_t grads_unscaled, void* stream);
 /* The apply launches.  `records_device`: the `count` records of THIS table (workspace + tensor_offset records), read only.
  * Clip record, scaler state, shadows and averaging state are NULL-able exactly as in zsv_sgd_multi; the other arguments of
- * zsv_lars_multi are zsv_sgd_multi's.  zsv_lamb_multi takes no clip record: the gradient is not read again. */
+ * zsv_lars_multi are zsv_sgd_multi's, and so is its kernel (one template, the ratio compiled in).  zsv_lamb_multi takes no
+ * clip record: the gradient is not read again. */
 int zsv_lars_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks,
                    const zsv_layer_record* records_device, double lr, float momentum, float dampening, int32_t nesterov,
                    double weight_decay, int32_t maximize, const zsv_clip_record* clip_device,

@@ -138,6 +138,14 @@ def test_signatures_defaults_and_group_options():
         opt.step()
 
 
+@pytest.mark.parametrize("base,layerwise", [(optim.FusedSGD, optim.FusedLARS), (optim.FusedAdam, optim.FusedLAMB)],
+                         ids=["sgd-lars", "adam-lamb"])
+def test_a_layerwise_optimizer_has_every_attribute_of_the_one_it_inherits(base, layerwise):
+    """The constructors share one set-up: a field the inherited optimizer creates exists in the layer-wise one."""
+    missing = set(vars(base(_ps(), lr=0.1))) - set(vars(layerwise(_ps(), lr=0.1)))
+    assert not missing, sorted(missing)
+
+
 def test_state_dicts_round_trip_and_an_adam_state_loads_into_lamb():
     adam = optim.FusedAdam(_ps(), lr=3e-4, weight_decay=0.02)
     lamb = optim.FusedLAMB([{"params": _ps(), "adapt": False}], lr=1e-3, trust_clip=10.0)

@@ -38,15 +38,18 @@ def _fp32(x, what):
     return x
 
 
-def ref_step(p, g, buf, hp, first, check=None, coef=1.0):
+def ref_step(p, g, buf, hp, first, check=None, coef=1.0, ratio=1.0):
     """torch/optim/sgd.py::_single_tensor_sgd in fp64 on one tensor: returns (p, buf).  ``buf`` is None with momentum == 0;
-    ``first``: the momentum buffer does not exist yet.  ``check`` sees every intermediate."""
+    ``first``: the momentum buffer does not exist yet.  ``check`` sees every intermediate.  ``ratio``: the trust ratio of LARS
+    on g + wd * p (1: the plain rule)."""
     ok = check or (lambda x, what: x)
     g = ok(g * coef, "g * clip_coef")
     if hp.get("maximize", False):
         g = -g
     if hp.get("weight_decay", 0) != 0:
         g = ok(g + ok(hp["weight_decay"] * p, "wd * p"), "g + wd * p")
+    if ratio != 1.0:
+        g = ok(ratio * g, "ratio * (g + wd * p)")
     momentum, dampening = hp.get("momentum", 0), hp.get("dampening", 0)
     if momentum != 0:
         if first:
@@ -180,12 +183,14 @@ class _Own:
         assert torch.equal(self.bufs[1].bytes(), self.g_before), f"{what}: g was written"
 
 
-@pytest.mark.parametrize("layout", list(LAYOUTS))
-def test_chunk_and_alignment_edges_stay_in_bounds(layout):
-    """2: tensors of 1 .. 2 * 4096 + 5 elements in ONE launch (six descriptors, first_chunk 0, 1, 2, 3, 4, 6), each array in
-    poisoned surroundings: the bands hold 0xFF (a NaN, which survives every product, sum and fma of the rule -- there is no max and
-    no comparison on data in it), so a read outside [0, n) reaches a result and a write outside [0, n) changes a band.  One step
-    that reads the buffer (not the first) with weight decay and an EMA shadow, on dyadic operands: values equal the fp64 rule."""
+# the entry point and the trust ratio in every record: zsv_lars_multi is zsv_sgd_multi's kernel with the ratio compiled in
+ENTRIES = {"zsv_sgd_multi": None, "zsv_lars_multi-r1": 1.0, "zsv_lars_multi-r0.5": 0.5}
+EDGE_CASES = [(layout, entry) for layout in LAYOUTS for entry in ENTRIES]
+
+
+def _edge_launch(layout, ratio):
+    """One launch over the six tensors in the layout: ``zsv_sgd_multi``, or with ``ratio`` ``zsv_lars_multi`` reading that ratio from
+    every record (a plain (count, 3) tensor: no workspace launch).  Returns [(holder, operands)] after the launch has finished."""
     lib = _lib.load()
     offsets = LAYOUTS[layout]
     held, rows, first = [], [], 0
@@ -201,19 +206,41 @@ def test_chunk_and_alignment_edges_stay_in_bounds(layout):
     shadows = torch.tensor([h.ptr(3) for h, _ in held], dtype=torch.int64, device=DEV)
     avg_state = torch.tensor([1], dtype=torch.int32, device=DEV)                  # one step averaged already: the shadow is read
     hp = EDGE_HP
-    _lib.check(lib.zsv_sgd_multi(table.data_ptr(), len(rows), first, hp["lr"], hp["momentum"], hp["dampening"], 0, hp["weight_decay"],
-                                 0, None, None, 0, -1, shadows.data_ptr(), avg_state.data_ptr(), 0.5,
-                                 torch.cuda.current_stream().cuda_stream), "zsv_sgd_multi")
+    rule = (hp["lr"], hp["momentum"], hp["dampening"], 0, hp["weight_decay"], 0, None, None, 0, -1, shadows.data_ptr(),
+            avg_state.data_ptr(), 0.5, torch.cuda.current_stream().cuda_stream)
+    if ratio is None:
+        _lib.check(lib.zsv_sgd_multi(table.data_ptr(), len(rows), first, *rule), "zsv_sgd_multi")
+    else:
+        records = torch.tensor([[float("nan"), float("nan"), ratio]] * len(rows), dtype=torch.float32, device=DEV)   # only the ratio is read
+        _lib.check(lib.zsv_lars_multi(table.data_ptr(), len(rows), first, records.data_ptr(), *rule), "zsv_lars_multi")
     torch.cuda.synchronize()
-    for (h, (p, g, buf, shadow)), n in zip(held, SIZES):
-        what = f"{layout} n={n}"
+    assert int(avg_state) == 1                                                     # read, not advanced
+    return held
+
+
+@pytest.mark.parametrize("layout,entry", EDGE_CASES, ids=[l if ENTRIES[e] is None else f"{l}-{e}" for l, e in EDGE_CASES])
+def test_chunk_and_alignment_edges_stay_in_bounds(layout, entry):
+    """2: tensors of 1 .. 2 * 4096 + 5 elements in ONE launch (six descriptors, first_chunk 0, 1, 2, 3, 4, 6), each array in
+    poisoned surroundings: the bands hold 0xFF (a NaN, which survives every product, sum and fma of the rule -- there is no max and
+    no comparison on data in it), so a read outside [0, n) reaches a result and a write outside [0, n) changes a band.  One step
+    that reads the buffer (not the first) with weight decay and an EMA shadow, on dyadic operands: values equal the fp64 rule --
+    through ``zsv_sgd_multi``, through ``zsv_lars_multi`` with every ratio 0.5 (dyadic, so still exact), and through
+    ``zsv_lars_multi`` with every ratio 1, which must also leave the very bytes of the ``zsv_sgd_multi`` launch on the same operands."""
+    ratio = ENTRIES[entry]
+    held = _edge_launch(layout, ratio)
+    plain = _edge_launch(layout, None) if ratio == 1.0 else None
+    hp = EDGE_HP
+    for i, ((h, (p, g, buf, shadow)), n) in enumerate(zip(held, SIZES)):
+        what = f"{entry} {layout} n={n}"
         h.check(what)
-        p1, buf1 = ref_step(p, g, buf, hp, first=False, check=_fp32)
+        p1, buf1 = ref_step(p, g, buf, hp, first=False, check=_fp32, ratio=1.0 if ratio is None else ratio)
         s1 = _fp32(p1 - (p1 - shadow) * 0.5, "shadow")                             # lerp(avg, p, 0.5), torch's form for w >= 0.5
         assert_same_values(h.get(0), p1, what=what + " p")
         assert_same_values(h.get(2), buf1, what=what + " buf")
         assert_same_values(h.get(3), s1, what=what + " shadow")
-    assert int(avg_state) == 1                                                     # read, not advanced
+        if plain is not None:
+            for r, name in ((0, "p"), (2, "buf"), (3, "shadow")):
+                assert torch.equal(h.get(r).view(torch.int32), plain[i][0].get(r).view(torch.int32)), f"{what} {name}: not zsv_sgd_multi's bytes"
 
 
 # ---- 3: random operands, two groups -------------------------------------------------------------------------------------------

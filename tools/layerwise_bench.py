@@ -1,6 +1,6 @@
 """What the layer-wise trust ratio costs on the live parameter set of R(2+1)D-18: FusedLARS against FusedSGD and FusedLAMB against
 FusedAdam(weight_decay=, decoupled_weight_decay=True), alternated in one process on one device.
-    python tools/layerwise_bench.py [--rounds 7] [--steps 50] [--out profiles/layerwise_step.json]
+    python tools/layerwise_bench.py [--rounds 7] [--steps 50] [--out profiles/layerwise_step.json] [--scalar-lib other/libzsv_hip.so]
 
 The table is the live parameter set of R(2+1)D-18 inside network.Model (115 tensors, 31.7 M fp32 values); the gradients are
 synthetic and stay in place, so only the optimizer runs.  Variants are alternated per round (order reversed every other round)
@@ -9,7 +9,8 @@ after a synchronised warm-up, as in tools/sgd_bench.py.
 * "raw": the launches of one step back to back on one prebuilt descriptor table (every tensor 16-byte aligned), timed by device
   events -- the kernel time.  `lars` = zsv_lars_norms + zsv_layerwise_finalize + zsv_lars_multi against `sgd` = zsv_sgd_multi;
   `lamb` = zsv_lamb_moments + zsv_layerwise_finalize + zsv_lamb_multi against `adamw` = zsv_adamw_multi; each baseline a second
-  time in the same rounds (the run-to-run spread).
+  time in the same rounds (the run-to-run spread).  With `--scalar-lib` (as in tools/sgd_bench.py: a second build of the library,
+  with -DZSV_SGD_SCALAR or another commit's) `sgd` and `lars` of that library run in the same rounds, `sgd` twice: the A/B.
 * "parts": the five launches of the two three-launch steps, each back to back on its own: where their time goes.
 * "step": `optimizer.step()` as a training loop calls it, host work included, with per-step tables and over the flat buckets of
   ddp.GradientSync(local=True) (`*_buckets`: the table built once, the gradients bucket views at element offsets).  `device_us`
@@ -20,6 +21,7 @@ Expected kernel-time ratios from bytes per value: LARS reads p and g for the nor
 LAMB moves 24 B (read g, m, v, p, write m, v) and 16 B (read m, v, p, write p) against AdamW's 28 B: 40 / 28 = 1.43; the finalize
 launch comes on top of both.  The summary records the measured ratios next to these."""
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -40,12 +42,18 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--network", default="r2plus1d_18")
+ap.add_argument("--scalar-lib", default="", help="a second build of libzsv_hip.so whose sgd and lars launches run in the same rounds (the A/B)")
 ap.add_argument("--out", default="")
 args = ap.parse_args()
 if not torch.cuda.is_available():
     raise SystemExit("layerwise_bench: needs the GPU (no CPU timing is meaningful here)")
 dev = torch.device("cuda")
 lib = _lib.load()
+other = None
+if args.scalar_lib:
+    other = ctypes.CDLL(os.path.abspath(args.scalar_lib))
+    for sym in ("zsv_sgd_multi", "zsv_lars_norms", "zsv_layerwise_finalize", "zsv_lars_multi"):
+        getattr(other, sym).restype, getattr(other, sym).argtypes = _lib.SIGNATURES[sym]
 
 # the live parameter set: one small training step tells which parameters receive gradients
 model = network.get_network(SimpleNamespace(network=args.network, fixconvs=False, nopretrained=False))
@@ -90,15 +98,23 @@ T, W = table.data_ptr(), ws.data_ptr()
 PLACE = (T, count, chunks, 0, 0, count, W, ws_bytes)
 
 
-def raw_sgd():
-    _lib.check(lib.zsv_sgd_multi(T, count, chunks, 1e-6, 0.9, 0.0, 0, 1e-4, 0, None, None, 0, -1, None, None, 0.0, stream()), "zsv_sgd_multi")
+def raw_sgd_of(which):
+    def run():
+        _lib.check(which.zsv_sgd_multi(T, count, chunks, 1e-6, 0.9, 0.0, 0, 1e-4, 0, None, None, 0, -1, None, None, 0.0, stream()),
+                   "zsv_sgd_multi")
+    return run
 
 
-def raw_lars():
-    _lib.check(lib.zsv_lars_norms(*PLACE, None, stream()), "zsv_lars_norms")
-    _lib.check(lib.zsv_layerwise_finalize(*PLACE, 0, 1, 1e-3, 1e-4, 1e-8, 0.0, None, None, 0, stream()), "zsv_layerwise_finalize")
-    _lib.check(lib.zsv_lars_multi(T, count, chunks, W, 1e-6, 0.9, 0.0, 0, 1e-4, 0, None, None, 0, -1, None, None, 0.0, stream()),
-               "zsv_lars_multi")
+def raw_lars_of(which):
+    def run():
+        _lib.check(which.zsv_lars_norms(*PLACE, None, stream()), "zsv_lars_norms")
+        _lib.check(which.zsv_layerwise_finalize(*PLACE, 0, 1, 1e-3, 1e-4, 1e-8, 0.0, None, None, 0, stream()), "zsv_layerwise_finalize")
+        _lib.check(which.zsv_lars_multi(T, count, chunks, W, 1e-6, 0.9, 0.0, 0, 1e-4, 0, None, None, 0, -1, None, None, 0.0, stream()),
+                   "zsv_lars_multi")
+    return run
+
+
+raw_sgd, raw_lars = raw_sgd_of(lib), raw_lars_of(lib)
 
 
 def raw_adamw():
@@ -112,6 +128,9 @@ def raw_lamb():
 
 
 raw = {"sgd": raw_sgd, "lars": raw_lars, "sgd_again": raw_sgd, "adamw": raw_adamw, "lamb": raw_lamb, "adamw_again": raw_adamw}
+if other is not None:
+    raw.update({"sgd_other_build": raw_sgd_of(other), "lars_other_build": raw_lars_of(other), "sgd_other_build_again": raw_sgd_of(other),
+                "lars_other_build_again": raw_lars_of(other)})
 
 # the same launches one at a time: where the three-launch steps spend their time (bytes per value: what that launch moves)
 parts = {

@@ -10,7 +10,8 @@ alternated per round (order reversed every other round) after a synchronised war
   with scaler state, clip record and shadows; `zsv_adam_multi` on the same table.  With `--scalar-lib` (sgd.hip built with
   -DZSV_SGD_SCALAR into a library of its own: `hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DZSV_SGD_SCALAR
   -Iinclude -Izeroshotvideoclassification_amd/csrc zeroshotvideoclassification_amd/csrc/sgd.hip -o libzsv_sgd_scalar.so`) the 4-bytes-per-lane form of the same kernel runs in the same rounds: the A/B of
-  the 16-byte accesses.
+  the 16-byte accesses.  Any other build of `zsv_sgd_multi` -- another commit's library -- is compared the same way: the second
+  library runs the plain launch twice (its own spread) and the launch with every option.
 * "step": a training loop's calls, host work included: (1) FusedSGD(momentum=0.9, weight_decay=1e-4), (2) the same under
   LossScaler with max_grad_norm and a WeightAverage, and FusedSGD(grad_buckets=) on the local buckets of ddp.GradientSync (the table
   built once; the gradients of every "step" variant are the bucket views, which start at element offsets), (3)
@@ -41,7 +42,8 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--network", default="r2plus1d_18")
-ap.add_argument("--scalar-lib", default="", help="a library exporting zsv_sgd_multi built with -DZSV_SGD_SCALAR (the A/B)")
+ap.add_argument("--scalar-lib", default="",
+                help="a second library exporting zsv_sgd_multi, run in the same rounds: built with -DZSV_SGD_SCALAR, or another commit's (the A/B)")
 ap.add_argument("--out", default="")
 ap.add_argument("--ab-out", default="", help="where the vector / scalar A/B goes (with --scalar-lib)")
 args = ap.parse_args()
@@ -113,17 +115,21 @@ def sgd_of(which):
     return run
 
 
-def sgd_all_options():
-    _lib.check(lib.zsv_sgd_multi(T, count, chunks, 1e-6, 0.9, 0.0, 0, 1e-4, 0, R, S, 0, -1, SH, AS, 1e-3, stream()), "zsv_sgd_multi")
+def sgd_all_options_of(which):
+    def run():
+        _lib.check(which.zsv_sgd_multi(T, count, chunks, 1e-6, 0.9, 0.0, 0, 1e-4, 0, R, S, 0, -1, SH, AS, 1e-3, stream()), "zsv_sgd_multi")
+    return run
 
 
 def adam_multi():
     _lib.check(lib.zsv_adam_multi(T, count, chunks, 1e-6, 0.9, 0.999, 1e-8, 100, stream()), "zsv_adam_multi")
 
 
-raw = {"sgd_multi": sgd_of(lib), "sgd_multi_again": sgd_of(lib), "sgd_multi_scaler_clip_avg": sgd_all_options, "adam_multi": adam_multi}
+raw = {"sgd_multi": sgd_of(lib), "sgd_multi_again": sgd_of(lib), "sgd_multi_scaler_clip_avg": sgd_all_options_of(lib),
+       "adam_multi": adam_multi}
 if scalar is not None:
-    raw["sgd_multi_scalar_build"] = sgd_of(scalar)
+    raw.update({"sgd_multi_scalar_build": sgd_of(scalar), "sgd_multi_scalar_build_again": sgd_of(scalar),
+                "sgd_multi_scaler_clip_avg_scalar_build": sgd_all_options_of(scalar)})
 
 # ---- the optimizers as a loop calls them ------------------------------------------------------------------------------------
 full = optim.FusedSGD(live, max_grad_norm=1.0, **HP)
@@ -222,7 +228,7 @@ if args.out:
 if args.ab_out and scalar is not None:
     ab = {k: result[k] for k in ("network", "device", "tensors", "values", "values_in_16_byte_aligned_tensors", "sgd_step_bytes",
                                  "steps_per_round", "rounds")}
-    ab["raw"] = {k: result["raw"][k] for k in ("sgd_multi", "sgd_multi_again", "sgd_multi_scalar_build")}
+    ab["raw"] = {k: v for k, v in result["raw"].items() if k != "adam_multi"}
     ab["scalar_build_over_vector_kernel"] = result["summary"]["scalar_build_over_vector_kernel"]
     with open(args.ab_out, "w") as f:
         json.dump(ab, f, indent=1)

@@ -1,6 +1,6 @@
 // layerwise.hip -- LARS and LAMB: the SGD and Adam rules with every tensor's update scaled by a trust ratio built from two
-// 2-norms over that tensor (include/zsv_hip.h: zsv_layerwise_*, zsv_lars_*, zsv_lamb_*).  Three passes per parameter group over
-// the zsv_adam_tensor table of zsv_adam_multi, none of which meets the host:
+// 2-norms over that tensor (include/zsv_hip.h: zsv_layerwise_*, zsv_lars_norms, zsv_lamb_*).  Three passes per parameter group
+// over the zsv_adam_tensor table of zsv_adam_multi, none of which meets the host:
 //
 //   partials   one workgroup of 256 per 4096-element chunk (multi_tensor.h) leaves {sum p^2, sum q^2} of its chunk.
 //              LARS: q = g as it lies in memory (the scalar factors 1/scale and clip_coef are applied to the norm in the finalize).
@@ -8,15 +8,16 @@
 //   finalize   one workgroup per TENSOR sums the partials of its chunks [first_chunk, first_chunk + ceil(n / 4096)) in double in a
 //              fixed order and writes the record {p_norm, q_norm, ratio}.
 //   apply      one workgroup per chunk again; the chunk finds its tensor by the binary search it always used and reads
-//              records[index].ratio.  LARS: torch.optim.SGD's element rule (sgd.hip) on d = ratio * (g + wd * p).  LAMB: u is
-//              recomputed from the updated m, v and the old p by the very function the first pass ran (lamb_u, contraction off),
-//              p -= lr * ratio * u.
+//              records[index].ratio.  LARS: zsv_lars_multi, which is sgd.hip's -- the kernel of zsv_sgd_multi with the ratio
+//              compiled in.  LAMB, here: u is recomputed from the updated m, v and the old p by the very function the first pass
+//              ran (lamb_u, contraction off), p -= lr * ratio * u.
 //
 // HBM-bound like sgd.hip, so every array moves 16 bytes per lane where its own base is 16-byte aligned and 4 bytes per lane
 // otherwise.  Both forms walk a chunk as 1024 quads of four consecutive elements, quad v belonging to lane v mod 256, and run the
 // same body on registers: which elements a lane sums, and in which order (<= 16 serial adds, then the fixed 8-level tree of
-// block_sum_256), does not depend on the alignment, so neither do the bits.  No atomics: the same inputs give the same bits on
-// every run.  No element outside [0, n) of any array is read or written, and nothing outside the workspace.
+// block_sum_256), does not depend on the alignment, so neither do the bits.  (The LARS apply has no sum to keep in order and walks
+// a chunk sgd.hip's way, which is the faster one for a chunk with an array off the boundary.)  No atomics: the same inputs give
+// the same bits on every run.  No element outside [0, n) of any array is read or written, and nothing outside the workspace.
 //
 // Under the loss scaler every pass returns on found_inf before it touches m, v, buf, p, the shadows or the records.
 #include "zsv_common.h"
@@ -28,10 +29,6 @@
 
 namespace zsv {
 namespace layerwise {
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool vec16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // quad v of an array: elements [4 v, 4 v + valid), valid in 1..4 (less than 4 only in the last quad of a tensor)
 __device__ __forceinline__ v4f load4(const float* __restrict__ a, int v, int valid, bool vec) {
     if (vec && valid == 4) return reinterpret_cast<const v4f*>(a)[v];
@@ -92,87 +89,6 @@ __global__ __launch_bounds__(256) void lars_norms_kernel(const zsv_adam_tensor* 
     if (threadIdx.x == 0) {
         partials[2 * chunk] = tp;
         partials[2 * chunk + 1] = tg;
-    }
-}
-
-struct LarsArgs {
-    float lr, momentum, one_minus_dampening, wd;
-    int use_momentum, nesterov, maximize;
-    int grads_unscaled;
-    int first_step;                     // "first" iff steps_done (0 without a scaler) == first_step
-    const zsv_clip_record* clip;        // NULL: no clipping
-    const zsv_scaler_state* st;         // NULL: no loss scaler
-    float* const* shadows;              // NULL: no averaging
-    const zsv_avg_state* avg;
-    float ema_weight;
-};
-
-struct LarsStep {
-    float inv_scale, clip;
-    bool first;
-};
-
-// sgd.hip's sgd_one with the trust ratio on g + wd * p: with ratio == 1 (1 * x is x) it is that function, operation for operation.
-__device__ __forceinline__ float lars_one(float p, float g, float& buf, float ratio, const LarsArgs& a, const LarsStep& s) {
-#pragma clang fp contract(off)
-    g = g * s.inv_scale;
-    g = g * s.clip;
-    if (a.maximize) g = -g;
-    if (a.wd != 0.f) g = fmaf(a.wd, p, g);
-    g = ratio * g;                                        // d = r * (g + wd * p)
-    if (a.use_momentum) {
-        if (s.first) {
-            buf = g;
-        } else {
-            const float mb = a.momentum * buf;
-            buf = fmaf(a.one_minus_dampening, g, mb);
-        }
-        g = a.nesterov ? fmaf(a.momentum, buf, g) : buf;
-    }
-    return fmaf(-a.lr, g, p);
-}
-
-__global__ __launch_bounds__(256) void lars_multi_kernel(const zsv_adam_tensor* __restrict__ table, int count,
-                                                         const zsv_layer_record* __restrict__ records, LarsArgs a) {
-    if (a.st != nullptr && a.st->found_inf) return;
-    LarsStep s;
-    s.inv_scale = a.st != nullptr && !a.grads_unscaled ? (float)(1.0 / (double)a.st->scale) : 1.f;
-    s.clip = a.clip != nullptr ? a.clip->clip_coef : 1.f;
-    s.first = (a.st != nullptr ? a.st->steps_done : 0) == a.first_step;
-
-    const long chunk = blockIdx.x;
-    const int index = find_index(table, count, chunk);
-    const zsv_adam_tensor t = table[index];
-    const Span span = chunk_span(t, chunk);
-    if (span.base >= span.end) return;
-    const int len = (int)(span.end - span.base);
-    const float ratio = records[index].ratio;
-    float* __restrict__ p = t.p + span.base;
-    const float* __restrict__ g = t.g + span.base;
-    float* __restrict__ buf = a.use_momentum ? t.exp_avg + span.base : nullptr;
-    float* __restrict__ shadow = a.shadows != nullptr ? a.shadows[index] + span.base : nullptr;
-    AvgWeight k{};
-    if (shadow != nullptr) k = avg_weight(a.avg, a.ema_weight);
-    const bool load_buf = buf != nullptr && !s.first;     // a first step never reads the buffer
-    const bool pv = vec16(p), gv = vec16(g), bv = vec16(buf), sv = vec16(shadow);
-
-    const int quads = (len + 3) >> 2;
-#pragma unroll 2
-    for (int v = threadIdx.x; v < quads; v += 256) {
-        const int valid = min(4, len - 4 * v);
-        v4f p4 = load4(p, v, valid, pv);
-        const v4f g4 = load4(g, v, valid, gv);
-        v4f b4 = v4f{0.f, 0.f, 0.f, 0.f};
-        if (load_buf) b4 = load4(buf, v, valid, bv);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float b = b4[e];
-            p4[e] = lars_one(p4[e], g4[e], b, ratio, a, s);
-            b4[e] = b;
-        }
-        if (buf != nullptr) store4(buf, v, valid, bv, b4);
-        store4(p, v, valid, pv, p4);
-        if (shadow != nullptr) average4(shadow, v, valid, sv, p4, k);
     }
 }
 
@@ -344,10 +260,6 @@ __global__ __launch_bounds__(256) void finalize_kernel(const zsv_adam_tensor* __
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 static inline size_t records_bytes(int64_t count) { return ((size_t)count * sizeof(zsv_layer_record) + 15) & ~(size_t)15; }
 
-static inline bool bad_table(int32_t count, int64_t total_chunks) {
-    return count <= 0 || total_chunks <= 0 || total_chunks > 0x7fffffffL;
-}
-
 struct Workspace {
     zsv_layer_record* records;          // of this table's first tensor
     float* partials;                    // of this table's first chunk
@@ -366,7 +278,6 @@ static int resolve(const void* table, void* workspace, size_t workspace_bytes, i
     return ZSV_OK;
 }
 
-static inline bool bad_rate(double x) { return !(x >= 0.0) || !isfinite(x); }
 }  // namespace layerwise
 }  // namespace zsv
 
@@ -453,38 +364,6 @@ extern "C" int zsv_layerwise_finalize(const zsv_adam_tensor* table_device, int32
     a.st = state_device;
     hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)count), dim3(256), 0, (hipStream_t)stream, table_device, w.partials,
                        w.records, a);
-    return launch_status();
-}
-
-extern "C" int zsv_lars_multi(const zsv_adam_tensor* table_device, int32_t count, int64_t total_chunks,
-                              const zsv_layer_record* records_device, double lr, float momentum, float dampening, int32_t nesterov,
-                              double weight_decay, int32_t maximize, const zsv_clip_record* clip_device,
-                              const zsv_scaler_state* state_device, int32_t grads_unscaled, int32_t first_step,
-                              float* const* shadows_device, const zsv_avg_state* avg_state_device, float ema_weight, void* stream) {
-    if (!table_device || !records_device) return ZSV_E_NULL;
-    if ((shadows_device == nullptr) != (avg_state_device == nullptr)) return ZSV_E_NULL;
-    if (bad_table(count, total_chunks)) return ZSV_E_BAD_SHAPE;
-    if (bad_rate(lr) || bad_rate(weight_decay)) return ZSV_E_BAD_SHAPE;
-    if (!(momentum >= 0.f) || !isfinite(momentum) || !isfinite(dampening)) return ZSV_E_BAD_SHAPE;
-    if (nesterov && (!(momentum > 0.f) || dampening != 0.f)) return ZSV_E_BAD_SHAPE;
-    if (shadows_device != nullptr && !(ema_weight <= 1.f)) return ZSV_E_BAD_SHAPE;
-    LarsArgs a;
-    a.lr = (float)lr;
-    a.momentum = momentum;
-    a.one_minus_dampening = (float)(1.0 - (double)dampening);
-    a.wd = (float)weight_decay;
-    a.use_momentum = momentum != 0.f;
-    a.nesterov = nesterov != 0;
-    a.maximize = maximize != 0;
-    a.grads_unscaled = grads_unscaled != 0;
-    a.first_step = first_step;
-    a.clip = clip_device;
-    a.st = state_device;
-    a.shadows = shadows_device;
-    a.avg = avg_state_device;
-    a.ema_weight = ema_weight;
-    hipLaunchKernelGGL(lars_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_device, count,
-                       records_device, a);
     return launch_status();
 }
 

@@ -19,8 +19,9 @@
 //                                                  device-resident count), swap_multi
 //
 // All of them walk a descriptor table the same way (multi_tensor.h): one workgroup of 256 threads per chunk, a binary search
-// over first_chunk.  The per-element Adam updates and the averaging rule are adam_update.h.  No floating-point atomics: every
-// sum has a fixed order, so the same gradients give the same norm bits and the same parameter bits on every run.
+// over first_chunk; what every entry point refuses of a table (bad_table, bad_rate) is there too.  The per-element Adam updates
+// and the averaging rule are adam_update.h.  No floating-point atomics: every sum has a fixed order, so the same gradients give
+// the same norm bits and the same parameter bits on every run.
 //
 // lr: the four zsv_adam_multi* entry points take it as float, the four zsv_adamw_multi* as double, and both families form
 // lr / (1 - beta1^step) in double -- of (double)(float)lr in the first, which is what their callers have always got.
@@ -311,10 +312,6 @@ __global__ __launch_bounds__(256) void grad_accum_multi_kernel(const zsv_accum_t
     }
 }
 
-static inline bool bad_table(int32_t count, int64_t total_chunks) {
-    return count <= 0 || total_chunks <= 0 || total_chunks > 0x7fffffffL;
-}
-
 // ---- the host half of every Adam launch ------------------------------------------------------------------------------------------
 static inline AdamArgs adam_args(double lr, float beta1, float beta2, float eps) {
     AdamArgs a{};                       // every pointer NULL until an entry point sets it
@@ -338,7 +335,7 @@ static int adam_launch(bool decay_clip, bool scaled, bool avg, const zsv_adam_te
     }
     a.decay = AdamDecay{0.f, 1.f, 0};
     if (decay_clip) {
-        if (!(a.lr >= 0.0) || !(weight_decay >= 0.0) || !isfinite(a.lr) || !isfinite(weight_decay)) return ZSV_E_BAD_SHAPE;
+        if (bad_rate(a.lr) || bad_rate(weight_decay)) return ZSV_E_BAD_SHAPE;
         a.decay.decoupled = decoupled != 0 && weight_decay != 0.0;
         if (a.decay.decoupled) a.decay.decay_factor = (float)(1.0 - a.lr * weight_decay);
         else a.decay.wd_l2 = (float)weight_decay;

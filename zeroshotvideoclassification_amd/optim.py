@@ -57,7 +57,8 @@ copies the gradient into the new buffer; here the launch is told -- by the host,
 steps taken, so that a skipped first step leaves the next one the first -- whether it is that step.
 
 ``FusedLARS`` and ``FusedLAMB`` are ``FusedSGD`` and ``FusedAdam`` with the update of every parameter tensor scaled by a trust ratio of
-two 2-norms over that tensor -- the large-batch forms of the two recipes.  Three launches per parameter group (csrc/layerwise.hip):
+two 2-norms over that tensor -- the large-batch forms of the two recipes.  Three launches per parameter group (csrc/layerwise.hip;
+the LARS update is ``zsv_sgd_multi``'s kernel with the ratio compiled in, csrc/sgd.hip):
 partial sums per chunk (LAMB's also updates the moments), one workgroup per tensor that leaves ``{|p|, |g| or |u|, ratio}`` on the
 device, the update.  No host synchronisation, no atomics; everything the base class gives works with both.  ``layer_norms`` is the
 per-layer norm monitor, ``layerwise_groups(model, weight_decay)`` the usual split into adapting weights and non-adapting affines / biases.
@@ -170,8 +171,26 @@ class _FusedOptimizer(torch.optim.Optimizer):
     """What ``FusedAdam`` and ``FusedSGD`` share: the descriptor tables {p, g, state, state, n, first_chunk} -- rebuilt per step and
     uploaded through a pinned ring, or built once per layout over the flat gradient buckets -- the ``LossScaler`` they are driven
     by, ``LossScaler.unscale_``, the norm pass of ``max_grad_norm``, the ``WeightAverage`` that rides in their launches, and
-    ``step()``.  A subclass names its per-parameter state tensors (``_state_keys``), creates them (``_entry_state``), launches the
-    update of one group (``_update``) and keeps its own count of steps (``_after_step``)."""
+    ``step()``.  A subclass validates its defaults and calls ``_setup``; it checks one group (``_check_group``), creates its own
+    host-side fields (``_reset_rule_state``), names its per-parameter state tensors (``_state_keys``), creates them
+    (``_entry_state``), launches the update of one group (``_update``) and keeps its own count of steps (``_after_step``)."""
+
+    def _setup(self, params, defaults, max_grad_norm, grad_buckets):
+        """What every constructor does once it has validated its defaults: torch's own set-up, the check of every group, the
+        fields of this class and those of the update rule."""
+        torch.optim.Optimizer.__init__(self, params, defaults)
+        for group in self.param_groups:
+            self._check_group(group)
+        self._init_fused(max_grad_norm, grad_buckets)
+        self._reset_rule_state()
+
+    def _check_group(self, group):
+        """Raise ``ValueError`` on a group option the update rule cannot take."""
+        raise NotImplementedError
+
+    def _reset_rule_state(self):
+        """Create the host-side fields of the update rule as they are before the first step (each rule names its own once)."""
+        raise NotImplementedError
 
     def _init_fused(self, max_grad_norm, grad_buckets):
         self.max_grad_norm = max_grad_norm
@@ -300,7 +319,10 @@ class _FusedOptimizer(torch.optim.Optimizer):
             raise RuntimeError(f"{type(self).__name__}: this optimizer is driven by a LossScaler; step through scaler.step(optimizer)")
 
     def _avg_args(self, table, count):
-        """(shadow-pointer array, averaging state, EMA weight) of a launch: the pointers sit behind the ``count`` descriptors."""
+        """(shadow-pointer array, averaging state, EMA weight) of a launch: the pointers sit behind the ``count`` descriptors.
+        Without a ``WeightAverage``: the NULLs that tell the launch so."""
+        if self._average is None:
+            return None, None, 0.0
         return table.data_ptr() + 48 * count, self._average._state_ptr(table.device), self._average._ema_weight
 
     def _tables(self):
@@ -425,13 +447,16 @@ class FusedAdam(_FusedOptimizer):
             raise ValueError("invalid Adam hyper-parameters")
         self._check_decay(weight_decay)
         max_grad_norm = self._check_max_grad_norm(max_grad_norm)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      decoupled_weight_decay=bool(decoupled_weight_decay)))
-        for group in self.param_groups:
-            self._check_decay(group["weight_decay"])
-            if not (math.isfinite(group["lr"]) and group["lr"] >= 0):
-                raise ValueError(f"invalid learning rate {group['lr']}")
-        self._init_fused(max_grad_norm, grad_buckets)
+        self._setup(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                 decoupled_weight_decay=bool(decoupled_weight_decay)), max_grad_norm, grad_buckets)
+
+    @classmethod
+    def _check_group(cls, group):
+        cls._check_decay(group["weight_decay"])
+        if not (math.isfinite(group["lr"]) and group["lr"] >= 0):
+            raise ValueError(f"invalid learning rate {group['lr']}")
+
+    def _reset_rule_state(self):
         self._host_steps = 0                              # steps taken without a scaler
         self._resumed = False                             # state came from load_state_dict (a scaler may then join late)
 
@@ -560,11 +585,10 @@ class FusedSGD(_FusedOptimizer):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         max_grad_norm = self._check_max_grad_norm(max_grad_norm)
-        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                                      nesterov=bool(nesterov), maximize=bool(maximize)))
-        for group in self.param_groups:
-            self._check_group(group)
-        self._init_fused(max_grad_norm, grad_buckets)
+        self._setup(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
+                                 maximize=bool(maximize)), max_grad_norm, grad_buckets)
+
+    def _reset_rule_state(self):
         self._started = False                             # an update has been launched, or buffers were loaded: no host-side "first"
         self._first_at = -1                               # under a scaler: the launch is the first iff steps_done == this (-1: never)
 
@@ -621,15 +645,18 @@ class FusedSGD(_FusedOptimizer):
         for group in self.param_groups:
             self._check_group(group)
 
-    def _update(self, lib, scaler, unscaled, clip_ptr):
-        state_ptr = scaler.state_ptr if scaler is not None else None
+    def _step_flags(self, scaler):
+        """``(state_ptr, first_step)`` of this step's launches: the scaler's device state, or None, and the count of steps taken
+        at which a launch is the first (class docstring) -- the host's own answer, 0 or -1, without a scaler."""
         if scaler is not None:
-            first_step = self._first_at
-        else:
-            first_step = -1 if self._started else 0
+            return scaler.state_ptr, self._first_at
+        return None, -1 if self._started else 0
+
+    def _update(self, lib, scaler, unscaled, clip_ptr):
+        state_ptr, first_step = self._step_flags(scaler)
 
         def launch(group, table, count, chunks):
-            shadows, avg_state, ema_weight = self._avg_args(table, count) if self._average is not None else (None, None, 0.0)
+            shadows, avg_state, ema_weight = self._avg_args(table, count)
             _lib.check(lib.zsv_sgd_multi(table.data_ptr(), count, chunks, float(group["lr"]), float(group["momentum"]),
                                          float(group["dampening"]), int(bool(group["nesterov"])), float(group["weight_decay"]),
                                          int(bool(group["maximize"])), clip_ptr, state_ptr, int(unscaled), first_step,
@@ -671,7 +698,8 @@ class _Layerwise:
 
     _layer_keys = ()                                      # the group options a state dict of the inherited optimizer lacks
 
-    def _init_layerwise(self):
+    def _reset_rule_state(self):
+        super()._reset_rule_state()                       # the fields of the inherited rule
         self._layer_ws = None                             # fp32 view of the workspace (records first)
         self._layout = ({}, 0, 0)                         # {id(group): (tensor offset, chunk offset)}, tensors, chunks of this step
         self.layer_params = []                            # the parameters behind the rows of layer_norms, in order
@@ -743,13 +771,7 @@ class FusedLARS(_Layerwise, FusedSGD):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
                         maximize=bool(maximize), trust_coefficient=trust_coefficient, eps=eps, adapt=True)
         self._check_group(defaults)
-        torch.optim.Optimizer.__init__(self, params, defaults)
-        for group in self.param_groups:
-            self._check_group(group)
-        self._init_fused(max_grad_norm, grad_buckets)
-        self._started = False
-        self._first_at = -1
-        self._init_layerwise()
+        self._setup(params, defaults, max_grad_norm, grad_buckets)
 
     @staticmethod
     def _check_group(group):
@@ -761,11 +783,7 @@ class FusedLARS(_Layerwise, FusedSGD):
             raise ValueError(f"Invalid eps value: {eps}")
 
     def _update(self, lib, scaler, unscaled, clip_ptr):
-        state_ptr = scaler.state_ptr if scaler is not None else None
-        if scaler is not None:
-            first_step = self._first_at
-        else:
-            first_step = -1 if self._started else 0
+        state_ptr, first_step = self._step_flags(scaler)
 
         def launch(group, table, count, chunks):
             place, records = self._place(lib, group, table, count, chunks)
@@ -774,7 +792,7 @@ class FusedLARS(_Layerwise, FusedSGD):
             _lib.check(lib.zsv_layerwise_finalize(*place, 0, int(bool(group["adapt"])), float(group["trust_coefficient"]), wd,
                                                   float(group["eps"]), 0.0, clip_ptr, state_ptr, int(unscaled), _stream()),
                        "zsv_layerwise_finalize")
-            shadows, avg_state, ema_weight = self._avg_args(table, count) if self._average is not None else (None, None, 0.0)
+            shadows, avg_state, ema_weight = self._avg_args(table, count)
             _lib.check(lib.zsv_lars_multi(table.data_ptr(), count, chunks, records, float(group["lr"]), float(group["momentum"]),
                                           float(group["dampening"]), int(bool(group["nesterov"])), wd, int(bool(group["maximize"])),
                                           clip_ptr, state_ptr, int(unscaled), first_step, shadows, avg_state, ema_weight, _stream()),
@@ -804,13 +822,7 @@ class FusedLAMB(_Layerwise, FusedAdam):
         max_grad_norm = self._check_max_grad_norm(max_grad_norm)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, trust_clip=trust_clip, adapt=True)
         self._check_group(defaults)
-        torch.optim.Optimizer.__init__(self, params, defaults)
-        for group in self.param_groups:
-            self._check_group(group)
-        self._init_fused(max_grad_norm, grad_buckets)
-        self._host_steps = 0
-        self._resumed = False
-        self._init_layerwise()
+        self._setup(params, defaults, max_grad_norm, grad_buckets)
 
     @classmethod
     def _check_group(cls, group):
@@ -842,7 +854,7 @@ class FusedLAMB(_Layerwise, FusedAdam):
             _lib.check(lib.zsv_layerwise_finalize(*place, 1, int(bool(group["adapt"])), 0.0, 0.0, 0.0,
                                                   float(group["trust_clip"] or 0.0), None, state_ptr, int(unscaled), _stream()),
                        "zsv_layerwise_finalize")
-            shadows, avg_state, ema_weight = self._avg_args(table, count) if self._average is not None else (None, None, 0.0)
+            shadows, avg_state, ema_weight = self._avg_args(table, count)
             _lib.check(lib.zsv_lamb_multi(table.data_ptr(), count, chunks, records, float(group["lr"]), float(b1), float(b2), eps, wd,
                                           state_ptr, step, shadows, avg_state, ema_weight, _stream()), "zsv_lamb_multi")
         return launch
