@@ -323,6 +323,43 @@ int zsv_split_accuracy(const float* pred, const float* true_embed, const int64_t
                        int32_t rows, int32_t dim, int32_t n_classes, const int32_t* split_pos, int32_t n_tables,
                        int32_t* counts, int32_t* class_counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- softmax cross-entropy (training a trunk as a classifier) -------------------------------- */
+/* torch.nn.functional.cross_entropy(logits, labels, ignore_index=, label_smoothing=, reduction="mean" | "sum") without
+ * class weights, its gradient, and the top-1 / top-5 hit counts of the same logits (csrc/softmax_xent.hip).  The reference
+ * has no such call: it is how the trunks it downloads (resnet.py:287-289) are trained.  logits (N, C) fp32 row-major (4-byte
+ * alignment is enough), labels (N) int64, both on the device.  Three launches; no atomics, no workspace, no host
+ * synchronisation; the same inputs give the same bits run to run and at any alignment of logits, dlogits and dx (a thread
+ * owns the same elements of a row whether the row is moved 16 or 4 bytes at a time).  The row maximum is subtracted before
+ * every exp.
+ *
+ * _fwd, one 256-thread workgroup per row.  With lse the row's log-sum-exp, p its softmax, y its label, e = label_smoothing:
+ *   row_loss[r] = (1 - e) (lse - x[y]) + e (lse - mean_j x[j]);
+ *   row_rank[r] = the number of classes j with x[j] > x[y], or x[j] == x[y] and j < y (ties go to the lower index, as in
+ *                 the cosine ranking above): the row is a top-k hit iff 0 <= rank < k;
+ *   dlogits[r]  = p - ((1 - e) onehot(y) + e / C), NOT yet scaled by the reduction; dlogits may be NULL (no gradient wanted).
+ * A row whose label equals ignore_index: loss 0, rank -1, a gradient row of zeros (written: the buffer arrives
+ * uninitialised).  A row with any other label outside [0, C) breaks the contract: its loss and gradient row are NaN, its
+ * rank is INT32_MAX (it counts as valid and is never a hit), and its logits are not read.  A NaN logit at the label gives
+ * rank INT32_MAX as well (and a NaN loss).
+ *
+ * _reduce, one workgroup, fixed order: counts = {valid rows (rank >= 0), top-1 hits (rank == 0), top-5 hits (rank < 5)},
+ * loss[0] = the sum of row_loss over the valid rows, divided by `valid` when mean != 0.  When EVERY row is ignored the loss
+ * is 0 (and the gradient, below, is 0) -- a deliberate departure from torch, which returns NaN (0 / 0) for the mean: the
+ * filter is on the device so that a batch of failed loads (label -1, auxiliary_dataset.py:502-505) needs no decision on
+ * the host.
+ *
+ * _bwd: dx = dlogits * grad_loss[0] * (mean ? 1 / max(valid, 1) : 1) with valid = counts[0]; grad_loss is a DEVICE scalar
+ * (the gradient arriving at the loss; a loss scale costs no synchronisation).  dx may be dlogits itself.
+ *
+ * All refusals are decided before any launch: ZSV_E_NULL; ZSV_E_BAD_SHAPE for N <= 0, C <= 0 or label_smoothing outside
+ * [0, 1); ZSV_E_TOO_LARGE for N * C >= 2^31. */
+int zsv_softmax_xent_fwd(const float* logits, const int64_t* labels, int32_t N, int32_t C, double label_smoothing,
+                         int64_t ignore_index, float* row_loss, int32_t* row_rank, float* dlogits, void* stream);
+int zsv_softmax_xent_reduce(const float* row_loss, const int32_t* row_rank, int32_t N, int32_t mean, float* loss,
+                            int32_t* counts, void* stream);
+int zsv_softmax_xent_bwd(const float* dlogits, const float* grad_loss, const int32_t* counts, int32_t mean, int32_t N,
+                         int32_t C, float* dx, void* stream);
+
 /* ---- optimiser ------------------------------------------------------------------ */
 /* One torch.optim.Adam step (main.py:131; betas (0.9, 0.999), eps 1e-8, no weight decay,
  * no amsgrad) over a flat fp32 buffer: p, g, exp_avg, exp_avg_sq of n elements.

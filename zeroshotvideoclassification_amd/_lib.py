@@ -129,6 +129,11 @@ SIGNATURES = {
     # pred, true, labels, class table, rows, dim, classes, position tables, tables, counts, class_counts, workspace, bytes, stream
     "zsv_split_accuracy_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "zsv_split_accuracy": (c_int, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_size_t, _P]),
+    # softmax cross-entropy (csrc/softmax_xent.hip): logits, labels, N, C, label_smoothing, ignore_index, row_loss, row_rank, dlogits,
+    # stream / row_loss, row_rank, N, mean, loss, counts, stream / dlogits, grad_loss, counts, mean, N, C, dx, stream
+    "zsv_softmax_xent_fwd": (c_int, [_P, _P, c_int32, c_int32, c_double, c_int64, _P, _P, _P, _P]),
+    "zsv_softmax_xent_reduce": (c_int, [_P, _P, c_int32, c_int32, _P, _P, _P]),
+    "zsv_softmax_xent_bwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "zsv_adam_multi": (c_int, [_P, c_int32, c_int64, c_float, c_float, c_float, c_float, c_int32, _P]),
     "zsv_grad_check_multi": (c_int, [_P, c_int32, c_int64, _P, _P]),
     "zsv_adam_multi_scaled": (c_int, [_P, c_int32, c_int64, c_float, c_float, c_float, c_float, _P, _P]),

@@ -10,6 +10,9 @@ builds but never uses), same outputs:
 * ``ResNet18`` (dead in the reference, kept for the surface)        network.py:50-80
 * ``MLP``                                                           network.py:603-618
 
+Beyond that surface: ``Classifier`` / ``get_classifier`` / ``SoftmaxCrossEntropy`` train a VideoResNet trunk on class labels
+(``trunk.fc`` applied, fused softmax cross-entropy), which is how the trunks the reference downloads are made.
+
 Convolutions, BatchNorm, ReLU, pooling and the dense layers run in the gfx950 kernels
 (``ops``); ``F.normalize``, dropout and the clip-mean stay in PyTorch, as does autograd.
 """
@@ -107,6 +110,85 @@ class Model(nn.Module):
         pooled = ops.mean_pool(feats)                          # torch.mean(feats, dim=(2,3,4)), network.py:595
         emb = F.normalize(self.output2emb_proj(pooled))        # network.py:596
         return emb, None
+
+
+class Classifier(nn.Module):
+    """A video trunk trained as a classifier: ``logits = trunk.fc(pooled feature)`` -- how R(2+1)D / R3D / CSN weights are made
+    before the zero-shot stage takes them over (the reference downloads them, resnet.py:287-289).  Not part of the reference's
+    surface.  ``network`` is a ``resnet`` factory; the trunk is ``self.model`` exactly as in ``Model``, so the state-dict keys
+    are ``model.*`` -- ``model.fc.*`` included -- and ``train.save_checkpoint(classifier)`` -> ``train.load_weights(Model(same
+    factory))`` carries every trunk tensor across.  ``fixconvs=True`` freezes everything but ``model.fc`` (a linear probe).
+
+    ``forward(x (bs, nc, 3, T, H, W)) -> logits (bs * nc, num_classes)``, a tensor.  Under ``amp.autocast()`` in training mode
+    the pooled feature comes from the bf16 trunk (``amp.trunk_features``) as in ``Model.forward``; ``fc`` stays fp32.  Every
+    other mode takes the fp32 modules (there is no reduced-precision classifier engine)."""
+
+    def __init__(self, network, num_classes=400, fixconvs=False):
+        super().__init__()
+        # (a class -- network.C3D, network.Model -- is not a trunk factory: refused below without being called)
+        model = network(pretrained=False, num_classes=num_classes) if callable(network) and not isinstance(network, type) else None
+        if not isinstance(model, models.VideoResNet):
+            raise TypeError(f"Classifier wraps a resnet.VideoResNet factory (r3d_18, mc3_18, r2plus1d_18, ir_csn_50), not {network!r}: "
+                            "network.C3D and other modules have no classification layer of their own here")
+        self.model = model
+        if fixconvs:
+            _freeze(self.model)
+            for p in self.model.fc.parameters():
+                p.requires_grad = True
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError(f"Classifier runs only on an MI355X HIP device; got a {x.device} tensor (there is no CPU fallback)")
+        bs, nc, ch, t, h, w = x.shape
+        clips = x.reshape(bs * nc, ch, t, h, w)
+        from . import amp
+        if amp.is_autocast_enabled() and self.training:
+            pooled = amp.trunk_features(self.model, clips)
+        else:
+            pooled, _ = self.model(clips)
+        return self.model.fc(pooled)
+
+
+def get_classifier(opt, num_classes=400):
+    """``get_network``'s substring dispatch on ``opt.network`` for the VideoResNet trunks, returning a ``Classifier``; reads
+    ``opt.fixconvs`` (a linear probe when set)."""
+    name = opt.network
+    if "r3d" in name:
+        factory = models.r3d_18
+    elif "2plus1d" in name:
+        factory = models.r2plus1d_18
+    elif "csn" in name:
+        factory = models.ir_csn_50
+    else:
+        raise Exception("Network {} has no classifier: r3d / 2plus1d / csn trunks only (c3d has no classification layer here)"
+                        .format(name))
+    return Classifier(factory, num_classes=num_classes, fixconvs=getattr(opt, "fixconvs", False))
+
+
+class SoftmaxCrossEntropy(nn.Module):
+    """``nn.CrossEntropyLoss(ignore_index=, label_smoothing=, reduction=)`` without class weights on ``ops.softmax_cross_entropy``:
+    ``forward(logits (N, C), labels (N) int64) -> loss``, the criterion of ``train.train_step(classifier, optimizer, criterion, x,
+    labels)``.  The hit counts of the last call stay on ``self.counts`` (int32[3] on the device: rows not ignored, top-1 hits,
+    top-5 hits; ``train.classification_accuracy`` turns them into percentages without a synchronisation).
+
+    Rows labelled ``ignore_index`` (-1: a failed load) are dropped on the device; a batch of nothing else gives loss 0 and a zero
+    gradient.  Under ``train_step(micro_batches=k)`` each part is reduced on its own and weighted by its SIZE, so with
+    ``reduction="mean"`` and ignored rows the step's loss is the size-weighted mean of the parts' means, not the mean over all
+    valid rows (the two agree when nothing is ignored); ``self.counts`` then holds the last part's."""
+
+    def __init__(self, label_smoothing=0.0, ignore_index=-1, reduction="mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"reduction {reduction!r}: \"mean\" or \"sum\"")
+        if not 0.0 <= float(label_smoothing) < 1.0:
+            raise ValueError(f"label_smoothing {label_smoothing} is outside [0, 1)")
+        self.label_smoothing, self.ignore_index, self.reduction = float(label_smoothing), int(ignore_index), reduction
+        self.counts = None
+
+    def forward(self, logits, labels):
+        loss, self.counts = ops.softmax_cross_entropy(logits, labels.reshape(-1), self.label_smoothing, self.ignore_index,
+                                                      self.reduction)
+        return loss
 
 
 class ResNet18(nn.Module):

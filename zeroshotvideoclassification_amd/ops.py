@@ -1316,6 +1316,85 @@ def linear(x, weight, bias=None, relu=False):
     return _Linear.apply(x, weight, bias, bool(relu))
 
 
+# ------------------------------------------------------------------------------------------
+class _SoftmaxCrossEntropy(Function):
+    """F.cross_entropy(logits, labels, ignore_index=, label_smoothing=, reduction=) and the top-1 / top-5 counts of the same
+    logits (csrc/softmax_xent.hip): two launches forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, label_smoothing, ignore_index, mean):
+        rows, classes = int(logits.shape[0]), int(logits.shape[1])
+        want_grad = ctx.needs_input_grad[0]
+        row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
+        row_rank = torch.empty(rows, dtype=torch.int32, device=logits.device)
+        dlogits = torch.empty_like(logits) if want_grad else None
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        counts = torch.empty(3, dtype=torch.int32, device=logits.device)
+        lib = _lib.load()
+        with torch.cuda.device(logits.device):
+            _lib.check(lib.zsv_softmax_xent_fwd(logits.data_ptr(), labels.data_ptr(), rows, classes, label_smoothing, ignore_index,
+                                                row_loss.data_ptr(), row_rank.data_ptr(), _ptr(dlogits), _stream()),
+                       "zsv_softmax_xent_fwd")
+            _lib.check(lib.zsv_softmax_xent_reduce(row_loss.data_ptr(), row_rank.data_ptr(), rows, 1 if mean else 0, loss.data_ptr(),
+                                                   counts.data_ptr(), _stream()), "zsv_softmax_xent_reduce")
+        ctx.dims = (rows, classes)
+        ctx.mean = bool(mean)
+        ctx.spent = False
+        ctx.save_for_backward(dlogits, counts)
+        ctx.mark_non_differentiable(counts)
+        return loss, counts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_counts=None):
+        dlogits, counts = ctx.saved_tensors
+        if ctx.spent:
+            raise RuntimeError("softmax_cross_entropy: backward ran already; it scales the saved gradient in place, so a second "
+                               "pass (retain_graph=True) needs a second forward")
+        ctx.spent = True
+        rows, classes = ctx.dims
+        grad_loss = grad_loss.to(device=dlogits.device, dtype=torch.float32).contiguous()
+        with torch.cuda.device(dlogits.device):
+            _lib.check(_lib.load().zsv_softmax_xent_bwd(dlogits.data_ptr(), grad_loss.data_ptr(), counts.data_ptr(),
+                                                        1 if ctx.mean else 0, rows, classes, dlogits.data_ptr(), _stream()),
+                       "zsv_softmax_xent_bwd")
+        return dlogits, None, None, None, None
+
+
+def softmax_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0, ignore_index: int = -1,
+                          reduction: str = "mean") -> Tuple[torch.Tensor, torch.Tensor]:
+    """``F.cross_entropy(logits, labels, ignore_index=, label_smoothing=, reduction=)`` without class weights, and the hit counts
+    of the same pass.  ``logits`` (N, C) fp32 and ``labels`` (N) int64, both on the device.  Returns ``(loss, counts)``: ``loss``
+    a 0-d fp32 device tensor, ``counts`` int32[3] on the device = rows not ignored, top-1 hits, top-5 hits (not differentiable;
+    ties at the label go to the lower class index).  Nothing synchronises: the backward scales the gradient the forward already
+    wrote by the incoming device scalar, in place -- so a graph can be walked once.
+
+    Rows labelled ``ignore_index`` contribute nothing; when every row is ignored the loss and the gradient are 0 (torch: NaN
+    for ``"mean"``).  Any other label outside ``[0, C)`` makes the loss and that gradient row NaN.  ``N == 0`` returns zeros
+    without a launch."""
+    if not (logits.is_cuda and labels.is_cuda):
+        raise RuntimeError("softmax_cross_entropy runs only on an MI355X HIP device; got "
+                           f"{logits.device} logits and {labels.device} labels (there is no CPU fallback)")
+    if logits.dtype != torch.float32:
+        raise RuntimeError(f"softmax_cross_entropy: fp32 logits expected, got {logits.dtype}")
+    if labels.dtype != torch.int64:
+        raise RuntimeError(f"softmax_cross_entropy: int64 labels expected, got {labels.dtype}")
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0] or logits.shape[1] == 0:
+        raise RuntimeError(f"softmax_cross_entropy: logits {tuple(logits.shape)} vs labels {tuple(labels.shape)}: (N, C) and (N) expected")
+    if labels.device != logits.device:
+        raise RuntimeError(f"softmax_cross_entropy: logits on {logits.device}, labels on {labels.device}")
+    if reduction not in ("mean", "sum"):
+        raise RuntimeError(f"softmax_cross_entropy: reduction {reduction!r} (\"mean\" or \"sum\")")
+    label_smoothing = float(label_smoothing)
+    if not 0.0 <= label_smoothing < 1.0:
+        raise RuntimeError(f"softmax_cross_entropy: label_smoothing {label_smoothing} is outside [0, 1)")
+    if logits.shape[0] == 0:
+        loss = (logits * 0.0).sum() if logits.requires_grad and torch.is_grad_enabled() else logits.new_zeros(())
+        return loss, torch.zeros(3, dtype=torch.int32, device=logits.device)
+    return _SoftmaxCrossEntropy.apply(logits.contiguous(), labels.contiguous(), label_smoothing, int(ignore_index),
+                                      reduction == "mean")
+
+
 def adam_step_(p: torch.Tensor, g: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: int,
                lr: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
     """In-place torch.optim.Adam update (main.py:131) of a flat fp32 buffer."""

@@ -16,6 +16,10 @@ and one device -> host copy of its integers.
 ``load_weights`` / ``save_checkpoint`` keep the reference's checkpoint format (main.py:114-124,
 361-365): ``{'state_dict' ('module.'-prefixed keys), 'opt', 'accuracy'}``, loaded by key
 intersection, so checkpoints move between the two implementations unchanged.
+
+``classification_accuracy`` / ``evaluate_classification`` are the same two things for a ``network.Classifier`` -- a trunk
+trained on class labels before the zero-shot stage takes it over (not in the reference, which downloads such trunks): top-1 /
+top-5 of the logits from the counts the loss kernel leaves on the device.
 """
 from __future__ import annotations
 
@@ -32,10 +36,18 @@ from . import _lib, ops
 _PREFIX = "module."       # nn.DataParallel's prefix in saved checkpoints (main.py:116,126,363)
 
 
+_CLASS_LAYER = "model.fc."    # the trunk's classification layer: its class count belongs to the task the checkpoint was trained on
+
+
 def load_weights(model: torch.nn.Module, path: str, key: str = "state_dict") -> int:
     """main.py:114-124: strip the ``module.`` prefix, keep the keys the model has, load the rest
     from the model itself.  Returns the number of tensors taken from the checkpoint.  ``key="state_dict_avg"`` loads the
-    averaged weights ``save_checkpoint(average=)`` stored next to the live ones."""
+    averaged weights ``save_checkpoint(average=)`` stored next to the live ones.
+
+    The trunk's classification layer (``model.fc.*``) is left out, and not counted, when its shape differs from the model's:
+    a ``network.Classifier`` pre-trained on any number of classes hands its trunk to a ``network.Model`` (which builds that
+    layer with 400 and never applies it) or to a classifier for another label set.  Every other shape mismatch raises, as
+    ``load_state_dict`` does."""
     checkpoint = torch.load(path, map_location="cpu", weights_only=False)
     if key not in checkpoint:
         raise KeyError(f"{path} has no {key!r}: it holds {sorted(checkpoint, key=str)}")
@@ -44,6 +56,8 @@ def load_weights(model: torch.nn.Module, path: str, key: str = "state_dict") -> 
     model_dict = own.state_dict()
     j = len(_PREFIX)
     weights = {k[j:]: v for k, v in weights.items() if k[j:] in model_dict}
+    weights = {k: v for k, v in weights.items()
+               if not (k.startswith(_CLASS_LAYER) and tuple(v.shape) != tuple(model_dict[k].shape))}
     model_dict.update(weights)
     own.load_state_dict(model_dict)
     _lib.note_raw_write()
@@ -445,3 +459,41 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]], 
         out["class_counts"] = per
         out["mean_class_accuracy"] = float(np.mean(per[seen, 1] / per[seen, 0] * 100)) if seen.any() else 0.0
     return out
+
+
+def classification_accuracy(counts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-1 and top-5 accuracy in percent from the ``counts`` of ``ops.softmax_cross_entropy`` /
+    ``network.SoftmaxCrossEntropy.counts`` (rows not ignored, top-1 hits, top-5 hits).  Two 0-d tensors on ``counts``' device,
+    no host synchronisation; 0 when no row was scored."""
+    scored = counts[0].clamp(min=1).to(torch.float32)
+    return counts[1].to(torch.float32) * 100.0 / scored, counts[2].to(torch.float32) * 100.0 / scored
+
+
+@torch.no_grad()
+def evaluate_classification(model: torch.nn.Module, batches: Iterable[Sequence[torch.Tensor]],
+                            device: Optional[torch.device] = None, label_smoothing: float = 0.0) -> dict:
+    """``evaluate``'s loop for a ``network.Classifier``: eval-mode forward under ``no_grad``, cross-entropy and top-1 / top-5
+    per clip.  ``batches`` yields ``(X (bs, nc, 3, T, H, W), labels (bs) or (bs, nc), ...)``; a clip labelled -1 (a failed load,
+    auxiliary_dataset.py:502-505) is dropped by the loss kernel's ``ignore_index`` on the device, not by indexing on the host.
+    The loss sum and the counts accumulate on the device and come back in ONE device -> host copy at the end.  Returns
+    ``{"loss": mean loss of the scored clips, "top1": percent, "top5": percent, "samples": clips scored}``.  One process;
+    clips are scored one by one (no averaging over the clips of a video)."""
+    modes = [(m, m.training) for m in model.modules()]
+    model.eval()
+    device = device or next(model.parameters()).device
+    totals = torch.zeros(4, dtype=torch.float64, device=device)          # loss sum, rows scored, top-1 hits, top-5 hits
+    for batch in batches:
+        x, l = batch[0], batch[1]
+        clips_per_sample = int(x.shape[1])
+        if l.dim() == 1 and clips_per_sample > 1:
+            l = l.repeat_interleave(clips_per_sample)
+        logits = model(x.to(device, non_blocking=True))
+        loss, counts = ops.softmax_cross_entropy(logits.float(), l.reshape(-1).to(device, non_blocking=True).long(),
+                                                 label_smoothing=label_smoothing, ignore_index=-1, reduction="sum")
+        totals[0] += loss
+        totals[1:] += counts
+    for m, training in modes:
+        m.training = training
+    loss_sum, samples, top1, top5 = totals.cpu().tolist()
+    n = max(samples, 1.0)
+    return {"loss": loss_sum / n, "top1": top1 / n * 100, "top5": top5 / n * 100, "samples": int(samples)}
