@@ -249,6 +249,61 @@ int zsv_bn_bwd_eval(const float* dy, const float* x, const float* y, int32_t N, 
 int zsv_bn_eval_coeffs(int32_t C, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                        float eps, float* coef, int32_t coef_pitch, void* stream);
 
+/* ---- BatchNorm3d with batch statistics over all ranks of a data-parallel job (torch.nn.SyncBatchNorm) ---------------------
+ * The training-mode forward and backward above, cut where the ranks have to talk: the caller runs ONE collective between
+ * two calls per direction and the library never sees a communicator.
+ *
+ *   forward :  zsv_bn_sync_moments  -> all_gather of 2C+1 doubles -> zsv_bn_sync_finalize -> zsv_bn_sync_apply
+ *   backward:  zsv_bn_sync_bwd_reduce -> all_reduce(SUM) of 2C doubles -> zsv_bn_sync_bwd_apply
+ *
+ * The passes over the big tensors are the plain family's kernels (one read of x for the moments; read x (+ residual), write y;
+ * read dy, x (, y) for the sums; read dy, x (, y), write dx (+ d_residual)) with the same float4 route on S % 4 == 0, the same
+ * non-temporal streaming, the same fixed-order fp64 block sums (bitwise reproducible, no atomics) and the same per-element
+ * arithmetic: the normalise fma, the ReLU masks of zsv_bn_bwd's modes 1 and 2 and the pivoted sums are the same device
+ * functions.  One difference: with fuse_relu = 1 AND a residual gradient zsv_bn_bwd writes the masked gradient in its
+ * reduction and reads it alone in its apply pass (7 passes); here the reduction has no tensor output and the apply pass reads
+ * dy and y again (8 passes).
+ *
+ * moments (one rank's contribution): double[2*C + 1] = C local means | C local M2 (sum of squared deviations from the local
+ *   mean) | the local count N*S.  The sums are shifted by this rank's own x[c*S] (the pivot never leaves the rank) and
+ *   finalised in fp64: mean = K + s1/n, M2 = s2 - s1*s1/n (clamped at 0).  N == 0 is legal: zeros and count 0, x is not read.
+ * zsv_bn_sync_finalize: gathered = double[world][2*C + 1] in rank order.  The ranks are merged in that order with Chan's
+ *   pairwise update in fp64 (n = n_a + n_b, delta = mean_b - mean_a, mean += delta * n_b / n, M2 += M2_b + delta^2 * n_a * n_b / n;
+ *   a rank whose count is 0 is skipped).  save_mean = mean, save_invstd = 1 / sqrt(M2 / n + eps) (biased variance);
+ *   running_mean / running_var (both may be NULL) are updated in place with `momentum` and the unbiased variance over the
+ *   TOTAL count, like torch; total_count_out (one double, device) = n.  Every rank computes this from the same bytes in the same
+ *   order: the outputs are bit-identical across ranks.  gamma and beta are accepted for symmetry with zsv_bn_fwd_train and are
+ *   not read (the apply passes form scale and shift themselves).  One launch, one thread per channel.
+ * zsv_bn_sync_apply: y = relu?(fma(x, scale, shift) (+ residual)), scale = gamma * save_invstd, shift = fma(-save_mean, scale,
+ *   beta) -- the expressions zsv_bn_fwd_train's finalize uses, so the mode-2 mask of the backward recomputes y's sign exactly.
+ * zsv_bn_sync_bwd_reduce: sums = double[2*C] = C local sums of g | C local sums of g * xhat, g = dy * mask, xhat =
+ *   (x - save_mean) * save_invstd.  fuse_relu 0, 1 (mask from y) or 2 (mask recomputed from x; y may be NULL), as zsv_bn_bwd.
+ * zsv_bn_sync_bwd_apply: dx = gamma * invstd * (g - sum_g / M - xhat * sum_gx / M) with the sums of sums_global (the
+ *   all-reduced buffer) and M = *total_count (a device pointer: no host read); d_residual = g when not NULL;
+ *   dgamma = sum_gx, dbeta = sum_g of sums_LOCAL (either may be NULL), as torch.nn.SyncBatchNorm: the gradient all-reduce
+ *   averages them afterwards.
+ *
+ * gamma, beta may be NULL (affine=False).  N == 0 is legal everywhere (no tensor is touched; sums are zeros, dgamma / dbeta 0).
+ * Alignment: fp32 tensors and vectors 4 bytes, each on its own; the double buffers (moments, gathered, sums, total_count)
+ * 8 bytes; the workspace 16.  Status: ZSV_E_BAD_SHAPE (N < 0, C <= 0, S <= 0, world <= 0, fuse_relu outside 0..2),
+ * ZSV_E_TOO_LARGE (N*C*S >= 2^31), ZSV_E_NULL, ZSV_E_WORKSPACE, ZSV_E_UNSUPPORTED (a misaligned pointer); all before any launch.
+ * zsv_bn_sync_workspace_bytes(N, C, S): bytes for moments and bwd_reduce on this shape (0 = illegal shape; 16 when N == 0). */
+size_t zsv_bn_sync_workspace_bytes(int32_t N, int32_t C, int32_t S);
+int zsv_bn_sync_moments(const float* x, int32_t N, int32_t C, int32_t S, double* moments, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int zsv_bn_sync_finalize(const double* gathered, int32_t world, int32_t C, const float* gamma, const float* beta,
+                         float* running_mean, float* running_var, float momentum, float eps, float* save_mean,
+                         float* save_invstd, double* total_count_out, void* stream);
+int zsv_bn_sync_apply(const float* x, int32_t N, int32_t C, int32_t S, const float* save_mean, const float* save_invstd,
+                      const float* gamma, const float* beta, const float* residual, int fuse_relu, float* y, void* stream);
+int zsv_bn_sync_bwd_reduce(const float* dy, const float* x, const float* y, int32_t N, int32_t C, int32_t S,
+                           const float* save_mean, const float* save_invstd, const float* gamma, const float* beta,
+                           int fuse_relu, double* sums, void* workspace, size_t workspace_bytes, void* stream);
+int zsv_bn_sync_bwd_apply(const float* dy, const float* x, const float* y, int32_t N, int32_t C, int32_t S,
+                          const float* save_mean, const float* save_invstd, const float* gamma, const float* beta,
+                          int fuse_relu, const double* sums_local, const double* sums_global, const double* total_count,
+                          float* dx, float* d_residual, float* dgamma, float* dbeta, void* stream);
+
 /* ---- elementwise -------------------------------------------------------------- */
 /* nn.ReLU / F.relu (resnet.py:49; network.py:147-166,614). */
 int zsv_relu_fwd(const float* x, float* y, int64_t n, void* stream);

@@ -72,6 +72,17 @@ SIGNATURES = {
     "zsv_bn_bwd_eval": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_float, c_int, _P, _P, _P, _P, _P,
                                 c_size_t, _P]),
     "zsv_bn_eval_coeffs": (c_int, [c_int32, _P, _P, _P, _P, c_float, _P, c_int32, _P]),
+    # BatchNorm statistics over all ranks (a collective runs between moments and finalize, and between bwd_reduce and bwd_apply):
+    # x, N, C, S, moments, workspace, bytes, stream / gathered, world, C, gamma, beta, running_mean, running_var, momentum, eps,
+    # save_mean, save_invstd, total_count_out, stream / x, N, C, S, save_mean, save_invstd, gamma, beta, residual, fuse_relu, y,
+    # stream / dy, x, y, N, C, S, save_mean, save_invstd, gamma, beta, fuse_relu, sums, workspace, bytes, stream / dy, x, y, N, C,
+    # S, save_mean, save_invstd, gamma, beta, fuse_relu, sums_local, sums_global, total_count, dx, d_residual, dgamma, dbeta, stream
+    "zsv_bn_sync_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "zsv_bn_sync_moments": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, c_size_t, _P]),
+    "zsv_bn_sync_finalize": (c_int, [_P, c_int32, c_int32, _P, _P, _P, _P, c_float, c_float, _P, _P, _P, _P]),
+    "zsv_bn_sync_apply": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int, _P, _P]),
+    "zsv_bn_sync_bwd_reduce": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int, _P, _P, c_size_t, _P]),
+    "zsv_bn_sync_bwd_apply": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "zsv_relu_fwd": (c_int, [_P, _P, c_int64, _P]),
     "zsv_relu_bwd": (c_int, [_P, _P, _P, c_int64, _P]),
     "zsv_relu_bwd_bias": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, c_size_t, _P]),

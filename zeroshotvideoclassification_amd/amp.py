@@ -831,6 +831,12 @@ def trunk_features(trunk: nn.Module, clips: torch.Tensor) -> torch.Tensor:
     Each BatchNorm keeps its own mode: eval-mode (frozen) ones normalise with their running statistics and leave them alone."""
     if not clips.is_cuda:
         raise RuntimeError("amp: MI355X HIP tensors only (there is no CPU fallback)")
+    from .layers import synchronizes
+    if any(synchronizes(m) for m in trunk.modules()):
+        # before anything is packed or launched: the channels-last bf16 BatchNorm (zsv_bn_cl_*) has no synchronised form and
+        # would quietly normalise with this rank's statistics
+        raise RuntimeError("amp: the bf16 training path does not synchronise BatchNorm statistics across ranks; a trunk with a "
+                           "SyncBatchNorm3d (ddp.convert_sync_batchnorm) trains on the fp32 path (autocast=False)")
     path = train_path_for(trunk)
     _lib.note_raw_write(parameters=False)               # BatchNorm running statistics are written through raw pointers
     return _TrunkBf16.apply(clips, path, torch.is_grad_enabled(), *path.params)

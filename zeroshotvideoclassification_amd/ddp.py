@@ -17,7 +17,14 @@ gradients (126.9 MB fp32), issued bucket by bucket while backward is still runni
 * parameters that never receive a gradient (the reference's unused Transformer encoder,
   ``model.fc``, ... -- SURVEY F5) are discovered in the first step and excluded, so nothing
   waits for them;
-* BatchNorm statistics stay per replica, as under DataParallel.
+* BatchNorm statistics stay per replica by default, as under DataParallel -- right for the reference's 22 clips
+  per GPU.  ``convert_sync_batchnorm(model)`` is the opt-in for a few clips per rank (``ir_csn_50``, long clips, large crops)
+  and for LARS / LAMB batches, whose statistics are meant to be the global batch's: it swaps every ``layers.BatchNorm3d`` for a
+  ``layers.SyncBatchNorm3d`` (same tensors), which in training mode takes mean and variance over all ranks -- the same passes
+  over the activations, plus one all_gather of 2C+1 doubles per forward and one all_reduce of 2C doubles per backward and layer.
+  fp32 path only (``amp.autocast()`` refuses such a trunk); with ``train_step(micro_batches=k)`` each micro-batch synchronises
+  across ranks on its own.  Measured on one device without the collectives (profiles/sync_bn.json); RCCL at world > 1 has
+  not run here, so the cost of the collectives is not measured.
 
 After ``finish_step()`` every live parameter's ``.grad`` IS a view of its bucket (the averaged values are not
 copied back), so ``optim.FusedAdam(..., grad_buckets=sync)`` walks the all-reduce buffers themselves with a
@@ -76,6 +83,34 @@ def broadcast_tensors(tensors, src: int = 0, group=None) -> int:
                 t.copy_(flat[off:off + n].view_as(t))
                 off += n
     return calls
+
+
+def convert_sync_batchnorm(model: torch.nn.Module, process_group=None) -> torch.nn.Module:
+    """``torch.nn.SyncBatchNorm.convert_sync_batchnorm`` for this package: every ``layers.BatchNorm3d`` in ``model`` becomes a
+    ``layers.SyncBatchNorm3d`` over ``process_group`` (default: the world), in place, holding the SAME Parameter and buffer
+    objects -- an optimizer or a ``GradientSync`` built earlier stays valid and ``state_dict`` keys do not change; the train /
+    eval mode of each layer is kept (hooks are not, as with torch's converter).  Layers that already are ``SyncBatchNorm3d``
+    are left alone: a second call is a no-op.  Returns ``model`` (a lone ``BatchNorm3d`` comes back as its replacement).
+    torch's own converter would hand the layers to ATen and lose the one-pass BN + residual + ReLU kernels."""
+    from .layers import BatchNorm3d, SyncBatchNorm3d
+
+    def converted(bn):
+        new = SyncBatchNorm3d(bn.num_features, bn.eps, bn.momentum, bn.affine, bn.track_running_stats, process_group,
+                              device="meta")
+        new._parameters, new._buffers = bn._parameters, bn._buffers      # the same Parameter / buffer objects, not copies
+        new.training = bn.training
+        return new
+
+    def plain(m):
+        return isinstance(m, BatchNorm3d) and not isinstance(m, SyncBatchNorm3d)
+
+    if plain(model):
+        return converted(model)
+    for parent in list(model.modules()):
+        for name, child in list(parent.named_children()):
+            if plain(child):
+                setattr(parent, name, converted(child))
+    return model
 
 
 class _Bucket:

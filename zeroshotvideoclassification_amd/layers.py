@@ -57,6 +57,45 @@ class BatchNorm3d(nn.BatchNorm3d):
         return self(x, stats=stats, defer=True)
 
 
+class SyncBatchNorm3d(BatchNorm3d):
+    """``BatchNorm3d`` whose training-mode batch statistics are taken over every rank of ``process_group`` (default: the world):
+    ``torch.nn.SyncBatchNorm`` for this package's fused passes.  Same parameters, buffers and ``state_dict`` keys as
+    ``BatchNorm3d`` (``ddp.convert_sync_batchnorm`` swaps the class and keeps the tensors).  It synchronises only in training
+    mode with ``torch.distributed`` initialised and a world size above 1 -- torch's rule; in every other case (eval mode, a
+    frozen backward, no process group, one rank) ``forward`` IS the parent's, bit for bit and with all its fusions.  fp32 only:
+    ``amp.autocast()`` refuses a trunk with a layer that would synchronise."""
+
+    def __init__(self, num_features, eps: float = 1e-5, momentum=0.1, affine: bool = True, track_running_stats: bool = True,
+                 process_group=None, device=None, dtype=None):
+        super().__init__(num_features, eps, momentum, affine, track_running_stats, device=device, dtype=dtype)
+        self.process_group = process_group
+
+    def synchronizes(self) -> bool:
+        """Would a forward in the current mode exchange statistics?"""
+        if not self.training:
+            return False
+        import torch.distributed as dist
+        return dist.is_available() and dist.is_initialized() and dist.get_world_size(self.process_group) > 1
+
+    def forward(self, x, residual=None, relu: bool = False, stats=None, skip_link=None, defer: bool = False):
+        """The parent's signature.  When synchronising: BatchNorm + residual + ReLU stay one apply pass and ``skip_link`` is
+        honoured; ``stats`` (the producing convolution's epilogue sums) are not used -- the moments pass shifts by a pivot,
+        the epilogue does not -- and ``defer=True`` is refused: the fold's backward is ``zsv_bn_bwd`` with this rank's sums
+        alone (``resnet._run_chain`` asks a synchronising layer for neither)."""
+        if not self.synchronizes():
+            return super().forward(x, residual=residual, relu=relu, stats=stats, skip_link=skip_link, defer=defer)
+        if x.dim() != 5:
+            raise ValueError(f"expected 5D input (got {x.dim()}D input)")
+        if defer:
+            raise RuntimeError("SyncBatchNorm3d: a synchronising layer has no deferred fold into the next convolution")
+        return ops.sync_bn_module_act(x, self, residual=residual, relu=relu, skip_link=skip_link)
+
+
+def synchronizes(m: nn.Module) -> bool:
+    """True for a ``SyncBatchNorm3d`` that would exchange statistics in its current mode (False for every other module)."""
+    return isinstance(m, SyncBatchNorm3d) and m.synchronizes()
+
+
 class ReLU(nn.ReLU):
     """``inplace`` is accepted for signature compatibility; the kernel writes a fresh tensor and
     keeps only the output for backward, which is what inplace ReLU keeps too."""

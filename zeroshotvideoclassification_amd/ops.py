@@ -1110,6 +1110,128 @@ def bn_module_act(x, bn: torch.nn.Module, residual=None, relu=False, stats=None,
 
 
 # ------------------------------------------------------------------------------------------
+# BatchNorm with batch statistics over all ranks (torch.nn.SyncBatchNorm): the same passes over the activations as
+# _BatchNormAct, cut where the ranks talk -- one all_gather of 2C+1 doubles in the forward, one all_reduce of 2C doubles in the
+# backward (include/zsv_hip.h: zsv_bn_sync_*).
+class _SyncBatchNormAct(Function):
+    """Training-mode ``BatchNorm3d`` (+ ``out += residual``) (+ ReLU) whose mean and variance are those of the batch on ALL ranks
+    of ``group``.  Both collectives are issued from the thread and on the stream the kernels around them run on (the forward's
+    in ``forward``, autograd's in ``backward``), as synchronous ``torch.distributed`` calls on HIP tensors: RCCL orders them
+    on that stream, gloo blocks the host until the result is in place."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, residual, momentum, eps, relu, group, skip_link=None):
+        import torch.distributed as dist
+        _require(x, gamma, beta, running_mean, running_var, residual)
+        if x.dim() < 2:
+            raise RuntimeError("sync_batch_norm_act expects an (N, C, ...) tensor")
+        x = x.contiguous()
+        n, c = int(x.shape[0]), int(x.shape[1])
+        s = 1
+        for v in x.shape[2:]:
+            s *= int(v)
+        if residual is not None:
+            if residual.shape != x.shape:
+                raise RuntimeError(f"residual shape {tuple(residual.shape)} != {tuple(x.shape)}")
+            residual = residual.contiguous()
+        lib = _lib.load()
+        world = dist.get_world_size(group)
+        y = torch.empty_like(x)
+        moments = torch.empty(2 * c + 1, dtype=torch.float64, device=x.device)
+        gathered = torch.empty((world, 2 * c + 1), dtype=torch.float64, device=x.device)
+        save_mean = torch.empty(c, dtype=torch.float32, device=x.device)
+        save_invstd = torch.empty(c, dtype=torch.float32, device=x.device)
+        count = torch.empty(1, dtype=torch.float64, device=x.device)
+        nbytes = lib.zsv_bn_sync_workspace_bytes(n, c, s)
+        ws = _workspace(nbytes, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.zsv_bn_sync_moments(x.data_ptr(), n, c, s, moments.data_ptr(), _ptr(ws), nbytes, _stream()),
+                       "zsv_bn_sync_moments")
+            dist.all_gather(list(gathered.unbind(0)), moments, group=group)
+            _lib.check(lib.zsv_bn_sync_finalize(gathered.data_ptr(), world, c, _ptr(gamma), _ptr(beta), _ptr(running_mean),
+                                                _ptr(running_var), float(momentum), float(eps), save_mean.data_ptr(),
+                                                save_invstd.data_ptr(), count.data_ptr(), _stream()), "zsv_bn_sync_finalize")
+            if running_mean is not None:
+                _lib.note_raw_write(parameters=False)          # running statistics written behind the version counters
+            _lib.check(lib.zsv_bn_sync_apply(x.data_ptr(), n, c, s, save_mean.data_ptr(), save_invstd.data_ptr(), _ptr(gamma),
+                                             _ptr(beta), _ptr(residual), 1 if relu else 0, y.data_ptr(), _stream()),
+                       "zsv_bn_sync_apply")
+        ctx.relu = bool(relu)
+        ctx.has_res = residual is not None
+        ctx.dims = (n, c, s)
+        ctx.group = group
+        ctx.skip_link = skip_link if (skip_link is not None and skip_link.armed and residual is not None) else None
+        # with a ReLU but no residual the backward recomputes the mask from x: y need not be kept
+        ctx.save_for_backward(x, gamma, beta, save_mean, save_invstd, count, y if (relu and residual is not None) else None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        import torch.distributed as dist
+        x, gamma, beta, save_mean, save_invstd, count, y = ctx.saved_tensors
+        n, c, s = ctx.dims
+        lib = _lib.load()
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        want_res = ctx.has_res and ctx.needs_input_grad[5]
+        # without a fused ReLU the residual gradient is dy itself
+        dres = torch.empty_like(x) if (want_res and ctx.relu) else None
+        mode = 0 if not ctx.relu else (1 if ctx.has_res else 2)
+        sums_local = torch.empty(2 * c, dtype=torch.float64, device=x.device)
+        dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
+        dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
+        nbytes = lib.zsv_bn_sync_workspace_bytes(n, c, s)
+        ws = _workspace(nbytes, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.zsv_bn_sync_bwd_reduce(dy.data_ptr(), x.data_ptr(), _ptr(y), n, c, s, save_mean.data_ptr(),
+                                                  save_invstd.data_ptr(), _ptr(gamma), _ptr(beta), mode, sums_local.data_ptr(),
+                                                  _ptr(ws), nbytes, _stream()), "zsv_bn_sync_bwd_reduce")
+            sums_global = sums_local.clone()
+            dist.all_reduce(sums_global, op=dist.ReduceOp.SUM, group=ctx.group)
+            # dgamma / dbeta are the LOCAL sums, as torch.nn.SyncBatchNorm returns them: the gradient exchange averages them
+            _lib.check(lib.zsv_bn_sync_bwd_apply(dy.data_ptr(), x.data_ptr(), _ptr(y), n, c, s, save_mean.data_ptr(),
+                                                 save_invstd.data_ptr(), _ptr(gamma), _ptr(beta), mode, sums_local.data_ptr(),
+                                                 sums_global.data_ptr(), count.data_ptr(), dx.data_ptr(), _ptr(dres),
+                                                 dgamma.data_ptr(), dbeta.data_ptr(), _stream()), "zsv_bn_sync_bwd_apply")
+        if want_res and not ctx.relu:
+            dres = dy
+        if want_res and ctx.skip_link is not None:
+            # identity shortcut: the first convolution of the block adds this in its dgrad epilogue (as _BatchNormAct)
+            ctx.skip_link.dres = dres
+            dres = None
+        return (dx if ctx.needs_input_grad[0] else None, dgamma if ctx.needs_input_grad[1] else None,
+                dbeta if ctx.needs_input_grad[2] else None, None, None, dres if want_res else None,
+                None, None, None, None, None)
+
+
+def sync_batch_norm_act(x, gamma, beta, running_mean, running_var, residual=None, momentum=0.1, eps=1e-5, relu=False,
+                        group=None, skip_link=None):
+    """Training-mode ``batch_norm_act`` with the batch statistics of every rank of ``group`` (default: the world); every rank
+    of the group must make the call.  ``gamma`` / ``beta`` / the running statistics may be None as in ``batch_norm_act``.
+    The parameter gradients are this rank's own sums (``torch.nn.SyncBatchNorm``'s convention)."""
+    import torch.distributed as dist
+    if momentum is None:
+        raise RuntimeError("cumulative-average BatchNorm (momentum=None) is not supported")
+    if not (dist.is_available() and dist.is_initialized()):
+        raise RuntimeError("sync_batch_norm_act: torch.distributed is not initialised (init_process_group first)")
+    return _SyncBatchNormAct.apply(x, gamma, beta, running_mean, running_var, residual, float(momentum), float(eps), bool(relu),
+                                   group, skip_link)
+
+
+def sync_bn_module_act(x, bn: torch.nn.Module, residual=None, relu=False, skip_link=None):
+    """``bn_module_act`` for a ``layers.SyncBatchNorm3d`` that synchronises (training mode): torch's running-statistics
+    semantics, statistics over ``bn.process_group``."""
+    if bn.momentum is None:
+        raise RuntimeError("cumulative-average BatchNorm (momentum=None) is not supported")
+    if bn.track_running_stats and bn.num_batches_tracked is not None:
+        count_batch(bn)
+    rm = bn.running_mean if bn.track_running_stats else None
+    rv = bn.running_var if bn.track_running_stats else None
+    return sync_batch_norm_act(x, bn.weight, bn.bias, rm, rv, residual, bn.momentum, bn.eps, relu, bn.process_group, skip_link)
+
+
+# ------------------------------------------------------------------------------------------
 class _ReLU(Function):
     """nn.ReLU / F.relu (resnet.py:49,95,98)."""
 

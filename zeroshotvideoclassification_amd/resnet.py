@@ -25,7 +25,7 @@ from torch import Tensor, nn
 import os
 
 from . import ops
-from .layers import AdaptiveAvgPool3d, BatchNorm3d, Conv3d, Linear, ReLU
+from .layers import AdaptiveAvgPool3d, BatchNorm3d, Conv3d, Linear, ReLU, synchronizes
 
 __all__ = ["r3d_18", "mc3_18", "r2plus1d_18"]          # the reference's list; `ir_csn_50` is this package's own factory
 
@@ -66,6 +66,13 @@ def _run_chain(mods: Sequence[nn.Module], x: Tensor, want_stats: bool = False):
         nxt = mods[i + 1] if i + 1 < n else None
         if isinstance(m, BatchNorm3d):
             relu = isinstance(nxt, nn.ReLU) and not _has_hooks(m, nxt)      # hooked: BatchNorm and ReLU run (and are observed) one by one
+            if synchronizes(m):
+                # statistics over all ranks (layers.SyncBatchNorm3d): BN + ReLU stay one pass; never the fold into the next
+                # convolution below (its backward is zsv_bn_bwd with this rank's sums alone)
+                x = m(x, relu=relu)
+                stats = None
+                i += 2 if relu else 1
+                continue
             after = mods[i + 2] if (relu and i + 2 < n) else None
             if relu and ((m.training and m.momentum is not None) or _frozen_in_graph(m, x, after)) and type(after) is Conv3d \
                     and x.is_contiguous() and not _has_hooks(m, nxt, after) and after.pre_supported(x.shape):
@@ -74,7 +81,7 @@ def _run_chain(mods: Sequence[nn.Module], x: Tensor, want_stats: bool = False):
                 # BatchNorm's affine comes from its running statistics)
                 handle, coef = m(x, stats=stats, defer=True)
                 after_next = mods[i + 3] if i + 3 < n else None
-                feeds = isinstance(after_next, BatchNorm3d) and after_next.training
+                feeds = isinstance(after_next, BatchNorm3d) and after_next.training and not synchronizes(after_next)
                 x, stats = after.forward_pre(handle, coef, want_stats=True) if (feeds or (i + 3 == n and want_stats)) \
                     else (after.forward_pre(handle, coef), None)
                 i += 3
@@ -83,7 +90,7 @@ def _run_chain(mods: Sequence[nn.Module], x: Tensor, want_stats: bool = False):
             stats = None
             i += 2 if relu else 1
             continue
-        feeds_bn = isinstance(nxt, BatchNorm3d) and nxt.training
+        feeds_bn = isinstance(nxt, BatchNorm3d) and nxt.training and not synchronizes(nxt)     # (a synchronising layer takes its own moments)
         last = i + 1 == n
         x, stats = _call(m, x, feeds_bn or (last and want_stats))
         i += 1
@@ -197,7 +204,7 @@ class BasicBlock(nn.Module):
             x.__dict__.pop("_zsv_skip_link", None)           # (not consumed: conv1 does not start with a Conv3d)
         if down is not None:
             x.__dict__.pop("_zsv_down_link", None)
-        out, stats = _call(self.conv2[0], out, fused_tail and tail.training)
+        out, stats = _call(self.conv2[0], out, fused_tail and tail.training and not synchronizes(tail))
         if down is not None and down.armed:
             x._zsv_down_src = down
         residual = x if self.downsample is None else self.downsample(x)
@@ -231,7 +238,7 @@ class Bottleneck(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         out = self.conv2(self.conv1(x))
-        out, stats = _call(self.conv3[0], out, self.conv3[1].training)
+        out, stats = _call(self.conv3[0], out, self.conv3[1].training and not synchronizes(self.conv3[1]))
         residual = x if self.downsample is None else self.downsample(x)
         return self.conv3[1](out, residual=residual, relu=True, stats=stats)
 
